@@ -7,10 +7,16 @@ Everything is resident in HBM before the timed region; frames are strictly depen
 filter frame t produced).  One process per GPU, one independent sequence per GPU (weak scaling, no data-path
 collective); RCCL is used only for the barrier and the end-of-batch (frames, seconds) gather.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: re-executes itself under torch.distributed.run)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                                                                 (N > 1: re-executes itself under torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0.  Besides the contract fields:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times exactly --steps frames and prints the contract fields
+(metric, value, unit, higher_is_better, dtype, ms_per_step) with the launch configuration and the per-rank record; nothing else.
+--dump-outputs DIR: after the timed frames, rank 0 writes what the last timed frame left for its caller (filter, scores, arg-max
+peak, memory boxes and weights, the memory slot it wrote) as DIR/<name>.npy in float32; the inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
+--full adds the legs below (each can still be switched off by its --no-* option):
   roofline        dominant feature-pass kernel: algorithmic bytes per launch / its average launch duration.  The
                   duration is rocprofv3's (`--kernel-trace --stats` of this very command in a child process, parsed
                   here -- the same tool that writes profiles/*kernel_stats.csv, so the two agree by construction), taken
@@ -442,6 +448,26 @@ class _DryState:
         return 2 * num_iter * 4 * self.n * c["C"] * c["H"] * c["W"]
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(st, last_slot, out_dir):
+    """What the last timed frame leaves for its caller, as float32 .npy files: the solved filter, its score map, the arg-max peak,
+    the memory's boxes and weights, and the memory slot that frame wrote."""
+    if isinstance(st, _DryState):
+        arrays = {"state": st.acc}
+    else:
+        arrays = {"filter": st.filter, "scores": st.scores, "peak": st.peak, "mem_bb": st.mem_bb,
+                  "sample_weight": st.sample_weight, "mem_feat_last_slot": st.mem_feat[last_slot]}
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET_BYTES}-byte budget")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -460,11 +486,17 @@ def main():
     ap.add_argument("--no-other", action="store_true", help="skip the other BASELINE workloads and the end-to-end leg")
     ap.add_argument("--no-clock-warmup", action="store_true",
                     help="skip the ~40 ms of idempotent pass replays in front of the warm-up frames (rounds 1-3 protocol)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the roofline / repeats / multi-sequence / head / other-workload / baseline / end-to-end legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed frame computed as DIR/<name>.npy (float32)")
     ap.add_argument("--profile-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--profile-mode", default="graph", choices=("graph", "eager"), help=argparse.SUPPRESS)
     ap.add_argument("--workload", default="dimp50", choices=("dimp50", "prdimp50"),
                     help="dimp50 = BASELINE configs[1] (the metric's configuration); prdimp50 = configs[2]'s per-GPU workload")
     args = ap.parse_args()
+    if not args.full:                                          # a plain run: the headline and nothing else
+        args.no_roofline = args.no_other = args.no_cpu_baseline = args.no_gpu_baseline = True
 
     # PT_BENCH_DRYRUN=1: walk this file's control flow (launcher re-exec, rank wiring, build-on-rank-0 + barrier, warm-up, barrier-
     # bracketed timed region, closing barrier, gather, ONE JSON line on rank 0) on a box WITHOUT a GPU: gloo instead of RCCL, a stub
@@ -614,6 +646,8 @@ def main():
         if dist is not None:
             dist.barrier()                                     # closing barrier of the bracket: not part of anybody's K frames
         elapsed_closed = time.perf_counter() - t0              # rounds 1-3 bracket: this rank's clock incl. the closing barrier
+        if args.dump_outputs and rank == 0:                    # before the repeats below move the state on
+            dump_outputs(st, (Wm + K - 1) % n, args.dump_outputs)
 
         # the same K-step region again (state keeps advancing; same graphs): where the reported value sits in this box's spread
         repeats = []
@@ -695,7 +729,7 @@ def main():
                 out["multi_sequence"] = {"error": f"{type(exc).__name__}: {exc}"[:300]}
         if world == 1 and cfg_name == "dimp50" and not args.no_roofline:
             out["head_inclusive"] = head_inclusive(cfg, n, dev, stream)
-        if world == 1 and cfg_name == "dimp50":
+        if world == 1 and cfg_name == "dimp50" and args.full:
             if not args.no_other:
                 out["other_workloads"] = workloads.all_other(dev)
             out.update(baselines(cfg, n, dev, not args.no_cpu_baseline, not args.no_gpu_baseline))

@@ -63,3 +63,43 @@ def test_committed_counter_summary_is_this_rounds():
         assert os.path.exists(os.path.join(ROOT, r["source"].split(":")[0]))
     alg = 4 * 50 * 512 * 18 * 18
     assert 1.0 <= rec["dimp50"]["k_corr2"]["hbm_bytes_per_launch"] / alg < 1.1       # traffic = 1.03 x the algorithmic bytes
+
+
+def _dry_bench(args, tmp_path):
+    import subprocess
+    env = dict(os.environ, PT_BENCH_DRYRUN="1", OMP_NUM_THREADS="1")
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + args, cwd=str(tmp_path), env=env,
+                         capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, res.stdout[:500]
+    return json.loads(lines[0])
+
+
+def test_plain_run_times_exactly_steps_and_dumps_reproducible_outputs(tmp_path):
+    """A plain run times --steps frames, reports ms_per_step, runs none of the --full legs, and --dump-outputs writes float32 .npy
+    files that are identical from run to run with the same arguments."""
+    import numpy as np
+    outs = []
+    for k in range(2):
+        d = _dry_bench(["--steps", "13", "--warmup", "3", "--dump-outputs", str(tmp_path / f"o{k}")], tmp_path)
+        assert d["steps"] == 13 and d["per_rank"][0]["frames"] == 13
+        assert abs(d["ms_per_step"] - 1e3 * d["per_rank"][0]["seconds"] / 13) < 1e-3
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype"):
+            assert key in d
+        assert d["roofline"] is None
+        assert not {"repeats", "multi_sequence", "head_inclusive", "other_workloads", "cpu_baseline", "gpu_stock_baseline",
+                    "end_to_end", "reference_bundle"} & set(d)
+        files = sorted(os.listdir(tmp_path / f"o{k}"))
+        assert files and all(f.endswith(".npy") for f in files)
+        outs.append({f: np.load(tmp_path / f"o{k}" / f) for f in files})
+    assert outs[0].keys() == outs[1].keys()
+    for f, a in outs[0].items():
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, outs[1][f]), f
+
+
+def test_full_option_is_accepted():
+    d = _dry_bench(["--steps", "7", "--warmup", "2", "--full"], ROOT)
+    assert d["steps"] == 7 and d["per_rank"][0]["frames"] == 7 and "reference_bundle" in d

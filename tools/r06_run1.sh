@@ -24,4 +24,4 @@ for n in 8 32; do
   rm -rf $OUT/p_lwl
 done
 bash tools/pmc_head.sh r06a/head_pmc > /dev/null 2>&1; cat $OUT/head_pmc/pmc_head.txt
-python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cut -c1-600 $OUT/bench.json
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cut -c1-600 $OUT/bench.json

@@ -35,4 +35,4 @@ cat $OUT/track_device_time.txt
 rm -rf $OUT/p_trk
 python -B tests/profile_installed_track.py --frames 40 --out $OUT/installed_track_breakdown.txt > /dev/null 2> $OUT/track_profile.err; tail -3 $OUT/track_profile.err; head -12 $OUT/installed_track_breakdown.txt
 # configs[2]'s per-GPU workload as the headline under the launcher (1 rank, nccl)
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --workload prdimp50 --steps 20 --warmup 5 --no-other > $OUT/torchrun_prdimp50.json 2> $OUT/torchrun_prdimp50.err; echo "torchrun rc=$?"; tail -1 $OUT/torchrun_prdimp50.json | cut -c1-400
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --workload prdimp50 --steps 20 --warmup 5 --full --no-other > $OUT/torchrun_prdimp50.json 2> $OUT/torchrun_prdimp50.err; echo "torchrun rc=$?"; tail -1 $OUT/torchrun_prdimp50.json | cut -c1-400
