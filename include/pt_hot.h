@@ -123,6 +123,30 @@ int pt_sd_solve_batch_f32(const pt_sd_params* p, int S, const float* const* w_in
                           int num_iter, float* const* w_iters, float* const* losses, void* const* ws, size_t ws_bytes_each,
                           void* stream, void* const* aux_streams, int n_aux);
 
+/* GNSteepestDescent.forward (ltr/models/meta/steepestdescent.py:32-105) on LinearFilterHinge
+ * (ltr/models/target_classifier/residual_modules.py:88-135), one sequence -- DiMP-simple's and the RTS classifier's online solver:
+ *   m = min((label > hinge_threshold) + activation_leak, 1); residuals [sw*(act(F w, m) - m*label), filter_reg*w];
+ *   act = LeakyReluPar (PT_ACT_RELU) or BentIdentPar(act_param) (PT_ACT_BENTPAR); sw = sqrt(sample_weight[i]), sqrt(1/n) when NULL;
+ *   alpha = |g|^2 / max(|J g|^2 + steplength_reg |g|^2, 1e-8) with the filter_reg^2 |g|^2 term inside |J g|^2; step length 1.
+ * label (n,OH,OW), OH = H + (K+1)%2; w_in (C,K,K) is not modified; w_iters receives all num_iter+1 iterates;
+ * losses (num_iter+1 floats) may be NULL, else losses[t] = (sum r^2 + filter_reg^2 |w_t|^2) / (n*OH*OW + C*K*K).
+ * Requires K*K <= 16 and num_iter <= 64. */
+typedef struct {
+    int   score_act;       /* PT_ACT_* */
+    float act_param;       /* BentIdentPar b */
+    float hinge_threshold;
+    float activation_leak;
+    float filter_reg;      /* the residual's filter_reg (its square is the regulariser) */
+    float steplength_reg;  /* GNSteepestDescent.steplength_reg */
+} pt_gn_hinge_params;
+size_t pt_gn_hinge_ws_bytes(int n, int C, int H, int W, int K);
+int pt_gn_hinge_solve_f32(const pt_gn_hinge_params* p, const float* w_in, const float* feat, long feat_stride_n,
+                          const float* label, const float* sample_weight, int n, int C, int H, int W, int K, int num_iter,
+                          float* w_iters, float* losses, void* ws, size_t ws_bytes, void* stream);
+/* Route pt_gn_hinge_solve_f32 takes for exactly these operands -- the solve's own predicate, evaluated on the host, nothing launched:
+ * 1 = the XCD-aligned fast route, 0 = the generic one (also every map of more than 1024 elements). */
+int pt_gn_hinge_route(const float* feat, long feat_stride_n, const float* w_in, const float* w_iters, int n, int C, int H, int W, int K);
+
 /* ------------------------------------------------------------------------------------------------
  * Multi-filter filter layer + LWL few-shot learner -- ltr/models/layers/filter.py (5-D `filter` / `input` branches),
  * ltr/models/meta/steepestdescent.py, ltr/models/lwl/loss_residual_modules.py

@@ -9,7 +9,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PT_HOT_LIB", os.path.join(_HERE, "libpt_hot.so"))   # override: experiments only
-SOURCES = ["filter_kernels.hip", "fast_passes.hip", "sd_solver.hip", "mf_kernels.hip", "lwl_solver.hip", "atom_cg.hip", "atom_gn.hip", "tomp.hip", "localize.hip", "iou_refine.hip", "prroi.hip", "patch.hip", "frame_full.hip", "api.hip"]
+SOURCES = ["filter_kernels.hip", "fast_passes.hip", "sd_solver.hip", "mf_kernels.hip", "lwl_solver.hip", "atom_cg.hip", "atom_gn.hip", "tomp.hip", "localize.hip", "iou_refine.hip", "prroi.hip", "patch.hip", "frame_full.hip", "api.hip", "gn_hinge.hip"]
 HEADERS = ["common.h", "pt_internal.h", "rbuild.h", "sd_common.h", "mfma_gemm.h", "prroi_dev.h", "localize_dev.h", "frame_mid.h", os.path.join("..", "..", "include", "pt_hot.h")]
 # kernarg preload: leading scalar kernel parameters arrive in SGPRs at wave launch (kernels that take them that way only)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-pass-failed", "-mllvm", "-amdgpu-kernarg-preload-count=14"]
@@ -93,7 +93,14 @@ EXPORTS = [
     "pt_track_frame_full_ws_bytes", "pt_track_frame_full_f32", "pt_track_frame_full_launch_f32", "pt_host_buffer_forget",
     "pt_track_frame_full_dyn_bytes", "pt_track_frame_full_dyn_fill_f32", "pt_host_wait_word_f32",
     "pt_sd_solve_batch_f32", "pt_stream_probe_f32",
+    "pt_gn_hinge_ws_bytes", "pt_gn_hinge_solve_f32", "pt_gn_hinge_route",
 ]
+
+
+class GnHingeParams(ctypes.Structure):
+    """`pt_gn_hinge_params` of include/pt_hot.h."""
+    _fields_ = [("score_act", ctypes.c_int)] + [(n, ctypes.c_float) for n in ("act_param", "hinge_threshold", "activation_leak",
+                                                                             "filter_reg", "steplength_reg")]
 
 
 class FramePending(ctypes.Structure):
@@ -332,6 +339,12 @@ def lib():
     L.pt_stream_probe_f32.argtypes = [vp, sz, vp, i, vp]
     L.pt_host_buffer_forget.restype = None
     L.pt_host_buffer_forget.argtypes = [vp]
+    L.pt_gn_hinge_ws_bytes.restype = sz
+    L.pt_gn_hinge_ws_bytes.argtypes = [i] * 5
+    L.pt_gn_hinge_solve_f32.restype = i
+    L.pt_gn_hinge_solve_f32.argtypes = [ctypes.POINTER(GnHingeParams), vp, vp, l, vp, vp] + [i] * 6 + [vp, vp, vp, sz, vp]
+    L.pt_gn_hinge_route.restype = i
+    L.pt_gn_hinge_route.argtypes = [vp, l, vp, vp] + [i] * 5
     L.pt_sample_patch_f32.restype = i
     L.pt_sample_patch_f32.argtypes = [vp, i, i, i, ctypes.POINTER(PatchGeom), i, vp, i, i, vp]
     L.pt_augment_patches_f32.restype = i

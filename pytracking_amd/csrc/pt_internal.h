@@ -80,6 +80,13 @@ static inline bool pt_fast_usable(const PtFast& f, const void* feat, long stride
     return f.ok && ((uintptr_t)feat % 16) == 0 && (stride_n % 4) == 0 && (long)f.n * stride_n * 4 < (1L << 31) &&
            ((uintptr_t)src % 16) == 0 && (f.KK != 16 || ((uintptr_t)filt % 16) == 0);
 }
+// The route of the steepest-descent solve (pt_sd_solve_impl; pt_gn_hinge_route reports it): the XCD-aligned fast path also needs a
+// 16-byte aligned iterate buffer and <= 16 adjoint slices; with a caller-supplied label map (gn_hinge.hip) its init stage runs one
+// element per thread, so maps of more than 1024 elements take the generic route.
+static inline bool pt_sd_route_fast(const PtFast& f, const void* feat, long stride_n, const void* w_in, const void* w_iters,
+                                    const void* src, bool label_map) {
+    return pt_fast_usable(f, feat, stride_n, w_in, src) && ((uintptr_t)w_iters % 16) == 0 && f.KSPL <= 16 && (!label_map || f.OO <= 1024);
+}
 static inline size_t pt_fast_spart_floats(const PtFast& p) { return (size_t)16 * p.n * p.OO; }   // room for KSC = 16
 static inline size_t pt_fast_gpart_floats(const PtFast& p) { return (size_t)p.KSPL * p.C * p.KK; }
 // spart[x][i][OH*OW], x = XCD channel range (8 slices).  `slot`/`src`/`copy_dst`: sample `slot` is read from `src`
@@ -149,10 +156,18 @@ struct PtClsFin {
 // left its last update pending (that many iterations; its step length and reg + alpha_eps): it is applied in the prologue of this
 // solve's first correlation and stored to w_final.  `defer`: this solve leaves ITS last update pending (pend is filled) instead of
 // launching it.  Both need the fast path (PT_ERR_UNSUPPORTED otherwise, nothing queued) and w_final == w_in (the chain's filter).
+// `lmap` (gn_hinge.hip, kind PT_SD_DIMP only): label and mask come from this caller-supplied map (hinge residual) instead of the
+// radial look-up tables; `bb` is then unused and may be null.  No classification epilogue, source override or chain with it.
+struct PtLabelMap { const float* label; float thr, leak; };
+#define PT_SD_MAX_ITER 64
 int pt_sd_solve_impl(const pt_sd_params* prm, const float* w_in, const float* feat, long feat_stride_n, const float* bb,
                      const float* sample_weight, int n, int C, int H, int W, int K, int num_iter, float* w_iters,
                      float* losses, void* ws, size_t ws_bytes, hipStream_t st, bool copy_w0, float* w_final,
-                     const PtClsFin* cls, const float* src, pt_frame_pending* pend = nullptr, bool defer = false);
+                     const PtClsFin* cls, const float* src, pt_frame_pending* pend = nullptr, bool defer = false,
+                     const PtLabelMap* lmap = nullptr);
+// init stages of the hinge residual (gn_hinge.hip): fast route (replaces k_fast_init2) and generic route (replaces k_sd_maps)
+int pt_launch_gn_hinge_init2(const SdArgs& a, const PtLabelMap& lm, hipStream_t st);
+int pt_launch_gn_hinge_maps(const SdArgs& a, const PtLabelMap& lm, hipStream_t st);
 // the pending update on its own (end of a chain)
 int pt_sd_flush_impl(const pt_frame_pending* pend, float* filter, int n, int C, int H, int W, int K, float* w_iters, void* ws,
                      size_t ws_bytes, hipStream_t st);

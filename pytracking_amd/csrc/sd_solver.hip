@@ -580,8 +580,6 @@ __global__ __launch_bounds__(512) void k_fast_final(const float* __restrict__ wp
     for (int e2 = e + blockDim.x; e2 < min(CKK, (i + 1) * chunk); e2 += blockDim.x) wn[e2] = sd_final_apply(wp[e2], g[e2], astep);
 }
 
-#define PT_SD_MAX_ITER 64
-
 extern "C" size_t pt_sd_ws_bytes(int n, int C, int H, int W, int K) {
     if (n <= 0 || C <= 0 || H <= 0 || W <= 0 || K <= 0) return 0;
     const int OH = H + (K + 1) % 2, OW = W + (K + 1) % 2;
@@ -639,7 +637,7 @@ static int sd_pending_operands(const PtFast& f, const pt_frame_pending* pend, co
 static int sd_solve_fast(const PtFast& f, const pt_sd_params* prm, const float* w_in, const float* feat, long stride_n,
                          const float* bb, const float* sample_weight, int num_iter, float* w_iters, float* losses,
                          void* ws, size_t ws_bytes, hipStream_t st, bool copy_w0, float* w_final, const PtClsFin* cls,
-                         const float* src, pt_frame_pending* pend, bool defer) {
+                         const float* src, pt_frame_pending* pend, bool defer, const PtLabelMap* lmap) {
     SdArgs a;
     float* sbuf[2];
     int rc = sd_fast_setup(f, prm, w_in, bb, sample_weight, w_iters, w_final, ws, ws_bytes, a, sbuf);
@@ -691,10 +689,12 @@ static int sd_solve_fast(const PtFast& f, const pt_sd_params* prm, const float* 
     // 6-7 samples (8 slice loads + the look-up-table arithmetic per element, six elements per lane): that pass is 15.3 us instead of
     // 7.9 and the frame 4.7 us SLOWER.  Opt-in for experiments: PT_SD_FUSE_INIT=1 in the environment (read per solve).
     const bool fuse_env = std::getenv("PT_SD_FUSE_INIT") && std::getenv("PT_SD_FUSE_INIT")[0] == '1';
-    const bool fuse_init = PT_SD_FUSE_INIT && fuse_env && pw2 && num_iter > 0 && !want_loss && !(cls && cls->after_init) &&
+    const bool fuse_init = !lmap && PT_SD_FUSE_INIT && fuse_env && pw2 && num_iter > 0 && !want_loss && !(cls && cls->after_init) &&
                            pt_adj2_init_fusable(f, a);
     if (fuse_init) {
         if (n > 65535 || a.OO > 65535) return PT_ERR_UNSUPPORTED;
+    } else if (lmap) {
+        if ((rc = pt_launch_gn_hinge_init2(a, *lmap, st))) return rc;
     } else if (pw2) {
         if (n > 65535 || a.OO > 65535 || a.OW > 4095 || a.K > 15 || a.num_bins > 65535 || n >= 0xfffff) return PT_ERR_UNSUPPORTED;
         InitLate il;
@@ -768,20 +768,21 @@ static int sd_solve_fast(const PtFast& f, const pt_sd_params* prm, const float* 
 int pt_sd_solve_impl(const pt_sd_params* prm, const float* w_in, const float* feat, long feat_stride_n, const float* bb,
                      const float* sample_weight, int n, int C, int H, int W, int K, int num_iter, float* w_iters,
                      float* losses, void* ws, size_t ws_bytes, hipStream_t st, bool copy_w0, float* w_final,
-                     const PtClsFin* cls, const float* src, pt_frame_pending* pend, bool defer) {
-    if (!prm || !w_in || !feat || !bb || !w_iters || !ws) return PT_ERR_NULL;
+                     const PtClsFin* cls, const float* src, pt_frame_pending* pend, bool defer, const PtLabelMap* lmap) {
+    if (!prm || !w_in || !feat || !(bb || lmap) || !w_iters || !ws) return PT_ERR_NULL;
     if (n <= 0 || C <= 0 || H <= 0 || W <= 0 || K <= 0 || num_iter < 0) return PT_ERR_SHAPE;
     if (K * K > 16 || num_iter > PT_SD_MAX_ITER) return PT_ERR_UNSUPPORTED;
     if (feat_stride_n < (long)C * H * W) return PT_ERR_SHAPE;
-    if (prm->kind == PT_SD_DIMP && (!prm->label_lut || !prm->mask_lut || !prm->spatial_lut || prm->num_bins < 1))
+    if (lmap && (prm->kind != PT_SD_DIMP || !lmap->label || cls || src || defer || pend)) return PT_ERR_UNSUPPORTED;
+    if (prm->kind == PT_SD_DIMP && !lmap && (!prm->label_lut || !prm->mask_lut || !prm->spatial_lut || prm->num_bins < 1))
         return PT_ERR_NULL;
     if (prm->kind < PT_SD_DIMP || prm->kind > PT_SD_PRDIMP) return PT_ERR_UNSUPPORTED;
     const int OH = H + (K + 1) % 2, OW = W + (K + 1) % 2;               // optimizer.py:105
     {
         PtFast f = pt_fast_plan(n, C, H, W, K, K, OH, OW);
-        if (pt_fast_usable(f, feat, feat_stride_n, w_in, src) && ((uintptr_t)w_iters % 16) == 0 && f.KSPL <= 16)
+        if (pt_sd_route_fast(f, feat, feat_stride_n, w_in, w_iters, src, lmap != nullptr))
             return sd_solve_fast(f, prm, w_in, feat, feat_stride_n, bb, sample_weight, num_iter, w_iters, losses, ws,
-                                 ws_bytes, st, copy_w0, w_final, cls, src, pend, defer);
+                                 ws_bytes, st, copy_w0, w_final, cls, src, pend, defer, lmap);
     }
     if (defer || (pend && pend->iters > 0)) return PT_ERR_UNSUPPORTED;   // frame chains exist on the fast path only
     if (src) return PT_ERR_UNSUPPORTED;                                 // source override exists on the fast path only
@@ -824,8 +825,12 @@ int pt_sd_solve_impl(const pt_sd_params* prm, const float* w_in, const float* fe
     }
     if (num_iter == 0 && !want_loss && !cls) return PT_OK;
 
-    hipLaunchKernelGGL(k_sd_maps, dim3(n), dim3(256), 0, st, a);
-    PT_CHECK_LAUNCH();
+    if (lmap) {
+        if (int rc = pt_launch_gn_hinge_maps(a, *lmap, st)) return rc;
+    } else {
+        hipLaunchKernelGGL(k_sd_maps, dim3(n), dim3(256), 0, st, a);
+        PT_CHECK_LAUNCH();
+    }
     if (cls && cls->after_init && hipEventRecord((hipEvent_t)cls->after_init, st) != hipSuccess) return PT_ERR_LAUNCH;
     if (num_iter == 0 && !want_loss) return PT_OK;
     int rc = pt_launch_corr(p, feat, feat_stride_n, w_in, a.spart, st);

@@ -19,14 +19,17 @@ What gets rebound (import path = contract; nothing in the reference tree is edit
                                                                                       -> pytracking_amd.preprocessing
   ltr.models.lwl.loss_residual_modules.LWTLResidual, ltr.models.meta.steepestdescent.GNSteepestDescent
                                                   (LWL few-shot learner)              -> pytracking_amd.steepestdescent
+  ltr.models.meta.steepestdescent.GNSteepestDescent on residual_modules.LinearFilterHinge
+                                                  (DiMP-simple, RTS classifier)       -> pytracking_amd.gn_hinge
+  ltr.models.rts.loss_residual_modules.RTSResidual (RTS segmentation learner)         -> pytracking_amd.steepestdescent
   ltr.models.transformer.transformer.Transformer, ltr.models.transformer.filter_predictor.FilterPredictor,
   ltr.models.transformer.heads.{LinearFilterClassifier, DenseBoxRegressor}
                                                   (ToMP model predictor, inference)   -> pytracking_amd.transformer
   ltr.models.target_classifier.features.residual_bottleneck  (final 3x3 conv + InstanceL2Norm, inference)
                                                                                       -> pytracking_amd.features
-  pytracking.libs.dcf.max2d, pytracking.tracker.dimp.dimp.DiMP.localize_advanced,
+  pytracking.libs.dcf.max2d, pytracking.tracker.dimp.dimp.DiMP.localize_advanced (and DiMPSimple's),
   pytracking.tracker.tomp.tomp.ToMP.localize_advanced  (score-map localisation)       -> pytracking_amd.localization
-  pytracking.tracker.dimp.dimp.DiMP.optimize_boxes_default / optimize_boxes_relative,
+  pytracking.tracker.dimp.dimp.DiMP.optimize_boxes_default / optimize_boxes_relative (and DiMPSimple's),
   pytracking.tracker.atom.atom.ATOM.optimize_boxes                                    (IoU-guided box refinement)
                                                                                       -> pytracking_amd.iou_refine
 
@@ -300,6 +303,7 @@ def _install_localization(orig, strict):
     max2d.__doc__, max2d.__wrapped__ = ref_max2d.__doc__, ref_max2d
     dmod.max2d = max2d
     for modname, clsname, fn in (("pytracking.tracker.dimp.dimp", "DiMP", _loc.localize_advanced),
+                                 ("pytracking.tracker.dimp_simple.dimp_simple", "DiMPSimple", _loc.localize_advanced),   # = DiMP's
                                  ("pytracking.tracker.tomp.tomp", "ToMP", _loc.localize_advanced_tomp)):
         try:
             cls = getattr(importlib.import_module(modname), clsname)
@@ -331,6 +335,13 @@ def _install_iou_refine(orig, strict):
                           (cls, "optimize_boxes_relative", cls.optimize_boxes_relative)]
     targets = [(cls, "optimize_boxes_default", _ir.optimize_boxes_default, lambda t: t.net.bb_regressor),
                (cls, "optimize_boxes_relative", _ir.optimize_boxes_relative, lambda t: t.net.bb_regressor)]
+    try:                                    # DiMPSimple's two methods are DiMP's, byte for byte (dimp_simple.py vs dimp.py)
+        scls = importlib.import_module("pytracking.tracker.dimp_simple.dimp_simple").DiMPSimple
+        for name, fast in (("optimize_boxes_default", _ir.optimize_boxes_default), ("optimize_boxes_relative", _ir.optimize_boxes_relative)):
+            orig["iou_refine"].append((scls, name, getattr(scls, name)))
+            targets.append((scls, name, fast, lambda t: t.net.bb_regressor))
+    except Exception:
+        pass
     try:
         acls = importlib.import_module("pytracking.tracker.atom.atom").ATOM
         orig["iou_refine"].append((acls, "optimize_boxes", acls.optimize_boxes))
@@ -449,7 +460,7 @@ def _install_preprocessing(orig, strict):
     pmod.sample_patch_transformed = sample_patch_transformed
     # the trackers import the names (`from pytracking.features.preprocessing import sample_patch_multiscale, ...`)
     # ... and ATOM reaches them through its feature extractors (`pytracking/features/extractor.py:3,112`)
-    for modname in ("pytracking.tracker.dimp.dimp", "pytracking.tracker.atom.atom", "pytracking.tracker.tomp.tomp",
+    for modname in ("pytracking.tracker.dimp.dimp", "pytracking.tracker.dimp_simple.dimp_simple", "pytracking.tracker.atom.atom", "pytracking.tracker.tomp.tomp",
                     "pytracking.tracker.kys.kys", "pytracking.tracker.lwl.lwl", "pytracking.features.extractor",
                     "pytracking.features.featurebase"):
         tmod = sys.modules.get(modname)
@@ -463,6 +474,72 @@ def _install_preprocessing(orig, strict):
             if getattr(tmod, name, None) is ref:
                 setattr(tmod, name, fn)
                 orig["preprocessing"]["importers"].append((tmod, name, ref))
+
+
+def _install_gn_hinge(orig, strict, smod):
+    """`GNSteepestDescent` on an exact reference `LinearFilterHinge` with parameter_batch_dim=0, residual_batch_dim=1
+    (dimpnet.py:236-242, rts_net.py:325-333) -> the fused solver (pytracking_amd.gn_hinge); the residual object stays the reference's.
+    CPU tensors, grad-enabled inputs and uncovered shapes run the reference forward (or raise under strict=True).  Does not depend on
+    the LWL modules importing."""
+    from . import gn_hinge as _gh
+    ref_gn = smod.GNSteepestDescent
+    orig["gn_hinge"] = ref_gn
+    try:
+        hinge_cls = importlib.import_module("ltr.models.target_classifier.residual_modules").LinearFilterHinge
+    except Exception:
+        return
+
+    class GNSteepestDescent(ref_gn):
+        """LinearFilterHinge -> fused hinge solver; any other residual module -> the reference class."""
+
+        def __new__(cls, residual_module=None, *args, **kw):
+            if (type(residual_module) is hinge_cls and kw.get("residual_batch_dim", 0) == 1
+                    and kw.get("parameter_batch_dim", 0) == 0):
+                return _FusedHinge(residual_module, *args, **kw)
+            return ref_gn.__new__(cls)
+
+    class _FusedHinge(_gh.GNSteepestDescent):
+        _compute_loss = ref_gn._compute_loss
+        _sqr_norm = ref_gn._sqr_norm
+
+        def forward(self, meta_parameter, num_iter=None, *args, **kwargs):
+            n_it = self.num_iter if num_iter is None else num_iter
+            fast = (not args and set(kwargs) <= {"feat", "bb", "train_label", "sample_weight", "is_distractor"}
+                    and kwargs.get("is_distractor") is None
+                    and _gh.covered(self.residual_module, meta_parameter, dict(kwargs, _num_iter=n_it),
+                                    self._parameter_batch_dim, self._residual_batch_dim))
+            if _hit("GNSteepestDescent.hinge", fast):
+                return _gh.GNSteepestDescent.forward(self, meta_parameter, num_iter, **kwargs)
+            if strict:
+                raise NotImplementedError("GNSteepestDescent (hinge residual): call outside the gfx950 hot path")
+            return ref_gn.forward(self, meta_parameter, num_iter, *args, **kwargs)
+
+    smod.GNSteepestDescent = GNSteepestDescent
+
+
+def _install_rts_residual(orig, strict, mirror):
+    """`ltr.models.rts.loss_residual_modules.RTSResidual` (forward identical to LWTLResidual's): undilated -> the LWTL mirror, so that the
+    LWL fused solver (which reads filter_reg through the mirror's scalar cache) takes the RTS segmentation learner."""
+    try:
+        rts = importlib.import_module("ltr.models.rts.loss_residual_modules")
+    except Exception:
+        return
+    ref_rts = getattr(rts, "RTSResidual", None)
+    if ref_rts is None:
+        return
+    orig["rts_residual"] = (rts, ref_rts)
+
+    class RTSResidual(ref_rts):
+        """No dilation factors -> the gfx950 LWTL mirror (same parameter); dilated filters -> the reference class."""
+
+        def __new__(cls, init_filter_reg=1e-2, filter_dilation_factors=None):
+            if filter_dilation_factors is None:
+                return mirror(init_filter_reg, filter_dilation_factors)
+            if strict:
+                raise NotImplementedError("RTSResidual: dilated filters are outside the gfx950 hot path")
+            return ref_rts.__new__(cls)
+
+    rts.RTSResidual = RTSResidual
 
 
 def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=True, iou_refine=True, preprocessing=True):
@@ -484,15 +561,23 @@ def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=T
     for n in names:
         setattr(omod, n, _optimizer_class(getattr(_optimizer, n), getattr(omod, n), strict))
     # LWL few-shot learner: the residual module is replaced outright (same parameters); the generic optimiser class
-    # dispatches on it so that other residual modules (RTS, dimp_simple) keep the reference implementation
+    # dispatches on it.  The hinge residual (dimp_simple, RTS classifier) is recognised and kept as the reference's object;
+    # the RTS segmentation residual (RTSResidual, the same forward as LWTLResidual) is replaced by the LWTL mirror like LWTLResidual.
+    # Any other residual module keeps the reference implementation.
     try:
-        rmod = importlib.import_module("ltr.models.lwl.loss_residual_modules")
         smod = importlib.import_module("ltr.models.meta.steepestdescent")
     except Exception:
-        rmod = smod = None
-    if rmod is not None:
+        smod = None
+    try:
+        rmod = importlib.import_module("ltr.models.lwl.loss_residual_modules")
+    except Exception:
+        rmod = None
+    if smod is not None:
+        _install_gn_hinge(orig, strict, smod)
+    if rmod is not None and smod is not None:
         orig["lwl"] = (rmod.LWTLResidual, smod.GNSteepestDescent)
         ref_gn, ref_res = smod.GNSteepestDescent, rmod.LWTLResidual
+        hinge_new = smod.GNSteepestDescent.__new__
 
         class LWTLResidual(ref_res):
             """No dilation factors -> the gfx950 mirror (same parameter); dilated filters -> the reference class."""
@@ -517,7 +602,7 @@ def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=T
                 if (isinstance(residual_module, _sd.LWTLResidual) and residual_module.filter_dilation_factors is None
                         and kw.get("residual_batch_dim", 0) == 1 and kw.get("parameter_batch_dim", 0) == 0):
                     return _FusedGN(residual_module, *args, **kw)
-                return ref_gn.__new__(cls)
+                return hinge_new(cls, residual_module, *args, **kw)
 
         class _FusedGN(_sd.GNSteepestDescent):
             _compute_loss = ref_gn._compute_loss
@@ -536,6 +621,7 @@ def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=T
 
         rmod.LWTLResidual = LWTLResidual
         smod.GNSteepestDescent = GNSteepestDescent
+        _install_rts_residual(orig, strict, _ResMirror)
     if tomp:
         _install_tomp(orig, strict)
     if clf_head:
@@ -650,8 +736,11 @@ def uninstall():
         pm.sample_patch, pm.sample_patch_multiscale, pm.sample_patch_transformed = orig["preprocessing"]["functions"]
         for tmod, name, ref in orig["preprocessing"]["importers"]:
             setattr(tmod, name, ref)
+    if "rts_residual" in orig:
+        orig["rts_residual"][0].RTSResidual = orig["rts_residual"][1]
     if "lwl" in orig:
         importlib.import_module("ltr.models.lwl.loss_residual_modules").LWTLResidual = orig["lwl"][0]
-        importlib.import_module("ltr.models.meta.steepestdescent").GNSteepestDescent = orig["lwl"][1]
+    if "gn_hinge" in orig:
+        importlib.import_module("ltr.models.meta.steepestdescent").GNSteepestDescent = orig["gn_hinge"]
     _state["installed"] = False
     orig.clear()

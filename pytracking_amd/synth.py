@@ -339,3 +339,32 @@ def tracker_tomp_params(seed, dims, cfg=None):
     p["cls.linear.weight"] = -p["cls.linear.weight"]
     p["cls.linear.bias"] = -p["cls.linear.bias"]
     return p
+
+
+# GNSteepestDescent on LinearFilterHinge (dimpnet50_simple, super_dimp_simple.py:105-108 / the RTS classifier, rts_net.py:325-333)
+DIMP_SIMPLE = dict(n=50, C=512, H=22, W=22, K=4, hinge_threshold=0.05, activation_leak=0.1, filter_reg=0.1)
+RTS_CLF = dict(n=50, C=512, H=15, W=26, K=4, hinge_threshold=0.05, activation_leak=0.0, filter_reg=0.1)
+
+
+def hinge_labels(rng, n, S, OH, OW, sigma=1.5):
+    """(n, S, OH, OW) Gaussian label maps around jittered centres (the trackers' `init_target_labels` shape), values in (0, 1]."""
+    cy = (OH - 1) / 2.0 + rng.uniform(-2.0, 2.0, size=(n, S, 1, 1))
+    cx = (OW - 1) / 2.0 + rng.uniform(-2.0, 2.0, size=(n, S, 1, 1))
+    y = np.arange(OH, dtype=np.float64).reshape(1, 1, OH, 1)
+    x = np.arange(OW, dtype=np.float64).reshape(1, 1, 1, OW)
+    return np.exp(-((y - cy) ** 2 + (x - cx) ** 2) / (2.0 * sigma * sigma)).astype(np.float32)
+
+
+def gn_hinge_problem(seed, n, C, H, W, K, S=1, sw_mode="none"):
+    """(w0, feat, label, sw) of one `GNSteepestDescent(LinearFilterHinge)` call: feat (n, S, C, H, W), w0 (S, C, K, K) small
+    random, label (n, S, OH, OW), sw None or (n,) per-image weights summing to 1 (the trackers' memory weights)."""
+    rng = np.random.default_rng(seed)
+    OH, OW = H + (K + 1) % 2, W + (K + 1) % 2
+    feat = np.stack([clf_features(rng, n, C, H, W, K) for _ in range(S)], axis=1)
+    w0 = (rng.standard_normal((S, C, K, K), dtype=np.float32) * np.float32(0.02)).astype(np.float32)
+    label = hinge_labels(rng, n, S, OH, OW)
+    sw = None
+    if sw_mode == "per_image":
+        u = rng.uniform(0.5, 1.5, size=n)
+        sw = (u / u.sum()).astype(np.float32)
+    return w0, feat, label, sw
