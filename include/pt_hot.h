@@ -582,6 +582,63 @@ int pt_track_frame_replay_pass_f32(const pt_sd_params* prm, const float* filter,
                                    const float* mem_bb, const float* sample_weight, int n, int C, int H, int W, int K,
                                    int num_iter, void* ws, size_t ws_bytes, int which, int reps, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Target-candidate matching (KeepTrack; pytracking/tracker/keep_track/keep_track.py:437-475), tcm.hip.
+ *
+ * pt_tcm_peaks_f32: local maxima of B score maps (ltr/data/processing_utils.py:669-705).
+ *   scores (B, H, W), H, W <= 64; ks odd (max_pool2d window, stride 1, padding ks/2: padding never wins);
+ *   a peak is scores == window max && scores > th.  Per map b: count[b] (int32) peaks, sorted by value, highest first,
+ *   ties in ascending raster order (the reference's argsort leaves the order of ties unspecified); coords (B, H*W, 2) int64
+ *   (y, x) and values (B, H*W): the first count[b] entries of map b are written.  Exact float comparisons: bit-identical to
+ *   the reference for the same map.
+ *
+ * pt_tcm_desc_f32: DescriptorExtractor.get_descriptors (target_candidate_matching.py:28-36) at P points per image only:
+ *   out[b, d, p] = bias[d] + sum_{c,u,v} weight[d, c, u, v] * x[b, c, y_p + u - 2, x_p + v - 2]
+ *   x (B, C, H, W), weight (D, C, 4, 4) contiguous (16-byte aligned), bias (D), coords (B, P, 2) int64 (y, x) on the
+ *   (H+1) x (W+1) output map (a point outside it reads zeros only), out (B, D, P).  C % 16 == 0, D % 64 == 0.  K = 16 C is
+ *   split over C/16 workgroups per 64 output channels; the partials (ws: pt_tcm_desc_ws_bytes) are summed in a fixed order
+ *   by a second launch: repeated calls are bit-identical.
+ *
+ * pt_tcm_match_f32: SuperGlue._forward (ltr/models/target_candidate_matching/superglue.py:299-361) for batch 1,
+ *   output_normalization 'sinkhorn', input_dim == descriptor_dim == 256, no bottleneck, eval-mode BatchNorm.
+ *   desc0 (256, M), desc1 (256, N) channel-major; kpts0 (M, 2), kpts1 (N, 2) as the caller passes them; scores0 (M),
+ *   scores1 (N); the keypoint encoder input is ((k[0] - center[0]) / scale, (k[1] - center[1]) / scale, score) per side
+ *   (normalize_keypoints: center = size / 2, scale = 0.7 max(size)).  bin_score is a device scalar, read at call time.
+ *   Outputs: log_assignment (M+1, N+1), matches0 (M) / matches1 (N) int64 (-1: unmatched), match_scores0 (M) /
+ *   match_scores1 (N).  One launch per dependent stage (5 per GNN layer), no host synchronisation: capturable.
+ *   layer_types: bit l set = GNN layer l is 'cross' (else 'self').  M, N <= 64.
+ *
+ *   Weight pack (float32, every block row-major (out, in), BatchNorm folded: w' = w s, b' = (b - mean) s + beta,
+ *   s = gamma / sqrt(var + eps)), in this order, pt_tcm_match_weight_floats(L) floats for L GNN layers (L = 0 with skip_gnn):
+ *     keypoint encoder  W 32x3, b 32, W 64x32, b 64, W 128x64, b 128, W 256x128, b 256 (BN folded, ReLU), W 256x256, b 256
+ *     per GNN layer     Wqkv 768x256 (proj[0]; proj[1]; proj[2]), bqkv 768, Wmerge 256x256, bmerge 256,
+ *                       W1 512x512 (BN folded; input = [x; message]), b1 512, W2 256x512, b2 256
+ *     final projection  W 256x256, b 256
+ * ---------------------------------------------------------------------------------------------- */
+#define PT_TCM_MAX_POINTS 64
+#define PT_TCM_MAX_LAYERS 32
+typedef struct pt_tcm_match_params {
+    int M, N;
+    int n_layers;            /* GNN layers in the pack (ignored when skip_gnn) */
+    unsigned layer_types;    /* bit l: layer l is 'cross' */
+    int skip_gnn;
+    int sinkhorn_iters;
+    float filter_threshold;
+    float kpt_center0[2], kpt_scale0, kpt_center1[2], kpt_scale1;
+    size_t weight_floats;    /* size of the pack handed in (checked against pt_tcm_match_weight_floats) */
+} pt_tcm_match_params;
+int pt_tcm_peaks_f32(const float* scores, int B, int H, int W, int ks, float th, int* count, long long* coords, float* values,
+                     void* stream);
+size_t pt_tcm_desc_ws_bytes(int B, int P, int C, int D);
+int pt_tcm_desc_f32(const float* x, const float* weight, const float* bias, const long long* coords, int B, int C, int H, int W,
+                    int P, int D, float* out, void* ws, size_t ws_bytes, void* stream);
+size_t pt_tcm_match_weight_floats(int n_layers);
+size_t pt_tcm_match_ws_bytes(const pt_tcm_match_params* p);
+int pt_tcm_match_f32(const pt_tcm_match_params* p, const float* weights, const float* bin_score, const float* desc0,
+                     const float* desc1, const float* kpts0, const float* kpts1, const float* scores0, const float* scores1,
+                     float* log_assignment, long long* matches0, long long* matches1, float* match_scores0,
+                     float* match_scores1, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

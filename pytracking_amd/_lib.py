@@ -9,7 +9,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PT_HOT_LIB", os.path.join(_HERE, "libpt_hot.so"))   # override: experiments only
-SOURCES = ["filter_kernels.hip", "fast_passes.hip", "sd_solver.hip", "mf_kernels.hip", "lwl_solver.hip", "atom_cg.hip", "atom_gn.hip", "tomp.hip", "localize.hip", "iou_refine.hip", "prroi.hip", "patch.hip", "frame_full.hip", "api.hip", "gn_hinge.hip"]
+SOURCES = ["filter_kernels.hip", "fast_passes.hip", "sd_solver.hip", "mf_kernels.hip", "lwl_solver.hip", "atom_cg.hip", "atom_gn.hip", "tomp.hip", "localize.hip", "iou_refine.hip", "prroi.hip", "patch.hip", "frame_full.hip", "api.hip", "gn_hinge.hip", "tcm.hip"]
 HEADERS = ["common.h", "pt_internal.h", "rbuild.h", "sd_common.h", "mfma_gemm.h", "prroi_dev.h", "localize_dev.h", "frame_mid.h", os.path.join("..", "..", "include", "pt_hot.h")]
 # kernarg preload: leading scalar kernel parameters arrive in SGPRs at wave launch (kernels that take them that way only)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-pass-failed", "-mllvm", "-amdgpu-kernarg-preload-count=14"]
@@ -94,7 +94,19 @@ EXPORTS = [
     "pt_track_frame_full_dyn_bytes", "pt_track_frame_full_dyn_fill_f32", "pt_host_wait_word_f32",
     "pt_sd_solve_batch_f32", "pt_stream_probe_f32",
     "pt_gn_hinge_ws_bytes", "pt_gn_hinge_solve_f32", "pt_gn_hinge_route",
+    "pt_tcm_peaks_f32", "pt_tcm_desc_ws_bytes", "pt_tcm_desc_f32",
+    "pt_tcm_match_weight_floats", "pt_tcm_match_ws_bytes", "pt_tcm_match_f32",
 ]
+
+PT_TCM_MAX_POINTS, PT_TCM_MAX_LAYERS = 64, 32       # include/pt_hot.h
+
+
+class TcmMatchParams(ctypes.Structure):
+    """`pt_tcm_match_params` of include/pt_hot.h."""
+    _fields_ = ([(n, ctypes.c_int) for n in ("M", "N", "n_layers")] + [("layer_types", ctypes.c_uint)]
+                + [(n, ctypes.c_int) for n in ("skip_gnn", "sinkhorn_iters")] + [("filter_threshold", ctypes.c_float)]
+                + [("kpt_center0", ctypes.c_float * 2), ("kpt_scale0", ctypes.c_float), ("kpt_center1", ctypes.c_float * 2),
+                   ("kpt_scale1", ctypes.c_float), ("weight_floats", ctypes.c_size_t)])
 
 
 class GnHingeParams(ctypes.Structure):
@@ -345,6 +357,18 @@ def lib():
     L.pt_gn_hinge_solve_f32.argtypes = [ctypes.POINTER(GnHingeParams), vp, vp, l, vp, vp] + [i] * 6 + [vp, vp, vp, sz, vp]
     L.pt_gn_hinge_route.restype = i
     L.pt_gn_hinge_route.argtypes = [vp, l, vp, vp] + [i] * 5
+    L.pt_tcm_peaks_f32.restype = i
+    L.pt_tcm_peaks_f32.argtypes = [vp, i, i, i, i, f, vp, vp, vp, vp]
+    L.pt_tcm_desc_ws_bytes.restype = sz
+    L.pt_tcm_desc_ws_bytes.argtypes = [i] * 4
+    L.pt_tcm_desc_f32.restype = i
+    L.pt_tcm_desc_f32.argtypes = [vp, vp, vp, vp] + [i] * 6 + [vp, vp, sz, vp]
+    L.pt_tcm_match_weight_floats.restype = sz
+    L.pt_tcm_match_weight_floats.argtypes = [i]
+    L.pt_tcm_match_ws_bytes.restype = sz
+    L.pt_tcm_match_ws_bytes.argtypes = [ctypes.POINTER(TcmMatchParams)]
+    L.pt_tcm_match_f32.restype = i
+    L.pt_tcm_match_f32.argtypes = [ctypes.POINTER(TcmMatchParams)] + [vp] * 14 + [sz, vp]
     L.pt_sample_patch_f32.restype = i
     L.pt_sample_patch_f32.argtypes = [vp, i, i, i, ctypes.POINTER(PatchGeom), i, vp, i, i, vp]
     L.pt_augment_patches_f32.restype = i

@@ -27,9 +27,12 @@ What gets rebound (import path = contract; nothing in the reference tree is edit
                                                   (ToMP model predictor, inference)   -> pytracking_amd.transformer
   ltr.models.target_classifier.features.residual_bottleneck  (final 3x3 conv + InstanceL2Norm, inference)
                                                                                       -> pytracking_amd.features
-  pytracking.libs.dcf.max2d, pytracking.tracker.dimp.dimp.DiMP.localize_advanced (and DiMPSimple's),
+  ltr.data.processing_utils.find_local_maxima, ltr.models.target_candidate_matching.target_candidate_matching
+  .DescriptorExtractor.get_descriptors, ltr.models.target_candidate_matching.superglue.SuperGlue._forward
+                                                  (KeepTrack candidate matching)      -> pytracking_amd.candidate_matching
+  pytracking.libs.dcf.max2d, pytracking.tracker.dimp.dimp.DiMP.localize_advanced (and DiMPSimple's, KeepTrack's),
   pytracking.tracker.tomp.tomp.ToMP.localize_advanced  (score-map localisation)       -> pytracking_amd.localization
-  pytracking.tracker.dimp.dimp.DiMP.optimize_boxes_default / optimize_boxes_relative (and DiMPSimple's),
+  pytracking.tracker.dimp.dimp.DiMP.optimize_boxes_default / optimize_boxes_relative (and DiMPSimple's, KeepTrack's),
   pytracking.tracker.atom.atom.ATOM.optimize_boxes                                    (IoU-guided box refinement)
                                                                                       -> pytracking_amd.iou_refine
 
@@ -304,6 +307,7 @@ def _install_localization(orig, strict):
     dmod.max2d = max2d
     for modname, clsname, fn in (("pytracking.tracker.dimp.dimp", "DiMP", _loc.localize_advanced),
                                  ("pytracking.tracker.dimp_simple.dimp_simple", "DiMPSimple", _loc.localize_advanced),   # = DiMP's
+                                 ("pytracking.tracker.keep_track.keep_track", "KeepTrack", _loc.localize_advanced),      # = DiMP's
                                  ("pytracking.tracker.tomp.tomp", "ToMP", _loc.localize_advanced_tomp)):
         try:
             cls = getattr(importlib.import_module(modname), clsname)
@@ -335,13 +339,17 @@ def _install_iou_refine(orig, strict):
                           (cls, "optimize_boxes_relative", cls.optimize_boxes_relative)]
     targets = [(cls, "optimize_boxes_default", _ir.optimize_boxes_default, lambda t: t.net.bb_regressor),
                (cls, "optimize_boxes_relative", _ir.optimize_boxes_relative, lambda t: t.net.bb_regressor)]
-    try:                                    # DiMPSimple's two methods are DiMP's, byte for byte (dimp_simple.py vs dimp.py)
-        scls = importlib.import_module("pytracking.tracker.dimp_simple.dimp_simple").DiMPSimple
+    # DiMPSimple's two methods are DiMP's, byte for byte (dimp_simple.py vs dimp.py); KeepTrack's differ from DiMP's in comments and
+    # docstrings only (keep_track.py vs dimp.py)
+    for modname, clsname in (("pytracking.tracker.dimp_simple.dimp_simple", "DiMPSimple"),
+                             ("pytracking.tracker.keep_track.keep_track", "KeepTrack")):
+        try:
+            scls = getattr(importlib.import_module(modname), clsname)
+        except Exception:
+            continue
         for name, fast in (("optimize_boxes_default", _ir.optimize_boxes_default), ("optimize_boxes_relative", _ir.optimize_boxes_relative)):
             orig["iou_refine"].append((scls, name, getattr(scls, name)))
             targets.append((scls, name, fast, lambda t: t.net.bb_regressor))
-    except Exception:
-        pass
     try:
         acls = importlib.import_module("pytracking.tracker.atom.atom").ATOM
         orig["iou_refine"].append((acls, "optimize_boxes", acls.optimize_boxes))
@@ -460,7 +468,8 @@ def _install_preprocessing(orig, strict):
     pmod.sample_patch_transformed = sample_patch_transformed
     # the trackers import the names (`from pytracking.features.preprocessing import sample_patch_multiscale, ...`)
     # ... and ATOM reaches them through its feature extractors (`pytracking/features/extractor.py:3,112`)
-    for modname in ("pytracking.tracker.dimp.dimp", "pytracking.tracker.dimp_simple.dimp_simple", "pytracking.tracker.atom.atom", "pytracking.tracker.tomp.tomp",
+    for modname in ("pytracking.tracker.dimp.dimp", "pytracking.tracker.dimp_simple.dimp_simple", "pytracking.tracker.keep_track.keep_track",
+                    "pytracking.tracker.atom.atom", "pytracking.tracker.tomp.tomp",
                     "pytracking.tracker.kys.kys", "pytracking.tracker.lwl.lwl", "pytracking.features.extractor",
                     "pytracking.features.featurebase"):
         tmod = sys.modules.get(modname)
@@ -474,6 +483,50 @@ def _install_preprocessing(orig, strict):
             if getattr(tmod, name, None) is ref:
                 setattr(tmod, name, fn)
                 orig["preprocessing"]["importers"].append((tmod, name, ref))
+
+
+def _install_candidate_matching(orig, strict):
+    """KeepTrack's target-candidate matching (keep_track.py:437-475): `ltr.data.processing_utils.find_local_maxima` (reached as
+    `prutils.find_local_maxima`), `DescriptorExtractor.get_descriptors` and `SuperGlue._forward`.  CPU tensors, grad-enabled
+    calls, training mode, the bottleneck / input-projection / double-softmax variants, more than 64 candidates on a side and the
+    reference's zero-keypoint branch keep the reference's code."""
+    from . import candidate_matching as _cm
+    try:
+        pmod = importlib.import_module("ltr.data.processing_utils")
+        tmod = importlib.import_module("ltr.models.target_candidate_matching.target_candidate_matching")
+        gmod = importlib.import_module("ltr.models.target_candidate_matching.superglue")
+    except Exception:
+        return
+    ref_flm, dcls, scls = pmod.find_local_maxima, tmod.DescriptorExtractor, gmod.SuperGlue
+    ref_desc, ref_fwd = dcls.get_descriptors, scls._forward
+    orig["candidate_matching"] = (pmod, ref_flm, dcls, ref_desc, scls, ref_fwd)
+
+    def find_local_maxima(scores, th, ks):
+        if _hit("find_local_maxima", _cm.covered_find_local_maxima(scores, th, ks)):
+            return _cm.find_local_maxima(scores, th, ks)
+        if strict:
+            raise NotImplementedError("find_local_maxima: call outside the gfx950 hot path")
+        return ref_flm(scores, th, ks)
+
+    def get_descriptors(self, x, coords):
+        if _hit("DescriptorExtractor.get_descriptors", _cm.covered_get_descriptors(self, x, coords)):
+            return _cm.get_descriptors(self, x, coords)
+        if strict:
+            raise NotImplementedError("DescriptorExtractor.get_descriptors: call outside the gfx950 hot path")
+        return ref_desc(self, x, coords)
+
+    def _forward(self, data):
+        if _hit("SuperGlue._forward", _cm.covered_match(self, data)):
+            return _cm.match(self, data, checked=True)
+        if strict:
+            raise NotImplementedError("SuperGlue._forward: call outside the gfx950 hot path")
+        return ref_fwd(self, data)
+
+    for fn, ref in ((find_local_maxima, ref_flm), (get_descriptors, ref_desc), (_forward, ref_fwd)):
+        fn.__doc__, fn.__wrapped__ = ref.__doc__, ref
+    pmod.find_local_maxima = find_local_maxima
+    dcls.get_descriptors = get_descriptors
+    scls._forward = _forward
 
 
 def _install_gn_hinge(orig, strict, smod):
@@ -542,7 +595,8 @@ def _install_rts_residual(orig, strict, mirror):
     rts.RTSResidual = RTSResidual
 
 
-def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=True, iou_refine=True, preprocessing=True):
+def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=True, iou_refine=True, preprocessing=True,
+            candidate_matching=True):
     """Rebind the boundary symbols.  Call after the reference is importable (`sys.path`) and before networks or
     trackers are constructed.  Idempotent."""
     if _state["installed"]:
@@ -632,6 +686,8 @@ def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=T
         _install_iou_refine(orig, strict)
     if preprocessing:
         _install_preprocessing(orig, strict)
+    if candidate_matching:
+        _install_candidate_matching(orig, strict)
     if atom_cg:
         try:
             pmod = importlib.import_module("pytracking.libs.optimization")
@@ -742,5 +798,8 @@ def uninstall():
         importlib.import_module("ltr.models.lwl.loss_residual_modules").LWTLResidual = orig["lwl"][0]
     if "gn_hinge" in orig:
         importlib.import_module("ltr.models.meta.steepestdescent").GNSteepestDescent = orig["gn_hinge"]
+    if "candidate_matching" in orig:
+        pmod, ref_flm, dcls, ref_desc, scls, ref_fwd = orig["candidate_matching"]
+        pmod.find_local_maxima, dcls.get_descriptors, scls._forward = ref_flm, ref_desc, ref_fwd
     _state["installed"] = False
     orig.clear()

@@ -368,3 +368,71 @@ def gn_hinge_problem(seed, n, C, H, W, K, S=1, sw_mode="none"):
         u = rng.uniform(0.5, 1.5, size=n)
         sw = (u / u.sum()).astype(np.float32)
     return w0, feat, label, sw
+
+
+# KeepTrack target-candidate matching (ltr/models/target_candidate_matching): layer3 maps, the descriptor conv and SuperGlue's
+# state as KeepTrack builds it (target_candidate_matching_net_resnet50: GNN_layers ['self', 'cross'] * 2)
+TCM_FAST = dict(C=1024, H=22, W=22, D=256)        # parameter/keep_track/default_fast.py: image_sample_size 22*16
+TCM_DEFAULT = dict(C=1024, H=30, W=30, D=256)     # parameter/keep_track/default.py: image_sample_size 30*16
+
+
+def tcm_layer3(seed, B, C, H, W):
+    """A non-negative layer3-like map (B, C, H, W)."""
+    rng = np.random.default_rng(seed)
+    return np.maximum(rng.standard_normal((B, C, H, W), dtype=np.float32), 0.0).astype(np.float32)
+
+
+def tcm_desc_conv(seed, D=256, C=1024):
+    """(weight (D, C, 4, 4), bias (D,)) of DescriptorExtractor.conv at a kaiming-like scale."""
+    rng = np.random.default_rng(seed)
+    w = (rng.standard_normal((D, C, 4, 4), dtype=np.float32) * np.float32(1.0 / np.sqrt(C * 16))).astype(np.float32)
+    b = (rng.standard_normal(D, dtype=np.float32) * np.float32(0.1)).astype(np.float32)
+    return w, b
+
+
+def tcm_superglue_state(seed, n_layers=4, skip_gnn=False, bin_score=1.0):
+    """A SuperGlue state_dict (numpy, float32) for the KeepTrack conf: 1/sqrt(fan_in) weights, and BatchNorm running statistics,
+    gains and shifts away from their defaults so that folding them is exercised."""
+    rng = np.random.default_rng(seed)
+    sd = {}
+
+    def conv(name, o, i, gain=1.0):
+        sd[name + ".weight"] = (rng.standard_normal((o, i, 1), dtype=np.float32) * np.float32(gain / np.sqrt(i))).astype(np.float32)
+        sd[name + ".bias"] = (rng.standard_normal(o, dtype=np.float32) * np.float32(0.1)).astype(np.float32)
+
+    def bn(name, c):
+        sd[name + ".weight"] = rng.uniform(0.5, 1.5, c).astype(np.float32)
+        sd[name + ".bias"] = (rng.standard_normal(c) * 0.1).astype(np.float32)
+        sd[name + ".running_mean"] = (rng.standard_normal(c) * 0.2).astype(np.float32)
+        sd[name + ".running_var"] = rng.uniform(0.5, 2.0, c).astype(np.float32)
+        sd[name + ".num_batches_tracked"] = np.array(100, dtype=np.int64)
+
+    dims = [3, 32, 64, 128, 256, 256]
+    for k in range(5):
+        conv(f"kenc.encoder.{3 * k}", dims[k + 1], dims[k], gain=1.4)
+        if k < 4:
+            bn(f"kenc.encoder.{3 * k + 1}", dims[k + 1])
+    if not skip_gnn:
+        for l in range(n_layers):
+            p = f"gnn.layers.{l}.update."
+            conv(p + "attn.merge", 256, 256)
+            for j in range(3):
+                conv(p + f"attn.proj.{j}", 256, 256, gain=1.5)
+            conv(p + "mlp.0", 512, 512, gain=1.4)
+            bn(p + "mlp.1", 512)
+            conv(p + "mlp.3", 256, 512, gain=0.5)
+    conv("final_proj", 256, 256, gain=0.6)
+    sd["bin_score"] = np.array(bin_score, dtype=np.float32)
+    return sd
+
+
+def tcm_match_inputs(seed, M, N, image_shape=(480, 640)):
+    """descriptors (1, 256, M) / (1, 256, N), image coordinates (M, 2) / (N, 2) as (y, x) like KeepTrack's, scores (1, M) / (1, N)."""
+    rng = np.random.default_rng(seed)
+    h, w = image_shape
+    out = {}
+    for s, n in (("0", M), ("1", N)):
+        out["descriptors" + s] = rng.standard_normal((1, 256, n), dtype=np.float32)
+        out["img_coords" + s] = np.stack([rng.uniform(0, h, n), rng.uniform(0, w, n)], 1).astype(np.float32)
+        out["scores" + s] = rng.uniform(0.05, 1.0, (1, n)).astype(np.float32)
+    return out
