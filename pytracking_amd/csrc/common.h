@@ -62,17 +62,10 @@ __device__ __forceinline__ float wave_max(float v) {
 // waits for every outstanding vector-memory operation as well (s_waitcnt vmcnt(0)) -- prefetched feature loads, and the write
 // acknowledgements of result stores nobody in the workgroup reads (k_adj2's home waves: ~0.4 us in front of the barrier the whole
 // workgroup then sits at).  Here: LDS / scalar counter only, then the barrier.  NOT for data exchanged through global memory.
-#ifndef PT_LDS_BARRIER
-#define PT_LDS_BARRIER 1
-#endif
 __device__ __forceinline__ void pt_lds_barrier() {
-#if PT_LDS_BARRIER
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-#else
-    __syncthreads();
-#endif
 }
 
 // Deterministic block-wide sum; `scratch` needs blockDim.x/64 floats of LDS.  Every thread gets the result.
@@ -188,26 +181,16 @@ __device__ __forceinline__ T pt_late_args(unsigned byte_offset) {
 
 // A pointer that came out of pt_late_args() is an integer pair to the compiler: accesses through it are FLAT (address-space
 // check per access, counted on both the vector-memory and the LDS counter).  pt_global() states that it points to global memory.
-#ifdef PT_GLOBAL_OFF                                // A/B switch: pt_global() becomes a no-op (flat accesses)
-template <typename T>
-using pt_gptr = T*;
-#else
 template <typename T>
 using pt_gptr = T __attribute__((address_space(1)))*;
-#endif
 // Pointer members of the late-fetched argument blocks of the solver / ATOM kernels have these types.  Declared global
-// (-DPT_LATE_GLOBAL) every access through them is a global_load / global_store instead of flat_* (134-166 flat accesses in k_adj2,
+// (address_space(1)) every access through them is a global_load / global_store instead of flat_* (134-166 flat accesses in k_adj2,
 // 3428 in fast_passes.hip) -- and the frame is 1 % SLOWER (A/B on one box, twice: 109.6 / 109.5 vs 108.5 / 108.6 us, k_corr2 8.43 vs
 // 8.34, k_adj2 7.77 vs 7.66 us; profiles/r03ae_late_pointer_address_space.txt): they are result stores and late loads, and the
-// compiler's schedule around them differs.  The generic form stays the default; the IoU kernels use pt_global() where it was measured
+// compiler's schedule around them differs.  The generic form stays; the IoU kernels use pt_global() where it was measured
 // with their loads.
-#ifdef PT_LATE_GLOBAL
-typedef const float __attribute__((address_space(1)))* pt_gcf;
-typedef float __attribute__((address_space(1)))* pt_gf;
-#else
 typedef const float* pt_gcf;
 typedef float* pt_gf;
-#endif
 template <typename T>
 __device__ __forceinline__ pt_gptr<T> pt_global(T* p) { return (pt_gptr<T>)p; }
 

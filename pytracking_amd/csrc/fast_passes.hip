@@ -16,12 +16,9 @@
 //             wave w owns U contiguous 16-position groups.  G[c][tap] = sum_P feat[c][P] * r[P shifted by tap]; the B
 //             operand is gathered from zero-padded residual maps the workgroup builds in LDS -- there is no im2col
 //             buffer in HBM.  In the solver the maps come from the fused update prologue (alpha, s_{t}, residual).
-#include <type_traits>
 #include "common.h"
 #include "pt_internal.h"
 #include "sd_common.h"
-
-typedef float f32x2a4 __attribute__((ext_vector_type(2), aligned(4)));   // 8-byte LDS access at 4-byte alignment (ds_read_b64)
 
 #ifndef PT_ADJ_WAVES
 #define PT_ADJ_WAVES 8                     // waves per k_adj2 workgroup (16 measured no better at 18x18, worse at 22x22)
@@ -44,33 +41,6 @@ typedef float f32x2a4 __attribute__((ext_vector_type(2), aligned(4)));   // 8-by
 #endif
 #ifndef PT_ADJ_PD
 #define PT_ADJ_PD 3      // round 3 sweep: 3 / 4 / 6 / 8 / 12 / 16 ahead -> 8.08 / 8.36 / 8.50 / 8.67 / 8.84 / 9.0 us
-#endif
-#ifndef PT_C2_BAR
-#define PT_C2_BAR 0      // 1: workgroup barrier between the filter-operand loads and the first feature loads
-#endif
-#ifndef PT_C2_PAIR
-#define PT_C2_PAIR 1     // 1: sample-pair workgroups in k_corr2 where the plan allows them (pt_fast_plan); 0: round 3's one sample per workgroup
-#endif
-#ifndef PT_C2_R16
-#define PT_C2_R16 0      // 1: 16 channel ranges -- the two k-step halves of an XCD's range as separate 5-wave workgroups
-#endif
-#ifndef PT_ADJ_BAR
-#define PT_ADJ_BAR 0     // 1: workgroup barrier between the small update-stage loads and the first feature loads
-#endif
-#ifndef PT_ADJ_G2
-#define PT_ADJ_G2 0      // 1: residual cells of a quad gathered as two 8-byte LDS reads at 4-byte alignment (even map widths).  Measured in
-//                          round 4 and NOT kept: k_adj2 7.6 -> 12.0 us (PrDiMP 12.7 -> 17.7) -- a misaligned ds_read_b64 costs far more
-//                          than the two scalar reads and two address adds it replaces; as two ds_read2_b32 (dword pairs, no alignment demand): 7.55 -> 7.94 us
-//                          (profiles/r04j_adjoint_pair_gather_ab.txt) -- fewer instructions in the loop do not make it faster
-#endif
-#ifndef PT_C2_AV_UPFRONT
-#define PT_C2_AV_UPFRONT 1 // 1: k_corr2 reads its NK filter-operand values from LDS in one batch in front of the MFMA loop (round 6)
-#endif
-#ifndef PT_C2_SA_DIRECT
-#define PT_C2_SA_DIRECT 1 // 1: k_corr2's 4x4 shift-and-add with uniform tap steps and row / column masks (round 6); 0: per-tap index arithmetic
-#endif
-#ifndef PT_ADJ_EARLY
-#define PT_ADJ_EARLY 1   // 1: first feature loads in front of the LDS work; 0: behind barrier 1
 #endif
 
 // Phase time stamps (experiments only, -DPT_STAMPS; tools/exp_stamps.py): every wave records the 100 MHz device wall clock at
@@ -123,7 +93,6 @@ PtFast pt_fast_plan(int n, int C, int H, int W, int KH, int KW, int OH, int OW) 
     p.CX = C / 8;
     p.KSC = 8;
     if (C == 64) { p.CX = C; p.KSC = 1; }                           // ATOM's compressed samples: a workgroup takes ALL channels of a sample
-    if (PT_C2_R16 && p.nh == 2 && n > 16 && C > 64) { p.nh = 1; p.CX = C / 16; p.KSC = 16; }
     // Sample pairs (round 4).  With more samples than one workgroup per CU (8 n > 256) the pass lasted as long as a CU holding two
     // 10-wave workgroups -- two prologues, two filter reductions, their MFMA phases colliding -- while other CUs held one.  A pair
     // workgroup takes TWO samples with the same 10 waves: wave = (sample of the pair, tile), each with ALL k-steps of the XCD's
@@ -132,7 +101,7 @@ PtFast pt_fast_plan(int n, int C, int H, int W, int KH, int KW, int OH, int OW) 
     p.spw = 1;
     // Maps of 6-8 tiles (22x22) already run one wave per tile with all k-steps; their pairs (16 waves) were measured SLOWER
     // (PrDiMP-50: 11.25 vs 10.83 us, profiles/r04i_*) and keep one sample per workgroup.
-    if (PT_C2_PAIR && p.nh == 2 && p.KSC == 8 && p.CX / 4 <= 16 && (n % 2) == 0 && 8 * n > 256) { p.nh = 1; p.spw = 2; }
+    if (p.nh == 2 && p.KSC == 8 && p.CX / 4 <= 16 && (n % 2) == 0 && 8 * n > 256) { p.nh = 1; p.spw = 2; }
     p.NK = p.CX / 4 / p.nh;
     if (p.NK > 16) return p;
     p.HWp = 64 * (p.TF + (p.rem > 0 ? 1 : 0)) + 4;
@@ -334,7 +303,6 @@ __global__ __launch_bounds__(1024, (NK <= 8 && NH == 2 ? PT_C2_MINW : 4)) void k
         bq[k] = pt_bload4(fr, fo + (unsigned)(4 * k) * HW * 4u);
         if (LEFT && t == 0) bl[k] = pt_bload1(fr, lo + (unsigned)(4 * k) * HW * 4u);
     };
-    if (PT_C2_BAR) __syncthreads();
     // the leftover-quad scalars first: the filter reduction below then waits for vmcnt(CD) on every wave -- the 16-byte loads stay
     // in flight behind it -- instead of a count that fits the waves without the leftover tile
     if (LEFT && t == 0) {
@@ -404,22 +372,16 @@ __global__ __launch_bounds__(1024, (NK <= 8 && NH == 2 ? PT_C2_MINW : 4)) void k
     PT_STAMP(a, 3);
 
     f32x4 acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0}, acc2 = {0, 0, 0, 0}, acc3 = {0, 0, 0, 0}, accL = {0, 0, 0, 0};
-#if PT_C2_AV_UPFRONT
     // the wave's NK filter-operand values in one batch of LDS reads in front of the loop (round 6: inside the loop every k-step was
     // read -> wait -> 4 MFMAs, the uniform leftover-tile branches keep the compiler from hoisting the next read over them)
     float avv[NK];
 #pragma unroll
     for (int k = 0; k < NK; ++k) avv[k] = afilt[(4 * (h * NK + k) + kq) * 16 + j];
     __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
         if (k + CD < NK) ldq(k + CD);
-#if PT_C2_AV_UPFRONT
         const float av = avv[k];
-#else
-        const float av = afilt[(4 * (h * NK + k) + kq) * 16 + j];
-#endif
         acc0 = mfma16(av, bq[k][0], acc0);
         acc1 = mfma16(av, bq[k][1], acc1);
         acc2 = mfma16(av, bq[k][2], acc2);
@@ -462,11 +424,7 @@ __global__ __launch_bounds__(1024, (NK <= 8 && NH == 2 ? PT_C2_MINW : 4)) void k
       for (int s2 = 0; s2 < nsm; ++s2) {                            // uniform: one round of the block per sample of the pair
         const float* __restrict__ T0 = lds + nsl + (long)s2 * NH * KK * hHWp;
         const float* __restrict__ T1 = T0 + (long)KK * hHWp;      // second k-step half (NH == 2)
-#if defined(PT_C2_OUT_GLOBAL) && PT_C2_OUT_GLOBAL
-        const auto out = pt_global((float*)a.spart) + ((long)x * a.n + (pair ? 2 * i0 + s2 : i0)) * OO;   // global_store instead of flat_store (A/B knob)
-#else
         const pt_gf out = a.spart + ((long)x * a.n + (pair ? 2 * i0 + s2 : i0)) * OO;
-#endif
         // Round 6 (profiles/r06l_pass_ablation.txt: this loop is 0.9 us of the pass, bound by VALU issue -- ~100 vector instructions per output
         // around 16 LDS reads): the 16 taps of an output sit at  base + u (4 HWp + W) + v (HWp + 1)  with a per-output base and UNIFORM
         // steps, and whether a tap lies inside the map is (row u ok) & (column v ok): 8 compares and one add per tap instead of two compares,
@@ -474,8 +432,7 @@ __global__ __launch_bounds__(1024, (NK <= 8 && NH == 2 ? PT_C2_MINW : 4)) void k
         // earlier planes lie in front of it; behind the last plane its own padding, or -- 22x22: HWp = 516 < HW + 2 W + 2 -- slack the plan
         // adds to the allocation) and is replaced by 0 through a BIT mask, so uninitialised slack cannot leak a NaN.  Same values added in
         // the same order: same bits.
-        const bool direct = PT_C2_SA_DIRECT && a.sa_direct;                                         // uniform
-        if (direct) {
+        if (a.sa_direct) {                                                                          // uniform
             const int su = 4 * hHWp + a.W, sv = hHWp + 1;
             for (int o = threadIdx.x; o < OO; o += nthreads) {
                 const int y = fdiv(o, inv_ow), xx0 = o - y * a.OW;
@@ -529,9 +486,6 @@ __global__ __launch_bounds__(1024, (NK <= 8 && NH == 2 ? PT_C2_MINW : 4)) void k
             float s = 0.f;
 #pragma unroll
             for (int q = 0; q < 16; ++q) s += tv[q];
-#if defined(PT_C2_EXP) && PT_C2_EXP == 1
-            s = T0[o];                                               // ABLATION (wrong results, timing only): no shift-and-add
-#endif
             out[o] = s;
         }
       }
@@ -1012,15 +966,12 @@ __global__ __launch_bounds__(PT_ADJ_WAVES * 64) void k_adj2(const float* h_feat,
         an_in = lane < hKS ? h_anum[lane] : 0.f;
     }
     PT_STAMP_B(a_arg, 1);
-    if (PT_ADJ_BAR) __syncthreads();
     f32x4 av[UM];
-    if (PT_ADJ_EARLY) {
 #pragma unroll
-        for (int u = 0; u < PD; ++u) {
-            int qi, qp;
-            quad_at(kq, wave, u, qi, qp);
-            av[u] = pt_bload4(fr, ((unsigned)qi * (unsigned)h_stride + (unsigned)qp) * 4u + chw4);
-        }
+    for (int u = 0; u < PD; ++u) {                                  // first feature loads in front of the LDS work
+        int qi, qp;
+        quad_at(kq, wave, u, qi, qp);
+        av[u] = pt_bload4(fr, ((unsigned)qi * (unsigned)h_stride + (unsigned)qp) * 4u + chw4);
     }
     __builtin_amdgcn_sched_barrier(0);                              // nothing that needs the argument block above this line
     PtLate<Adj2Late> late = pt_late_issue<Adj2Late>(56);            // 5 pointers / longs + 4 dwords = 56 bytes
@@ -1098,10 +1049,6 @@ __global__ __launch_bounds__(PT_ADJ_WAVES * 64) void k_adj2(const float* h_feat,
     i32x4 cell[UM];
     auto issue = [&](int u) { av[u] = pt_bload4(fr, (unsigned)foff[u] + chw4); };
     auto cells = [&](int u) { cell[u] = *(const i32x4*)__builtin_assume_aligned(tabI + 4 * (tq + u), 16); };
-    if (!PT_ADJ_EARLY) {
-#pragma unroll
-        for (int u = 0; u < PD; ++u) issue(u);
-    }
     float astep = 0.f;
     if (V != V_PLAIN && a.t > 0) {
         const float a_num = wave_sum(an_in);
@@ -1133,29 +1080,13 @@ __global__ __launch_bounds__(PT_ADJ_WAVES * 64) void k_adj2(const float* h_feat,
     //      A wave stalls at a load it cannot issue (the CU's memory pipeline accepts ~20-45 B/clk), so the loads are
     //      software-pipelined PD groups ahead of the MFMAs that consume them instead of being issued all up front.
     //      The loop is bound by instruction issue (3.3 of the pass's 7.6 us: 11 vector / LDS instructions around 4 MFMAs per group,
-    //      profiles/r04a_pmc_counters.txt).  Experiment PT_ADJ_G2 (round 4, lost): with an even map width a row wrap can only fall
-    //      between a quad's second and third position, so cells (0,1) and (2,3) are neighbours in the padded map and the four scalar
-    //      gathers can be two 8-byte LDS reads -- at 4-byte alignment, which the LDS serves far slower than four aligned dwords.
+    //      profiles/r04a_pmc_counters.txt).  Gathering a quad's cells as two 8-byte LDS reads at 4-byte alignment (even map
+    //      widths) lost: k_adj2 7.6 -> 12.0 us; as two dword-pair reads 7.55 -> 7.94 us (profiles/r04j_adjoint_pair_gather_ab.txt).
     f32x4 accA = {0, 0, 0, 0}, accB = {0, 0, 0, 0};
-    auto mfma_loop = [&](auto pair_tag) {
-        constexpr bool G2 = decltype(pair_tag)::value;
+    auto mfma_loop = [&]() {                                        // (a lambda: written inline the compiler schedules the pass differently)
         auto gather = [&](int u) {
-            if constexpr (G2) {
-                const f32x2a4 lo = *(const f32x2a4*)((const char*)maps + ((unsigned)cell[u][0] + tapoff4));
-                const f32x2a4 hi = *(const f32x2a4*)((const char*)maps + ((unsigned)cell[u][2] + tapoff4));
-                bv[u][0] = lo[0]; bv[u][1] = lo[1]; bv[u][2] = hi[0]; bv[u][3] = hi[1];
-            } else {
-#if defined(PT_ADJ_EXP) && PT_ADJ_EXP == 1
-                // ABLATION (wrong results, timing only; profiles/r06l_*): the four scalar gathers of a group as ONE aligned 16-byte read -- what a
-                // layout with four shifted copies of every residual map could reach at best
-                const f32x4 qv = *(const f32x4*)__builtin_assume_aligned((const char*)maps + (((unsigned)cell[u][0] + tapoff4) & ~15u), 16);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) bv[u][k] = qv[k];
-#else
-#pragma unroll
-                for (int k = 0; k < 4; ++k) bv[u][k] = *(const float*)((const char*)maps + ((unsigned)cell[u][k] + tapoff4));
-#endif
-            }
+            for (int k = 0; k < 4; ++k) bv[u][k] = *(const float*)((const char*)maps + ((unsigned)cell[u][k] + tapoff4));
         };
         cells(0);
         if (UM > 1) cells(1);
@@ -1172,8 +1103,7 @@ __global__ __launch_bounds__(PT_ADJ_WAVES * 64) void k_adj2(const float* h_feat,
             accB = mfma16(av[u][3], bv[u][3], accB);
         }
     };
-    if (PT_ADJ_G2 && (hW & 1) == 0) mfma_loop(std::true_type{});    // uniform
-    else mfma_loop(std::false_type{});
+    mfma_loop();
     PT_STAMP_A(a, 5);
 #pragma unroll
     for (int r = 0; r < 4; ++r) red[wave][(4 * kq + r) * 16 + j] = accA[r] + accB[r];

@@ -852,8 +852,7 @@ int pt_iou_refine_validate(const pt_iou_dims* d, const float* params, const floa
     if (P > 256) return PT_ERR_UNSUPPORTED;
     const IouCarve cv = iou_carve(d, P);
     if (ws_bytes < cv.total * sizeof(float) || ((uintptr_t)ws % 256) != 0) return PT_ERR_WORKSPACE;
-    static const bool unfused = [] { const char* e = getenv("PT_IOU_UNFUSED"); return e && e[0] == '1'; }();   // ablation switch
-    const bool fused = P <= FUSED_MAX_P && !unfused;
+    const bool fused = P <= FUSED_MAX_P;
     if ((boxes_on_host || seq != 0.f) && !fused) return PT_ERR_UNSUPPORTED;
     if (with_mid && (!fused || P > 16)) return PT_ERR_UNSUPPORTED;
     return PT_OK;
@@ -877,8 +876,7 @@ static int iou_refine_impl(const pt_iou_dims* d, const float* params, const floa
     SetupArgs sa{init_boxes, mod3, mod4, base + cv.state, base + cv.szn, base + cv.rois, base + cv.msc3, base + cv.msc4,
                  base + cv.prev, base + cv.slen, base + cv.pstep, P, K3, K4, relative,
                  {step_length4[0], step_length4[1], step_length4[2], step_length4[3]}, nullptr};
-    static const bool unfused = [] { const char* e = getenv("PT_IOU_UNFUSED"); return e && e[0] == '1'; }();   // ablation switch
-    const bool fused = P <= FUSED_MAX_P && !unfused;
+    const bool fused = P <= FUSED_MAX_P;
     if (fused) { sa.st0 = base + cv.st2; sa.K3 = sa.K4 = 0; }          // the per-column modulation tables belong to the unfused path
     if (boxes_on_host) {
         sa.boxes = nullptr; sa.use_hb = 1;

@@ -40,6 +40,8 @@ struct GemmArgs {
                                                 // a_zstride / w_zstride floats apart, output at C + z*c_zstride
     // k_gemm_ps<.., LNA> (round 6): the A operand is LayerNorm(A) over its K = 256 columns (eps 1e-5, affine ln_gam / ln_bet), formed
     // in registers on the way into LDS; the column-tile-0 workgroups also store the normalised rows to ln_out (row stride K)
+    // (no caller sets these since the fold lost its A/B, profiles/r06p_tomp_ln1_fold.txt; kept: the layout of this struct is the
+    // kernel-argument layout of every k_gemm* kernel)
     const float* ln_gam; const float* ln_bet; float* ln_out;
 };
 
@@ -723,23 +725,11 @@ GemmArgs gemm_args(const float* A, long lda, long a_rows, const float* Wt, int M
 // 32x32x64 everywhere except wide outputs (N >= 1024, many rows), where 64x64 tiles with 32-wide K steps halve the operand
 // traffic per flop and two workgroups still fit a CU: FFN first GEMM 36.3 -> 28.0 us.  Larger tiles (128x64, 128x128) run
 // their K steps at 67-74 % of the MFMA rate but leave too few workgroups at these sizes.
-// experiment knob: smallest N that takes the 64 x 64 tile kernel (PT_GEMM_T64N, default 1024)
-static int pt_gemm_tile64_min_n() {
-    static const int v = [] { const char* e = getenv("PT_GEMM_T64N"); return e ? atoi(e) : 1024; }();
-    return v;
-}
-
-// experiment knob: tile of long-K narrow-N products (PT_GEMM_LONGK: 0 = 32 x 32, 1 = 32 x 64, 2 = 64 x 32)
-static int pt_gemm_longk_tile() {
-    static const int v = [] { const char* e = getenv("PT_GEMM_LONGK"); return e ? atoi(e) : 0; }();
-    return v;
-}
+constexpr int GEMM_TILE64_MIN_N = 1024;                            // smallest N that takes the 64 x 64 tile kernel
 
 // gemm_store_t's conditions: plain row-major C, 16-byte aligned rows and bias, nothing but bias / ReLU / split offset in the epilogue
-// (PT_GEMM_WIDE_STORE=0: the 4-byte epilogue, A/B knob)
 static bool wide_store_ok(const GemmArgs& g) {
-    static const bool on = [] { const char* e = getenv("PT_GEMM_WIDE_STORE"); return !(e && e[0] == '0'); }();
-    return on && !g.R && !g.scale && !g.shift && !g.expo && !g.nchw && g.c_segstride == 0 && g.N % 4 == 0 && g.ldc % 4 == 0 && g.c_zstride % 4 == 0 &&
+    return !g.R && !g.scale && !g.shift && !g.expo && !g.nchw && g.c_segstride == 0 && g.N % 4 == 0 && g.ldc % 4 == 0 && g.c_zstride % 4 == 0 &&
            ((uintptr_t)g.C % 16) == 0 && (!g.bias || ((uintptr_t)g.bias % 16) == 0);
 }
 
@@ -751,12 +741,10 @@ int launch_gemm(const GemmArgs& g, hipStream_t st, bool conv = false) {
     const long rows = g.nchw ? (long)g.M * g.N : (g.c_segstride ? ((long)(g.M / g.c_seg) + 1) * g.c_segstride * g.ldc
                                                                    : (long)g.M * g.ldc);
     if ((rows + (long)(nz - 1) * g.c_zstride) * 4 >= 0xFFFFFFE0L) return PT_ERR_UNSUPPORTED;
-    // round 6: 128 x 64 tiles, two workgroups per CU (PT_GEMM_PS=0: the round-5 routes), for
+    // round 6: 128 x 64 tiles, two workgroups per CU (every other shape: the round-5 routes below), for
     //   * wide outputs at short K (FFN first product: N = 2048, K = 256 -> 512 workgroups of 8 stages)
     //   * split-K products the caller asked to be cut in >= 4 (FFN second product: 256 workgroups of 16 stages, M tiles on x)
-    static const bool ps_on = [] { const char* e = getenv("PT_GEMM_PS"); return !(e && e[0] == '0'); }();
-    static const bool ps_qkv = [] { const char* e = getenv("PT_GEMM_PS_QKV"); return !(e && e[0] == '0'); }();
-    if (ps_on && ps_qkv && !conv && g.pos && g.M >= 1024 && g.K % 32 == 0 && !g.batch && !g.nchw && nz == 1 && g.N % 64 == 0 && g.pos_cols % 64 == 0 &&
+    if (!conv && g.pos && g.M >= 1024 && g.K % 32 == 0 && !g.batch && !g.nchw && nz == 1 && g.N % 64 == 0 && g.pos_cols % 64 == 0 &&
         g.c_segstride == 0 && g.N >= 512) {
         // the attention's input projection (N = 3 D = 768, K = 256, "+pos" on the q | k column tiles): 64 x 64 tiles of 4 waves, 37 KB LDS,
         // up to four workgroups per CU; the 32 x 32 route took 16.2 us for 0.76 GFLOP (1464 workgroups = 1.45 rounds)
@@ -766,17 +754,7 @@ int launch_gemm(const GemmArgs& g, hipStream_t st, bool conv = false) {
         PT_CHECK_LAUNCH();
         return PT_OK;
     }
-    if (g.ln_gam) {
-        // LayerNorm on the A operand: served by the 128 x 64 pinned-schedule kernel only (never dropped silently)
-        if (!(ps_on && !conv && g.K == 256 && g.lda == 256 && !g.pos && !g.batch && !g.nchw && nz == 1 && !g.ksteps && g.ln_bet && wide_store_ok(g) &&
-              ((uintptr_t)g.A % 16) == 0 && ((uintptr_t)g.ln_gam % 16) == 0 && ((uintptr_t)g.ln_bet % 16) == 0 && ((uintptr_t)g.ln_out % 16) == 0))
-            return PT_ERR_UNSUPPORTED;
-        constexpr size_t lds = (2 * (128 + 64) * GB_LS + 512) * sizeof(float);
-        hipLaunchKernelGGL((k_gemm_ps<4, 2, 2, 2, false, true, true>), dim3((g.N + 63) / 64, (g.M + 127) / 128, 1), dim3(512), lds, st, g);
-        PT_CHECK_LAUNCH();
-        return PT_OK;
-    }
-    if (ps_on && !conv && g.M >= 1024 && g.K % 32 == 0 && !g.pos && !g.batch && !g.nchw && ((g.N >= 1024 && nz == 1) || (nz >= 4 && g.N % 64 == 0))) {
+    if (!conv && g.M >= 1024 && g.K % 32 == 0 && !g.pos && !g.batch && !g.nchw && ((g.N >= 1024 && nz == 1) || (nz >= 4 && g.N % 64 == 0))) {
         constexpr size_t lds = 2 * (128 + 64) * GB_LS * sizeof(float);
         const bool sw = wide_store_ok(g);
         if (nz == 1 && sw) hipLaunchKernelGGL((k_gemm_ps<4, 2, 2, 2, false, true>), dim3((g.N + 63) / 64, (g.M + 127) / 128, 1), dim3(512), lds, st, g);
@@ -803,25 +781,12 @@ int launch_gemm(const GemmArgs& g, hipStream_t st, bool conv = false) {
         } else {
             hipLaunchKernelGGL((k_gemm<32, 32, 1>), dim3((g.N + 31) / 32, (g.M + 31) / 32, nz), dim3(256), 0, st, g);
         }
-    } else if (g.N >= pt_gemm_tile64_min_n() && g.M >= 1024 && nz == 1 && g.K % 32 == 0) {
+    } else if (g.N >= GEMM_TILE64_MIN_N && g.M >= 1024 && nz == 1 && g.K % 32 == 0) {
         GemmArgs gs = g;
         const int gy = (g.M + 63) / 64;
         gs.swizzle = gy >= 16;
         hipLaunchKernelGGL((k_gemm<64, 64, 0, 32>), dim3((g.N + 63) / 64, gs.swizzle ? (gy + 7) / 8 * 8 : gy, 1), dim3(256), 0,
                            st, gs);
-    } else if (pt_gemm_longk_tile() && !g.batch && nz == 1 && g.K >= 1024 && g.K % 32 == 0 && g.M >= 1024 && g.N >= 64) {
-        // long-K, narrow-N products (the FFN's second GEMM: 1944 x 256 x 2048): 32 x 32 tiles re-read both operands through L2
-        // 488 times; a 2:1 tile halves one operand's traffic at the same workgroup count per CU
-        GemmArgs gs = g;
-        if (pt_gemm_longk_tile() == 1) {
-            const int gy = (g.M + 31) / 32;
-            gs.swizzle = gy >= 16;
-            hipLaunchKernelGGL((k_gemm<32, 64, 0>), dim3((g.N + 63) / 64, gs.swizzle ? (gy + 7) / 8 * 8 : gy, 1), dim3(256), 0, st, gs);
-        } else {
-            const int gy = (g.M + 63) / 64;
-            gs.swizzle = gy >= 16;
-            hipLaunchKernelGGL((k_gemm<64, 32, 0>), dim3((g.N + 31) / 32, gs.swizzle ? (gy + 7) / 8 * 8 : gy, 1), dim3(256), 0, st, gs);
-        }
     } else {
         GemmArgs gs = g;
         const int gy = (g.M + 31) / 32;

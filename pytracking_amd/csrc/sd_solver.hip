@@ -335,23 +335,17 @@ __global__ __launch_bounds__(1024) void k_fast_sgq2(const float* __restrict__ sp
     const int oc = min(o, OO - 1);
     const long q = (long)i * OO + oc;
     const int nthreads = ((OO + 63) >> 6) << 6;
-    // PT_SGQ_EXP (experiments only, profiles/r06c_*: where do the 1.9 us between this kernel and an empty one go?):
-    //   1: no loads (operands from the thread index)   2: no stores   3: neither   4: no block reduction (q_i of wave 0 only)
-#ifndef PT_SGQ_EXP
-#define PT_SGQ_EXP 0
-#endif
     float v[PT_PW_MAXKS];
     {
         const float* p = spart + q;
         const long st = (long)n * OO;
 #pragma unroll
-        for (int k = 0; k < PT_PW_MAXKS; ++k) v[k] = (PT_SGQ_EXP & 1) && PT_SGQ_EXP != 4 ? 1e-3f * (float)(o + k) : p[(long)min(k, KS - 1) * st];
+        for (int k = 0; k < PT_PW_MAXKS; ++k) v[k] = p[(long)min(k, KS - 1) * st];
     }
-    const float sv = (PT_SGQ_EXP & 1) && PT_SGQ_EXP != 4 ? 0.5f : sp[q];
+    const float sv = sp[q];
     f32x4 lm = {0, 0, 0, 0};
     float P = 0.f, L = 0.f;
-    if ((PT_SGQ_EXP & 1) && PT_SGQ_EXP != 4) { lm = (f32x4){0.1f, 0.5f, 1.0f, 0.f}; P = 0.01f; L = 0.01f; }
-    else if (kind != PT_SD_PRDIMP) lm = ((const f32x4*)p3)[q];
+    if (kind != PT_SD_PRDIMP) lm = ((const f32x4*)p3)[q];
     else { P = p3[q]; L = p4[q]; }
     __builtin_amdgcn_sched_barrier(0);
     const SgqLate l = pt_late_args<SgqLate>(48);                    // 4 pointers + 3 dwords = 44 bytes, 8-aligned
@@ -363,7 +357,6 @@ __global__ __launch_bounds__(1024) void k_fast_sgq2(const float* __restrict__ sp
         float act, der;
         act_pair(sact, act_param, sv, lm[1], act, der);
         const float qq = lm[2] * (der * sgv);                                       // :151-152
-#if PT_SGQ_EXP == 0
         // Round 6 (profiles/r06c_sgq_ablation.txt: the block reduction cost 0.43 us of this launch in the chain -- two barriers with the
         // result stores queued behind them): the element stores go out first, then ONE barrier; the waves that only contribute a
         // partial sum end there, thread 0 adds the partials in block_sum's order (same bits) and stores q_i.
@@ -382,17 +375,6 @@ __global__ __launch_bounds__(1024) void k_fast_sgq2(const float* __restrict__ sp
             for (int w = 0; w < (nthreads >> 6); ++w) tot += scratch[w];
             l.qs[i] = tot;
         }
-#else
-        const float tot = PT_SGQ_EXP == 4 ? wave_sum(ok ? qq * qq : 0.f) : block_sum(ok ? qq * qq : 0.f, scratch, nthreads);
-        if (ok && !((PT_SGQ_EXP & 2) && PT_SGQ_EXP != 4 && tot != 123.456f)) {
-            l.sg[q] = sgv;
-            f32x4 pk;
-            if (kind == PT_SD_DIMP && score_act == PT_ACT_BENTPAR) pk = (f32x4){sv, sgv, lm[0], lm[1]};
-            else { const float w2 = lm[2] * lm[2]; pk = (f32x4){w2 * sv, w2 * sgv, w2 * lm[0], lm[1]}; }
-            ((f32x4*)l.pk)[q] = pk;
-        }
-        if (o == 0) l.qs[i] = tot;
-#endif
     } else {
         const float swp = has_sw ? l.sw[i] : 1.0f / (float)n;
         const float tot = block_sum(ok ? P * sgv : 0.f, scratch, nthreads);                   // :419
@@ -415,9 +397,6 @@ __global__ __launch_bounds__(1024) void k_fast_sgq2(const float* __restrict__ sp
 #else
 #define PT_SD_FUSE_INIT 1      // 0 (A/B builds): never fold the init stage into the first adjoint pass
 #endif
-#endif
-#ifndef PT_INIT_LUT_HOT
-#define PT_INIT_LUT_HOT 1      // 0 (A/B builds): always take the look-up tables through the late argument block
 #endif
 struct InitLate {
     pt_gcf label_lut, mask_lut, spatial_lut;
@@ -707,7 +686,7 @@ static int sd_solve_fast(const PtFast& f, const pt_sd_params* prm, const float* 
         const unsigned cslot = (a.cls_spart && a.cls_slot >= 0) ? (unsigned)a.cls_slot : 0xfffffu;
         hipLaunchKernelGGL(k_fast_init2, dim3(n), dim3(pw_threads), lut_lds, st, (const float*)a.spart, a.bb, a.has_sw ? a.sw : (const float*)nullptr,
                            a.cls_slot_dyn,
-                           (PT_INIT_LUT_HOT && a.kind == PT_SD_DIMP && a.mask_lut == a.label_lut + a.num_bins &&
+                           (a.kind == PT_SD_DIMP && a.mask_lut == a.label_lut + a.num_bins &&
                             a.spatial_lut == a.label_lut + 2 * a.num_bins) ? a.label_lut : (const float*)nullptr,
                            (unsigned)n | ((unsigned)a.OO << 16), (unsigned)a.KS | ((unsigned)a.kind << 8) | (cslot << 12),
                            (unsigned)a.OW | ((unsigned)a.K << 12) | ((unsigned)(a.kind == PT_SD_DIMP ? a.num_bins : 0) << 16), a.feat_stride, il);
@@ -746,8 +725,7 @@ static int sd_solve_fast(const PtFast& f, const pt_sd_params* prm, const float* 
         // the last update stays pending: (w_{T-1}, g_T, qs, anum) are in the workspace, the next call of the chain applies it
         pend->iters = num_iter; pend->step_length = a.step; pend->reg_eps = a.reg + a.alpha_eps;
     } else if (num_iter > 0) {
-        static const bool final_old = std::getenv("PT_SD_FINAL_OLD") != nullptr;     // experiment: the struct-argument kernel
-        if (!want_loss && !final_old)
+        if (!want_loss)
             hipLaunchKernelGGL(k_fast_final, dim3(n), dim3(512), 0, st, sd_w_host(a, num_iter - 1), (const float*)a.g,
                                a.w_final ? a.w_final : a.w_iters + (long)num_iter * a.CKK, (const float*)a.qs, (const float*)a.anum, n, a.CKK,
                                a.KS, a.step, a.reg + a.alpha_eps);
@@ -793,23 +771,12 @@ int pt_sd_solve_impl(const pt_sd_params* prm, const float* w_in, const float* fe
     float* base = (float*)ws;
 
     SdArgs a;
-    a.n = n; a.C = C; a.H = H; a.W = W; a.K = K; a.OH = OH; a.OW = OW; a.OO = OH * OW; a.CKK = C * K * K;
+    sd_fill_params(a, prm, bb, sample_weight, n, C, H, W, K, OH, OW);
     a.KS = p.KS; a.KSPL = p.KSPL;
-    a.kind = prm->kind; a.score_act = prm->score_act; a.mask_act = prm->mask_act; a.has_sw = sample_weight != nullptr;
-    a.has_softmax_reg = prm->has_softmax_reg; a.normalize_label = prm->normalize_label; a.num_bins = prm->num_bins;
-    a.step = prm->step_length; a.reg = prm->reg; a.alpha_eps = prm->alpha_eps; a.feat_stride = prm->feat_stride;
-    a.bin_disp = prm->bin_displacement; a.act_param = prm->act_param; a.gauss_sigma = prm->gauss_sigma;
-    a.hinge_thr = prm->hinge_threshold; a.uni_weight = prm->uni_weight; a.label_shrink = prm->label_shrink;
-    a.softmax_reg = prm->softmax_reg; a.label_thr = prm->label_threshold;
-    a.bb = bb; a.sw = sample_weight; a.label_lut = prm->label_lut; a.mask_lut = prm->mask_lut;
-    a.spatial_lut = prm->spatial_lut;
     a.label = base + cv.label; a.mask = base + cv.mask; a.sws = base + cv.sws; a.s = base + cv.s; a.sg = base + cv.sg;
     a.spart = base + cv.spart; a.R = base + cv.R; a.gpart = base + cv.gpart; a.g = base + cv.g;
     a.anum = base + cv.anum; a.qs = base + cv.qs; a.lossp = base + cv.lossp; a.w_iters = w_iters;
     a.w0 = w_in; a.w_final = w_final;
-    a.s_in = nullptr; a.lms = nullptr; a.pk = nullptr; a.cls_stride = 0;
-    a.cls_spart = nullptr; a.cls_KS = 0; a.cls_slot = -1; a.cls_scores = nullptr; a.cls_peak = nullptr; a.cls_bb = nullptr;
-    a.cls_slot_dyn = nullptr;
     if (cls && cls->slot_dyn) return PT_ERR_UNSUPPORTED;                // a device-resident slot exists on the fast path only
     if (cls) {
         a.cls_spart = cls->spart; a.cls_KS = cls->KS; a.cls_stride = a.OO; a.cls_slot = cls->slot; a.cls_scores = cls->scores;

@@ -44,15 +44,8 @@ struct AttnArgs {
 // Workgroup = 64 queries x 2 key halves: wavefronts 0-3 own the even 64-key chunks, 4-7 the odd ones (two wavefronts per
 // SIMD, so one half's softmax / LDS waits hide behind the other's MFMAs -- B*nhead*L/16 query tiles alone are only one
 // wavefront per SIMD); the halves' (max, sum, O^T) are merged through LDS at the end.
-// PT_ATTN_EXP (experiments only, WRONG results, timing: profiles/r06q_attention_ablation.txt) -- bit mask:
-//   1: no exponentials (P = S - m)      2: K / V staged once (no stash, no barriers after the first iteration)
-//   4: fragments read from LDS once per iteration instead of per tile      8: K / V fetched from memory once
-#ifndef PT_ATTN_EXP
-#define PT_ATTN_EXP 0
-#endif
-#ifndef PT_ATTN_PIPE_EXP
-#define PT_ATTN_PIPE_EXP 0   // 1 (experiment, no gain: r06q): exponentials of the next key tile issued between the PV MFMAs of the current one
-#endif
+// (Issuing the exponentials of the next key tile between the PV MFMAs of the current one: same bits, no gain, 0.8875-0.8890 vs
+// 0.8850-0.8878 ms -- profiles/r06q_attention_ablation.txt.)
 template <int HD>
 __global__ __launch_bounds__(512) void k_attn(AttnArgs a) {
     constexpr int KS = HD + 4, NV = HD / 4, NF4 = HD / 16, DT = HD / 16;   // NV floats of q/k per lane, NF4 float4s
@@ -119,19 +112,15 @@ __global__ __launch_bounds__(512) void k_attn(AttnArgs a) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) pk[r] = prow(4 * kq + r);
     int it = 0;
-    bool first = true;                                            // (ablation builds only)
     while (it < nit && !live(it)) ++it;
     if (it < nit) fetch(it * 128);
     while (it < nit) {
         int nx = it + 1;
         while (nx < nit && !live(nx)) ++nx;
-        if (!(PT_ATTN_EXP & 2) || first) {
-            __syncthreads();                                      // previous iteration's LDS reads are done
-            stash();
-            __syncthreads();
-        }
-        if (nx < nit && !((PT_ATTN_EXP & 8) && !first)) fetch(nx * 128);
-        first = false;
+        __syncthreads();                                          // previous iteration's LDS reads are done
+        stash();
+        __syncthreads();
+        if (nx < nit) fetch(nx * 128);
         const int c0 = it * 128 + half * 64;
         it = nx;
         if (c0 >= a.L || (c0 >= mlo && c0 + 64 <= mhi)) continue;  // wave-uniform: nothing but padding in this half chunk
@@ -159,12 +148,10 @@ __global__ __launch_bounds__(512) void k_attn(AttnArgs a) {
             }
         };
         read_k(0, 0);
-        if (PT_ATTN_EXP & 4) { read_k(1, 1); read_v(0, 0); read_v(1, 1); }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt) {
-            if (PT_ATTN_EXP & 4) {}
-            else if (kt < 3) read_k(kt + 1, (kt + 1) & 1);
+            if (kt < 3) read_k(kt + 1, (kt + 1) & 1);
             else read_v(0, 0);
             __builtin_amdgcn_sched_barrier(0);
             f32x4 sc = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -189,7 +176,7 @@ __global__ __launch_bounds__(512) void k_attn(AttnArgs a) {
         mc = fmaxf(mc, __shfl_xor(mc, 32, 64));
         const float m_new = fmaxf(m_run, mc);
         const float m_use = m_new == -INFINITY ? 0.f : m_new;
-        const float alpha = (PT_ATTN_EXP & 1) ? 0.5f : __expf(m_run - m_use);                 // m_run = -inf -> 0
+        const float alpha = __expf(m_run - m_use);                 // m_run = -inf -> 0
         l_run *= alpha;
 #pragma unroll
         for (int d = 0; d < DT; ++d) ot[d] *= alpha;
@@ -197,45 +184,19 @@ __global__ __launch_bounds__(512) void k_attn(AttnArgs a) {
         // ---- P^T = exp(S^T - m) feeds the PV product straight from the accumulator registers:
         //      O^T[d][query] += sum_key V[key][d] * P^T[key][query]; k-slot kq of MFMA r <-> key prow(4*kq + r) of the tile
         __builtin_amdgcn_sched_barrier(0);
-#if PT_ATTN_PIPE_EXP
-        // Round 6 experiment (profiles/r06q_attention_ablation.txt: the exponentials are 2.3 us of the launch): the four exponentials of
-        // tile kt + 1 issued one behind each PV MFMA pair of tile kt (ISA: M M E x 12), only tile 0's in front.  Same bits -- and NO gain
-        // (0.8875-0.8890 vs 0.8850-0.8878 ms): the transcendental issue does not overlap the matrix pipe's issue on this SIMD.
-        auto pexp = [&](float sv) { return (PT_ATTN_EXP & 1) ? sv - m_use : __expf(sv - m_use); };
-        float pc[4], pn[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) pc[r] = pexp(st[0][r]);
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt) {
-            if (kt < 3 && !(PT_ATTN_EXP & 4)) read_v(kt + 1, (kt + 1) & 1);
+            if (kt < 3) read_v(kt + 1, (kt + 1) & 1);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                l_run += pc[r];
-#pragma unroll
-                for (int d = 0; d < DT; ++d) ot[d] = mfma16(vf[kt & 1][r][d], pc[r], ot[d]);
-                __builtin_amdgcn_sched_barrier(0);
-                if (kt < 3) pn[r] = pexp(st[kt < 3 ? kt + 1 : 3][r]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) pc[r] = pn[r];
-        }
-#else
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt) {
-            if (kt < 3 && !(PT_ATTN_EXP & 4)) read_v(kt + 1, (kt + 1) & 1);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float pe = (PT_ATTN_EXP & 1) ? st[kt][r] - m_use : __expf(st[kt][r] - m_use);
+                const float pe = __expf(st[kt][r] - m_use);
                 l_run += pe;
 #pragma unroll
                 for (int d = 0; d < DT; ++d) ot[d] = mfma16(vf[kt & 1][r][d], pe, ot[d]);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-#endif
     }
     l_run += __shfl_xor(l_run, 16, 64);
     l_run += __shfl_xor(l_run, 32, 64);
@@ -358,14 +319,6 @@ __global__ __launch_bounds__(256) void k_ln_rows(const float* in, float* out, co
         const int c = lane * per + i;
         out[(long)row * D + c] = (v[i] - mean) * rstd * gam[c] + bet[c];
     }
-}
-
-// The FFN's second product (K = dim_ff) runs as two K-halves whose partial sums, bias included, meet in the LayerNorm that follows
-// (which then also adds the residual): 976 instead of 488 workgroups of half the K loop, ToMP frame 1.006 -> 0.996 ms (round 4,
-// profiles/r04e_*).  PT_TOMP_FFN2_SPLIT=0 restores the single product (A/B knob).
-static int pt_tomp_ffn2_split() {
-    static const int v = [] { const char* e = getenv("PT_TOMP_FFN2_SPLIT"); return e ? atoi(e) : 4; }();   // round 6: 4 (k_gemm_ps); 2 = round 4's halves
-    return v;
 }
 
 // in2 / in3 are only served by the 256-wide vector path: callers check ln_rows_wide_ok() first
@@ -1344,8 +1297,7 @@ extern "C" int pt_tomp_predict_f32(const pt_tomp_dims* d, const float* params, c
     {
         TokArgs t{train_feat, test_feat, train_label, P + po.fg, P + po.testtok, X, n_train, n_seq, parallel ? 1 : 0, D,
                   HW, L, base + cv.zero, B * D, {nullptr, nullptr}, {nullptr, nullptr}, {0, 0}, B};
-        static const bool dec0_off = [] { const char* e = getenv("PT_TOMP_DEC0"); return e && e[0] == '0'; }();   // A/B knob
-        if (d->n_dec > 0 && (D + 31) / 32 >= 3 && !dec0_off) {    // layer 0 of the decoder: state after self-attention, folded query
+        if (d->n_dec > 0 && (D + 31) / 32 >= 3) {    // layer 0 of the decoder: state after self-attention, folded query
             const PrepLayout pl0 = prep_layout(D, NH, d->n_dec);
             t.cp_src[0] = prepared + pl0.dec[0].bsa; t.cp_dst[0] = base + cv.P1; t.cp_n[0] = D;
             t.cp_src[1] = prepared + pl0.qk0; t.cp_dst[1] = base + cv.qk; t.cp_n[1] = NH * D;
@@ -1387,43 +1339,24 @@ extern "C" int pt_tomp_predict_f32(const pt_tomp_dims* d, const float* params, c
         g = gemm_args(AO, D, rows, P + e.sa.w_out, rows, D, D, P + e.sa.b_out, Y, D);
         g.R = X;
         if ((rc = launch_gemm(g, st))) return rc;
-        // round 6, experiment P (LOST, profiles/r06p_tomp_ln1_fold.txt; opt-in PT_TOMP_LN1_FOLD=1): norm1 riding on the FFN's first
-        // product (k_gemm_ps<.., LNA>: the A slab normalised in registers, the column-tile-0 workgroups store X for the residual of
-        // norm2) saves a launch per layer, but the slab-up-front prologue costs that product 4.6 us (23.5 -> 28.1) against the 4.6 us
-        // LayerNorm launch (~3 in the chain): frame 0.885 -> 0.894 ms.
-        static const bool ln1_fold = [] { const char* e = getenv("PT_TOMP_LN1_FOLD"); return e && e[0] == '1'; }();
+        // (norm1 folded into the FFN's first product saved a launch per layer and lost: frame 0.885 -> 0.894 ms,
+        // profiles/r06p_tomp_ln1_fold.txt)
+        if ((rc = launch_ln_rows(Y, X, P + e.n1g, P + e.n1b, rows, D, st))) return rc;
+        PT_CHECK_LAUNCH();
         g = gemm_args(X, D, rows, P + e.w1, rows, ff, D, P + e.b1, Hd, ff);
         g.relu = 1;
-        bool folded = false;
-        if (ln1_fold && D == 256 && rows >= 1024 && ff >= 1024) {
-            GemmArgs gl = g;
-            gl.A = Y; gl.ln_gam = P + e.n1g; gl.ln_bet = P + e.n1b; gl.ln_out = X;
-            const int rl = launch_gemm(gl, st);
-            if (rl == PT_OK) folded = true;
-            else if (rl != PT_ERR_UNSUPPORTED) return rl;
-        }
-        if (!folded) {
-            if ((rc = launch_ln_rows(Y, X, P + e.n1g, P + e.n1b, rows, D, st))) return rc;
-            PT_CHECK_LAUNCH();
-            if ((rc = launch_gemm(g, st))) return rc;
-        }
+        if ((rc = launch_gemm(g, st))) return rc;
         const long rD = (long)rows * D;
-        if (pt_tomp_ffn2_split() == 4 && (ff / 64) % 4 == 0 && rows >= 1024 && D % 64 == 0 && cv.AO == cv.QKV + 3 * (size_t)rD &&
+        if ((ff / 64) % 4 == 0 && rows >= 1024 && D % 64 == 0 && cv.AO == cv.QKV + 3 * (size_t)rD &&
             ln_rows_wide_ok(QKV, X, P + e.n2g, P + e.n2b, D)) {
+            // The FFN's second product (K = dim_ff) runs as K-slices whose partial sums, bias included, meet in the LayerNorm that
+            // follows (which then also adds the residual); two halves: ToMP frame 1.006 -> 0.996 ms (round 4, profiles/r04e_*).
             // round 6: four K-quarters on 128 x 64 tiles (k_gemm_ps: 256 workgroups x 16 stages, M tiles on x) into the four row blocks
             // QKV[0..2], AO -- all free here -- that meet, with the residual, in the LayerNorm
             g = gemm_args(Hd, ff, rows, P + e.w2, rows, D, ff, P + e.b2, QKV, D);
             g.ksteps = ff / 64 / 4; g.c_zstride = rD;
             if ((rc = launch_gemm(g, st))) return rc;
             if ((rc = launch_ln_rows(QKV, X, P + e.n2g, P + e.n2b, rows, D, st, QKV + rD, X, nullptr, nullptr, QKV + 2 * rD, AO))) return rc;
-            PT_CHECK_LAUNCH();
-            continue;
-        }
-        if (pt_tomp_ffn2_split() == 2 && (ff / 64) % 2 == 0 && cv.Y > cv.AO && ln_rows_wide_ok(AO, X, P + e.n2g, P + e.n2b, D)) {
-            g = gemm_args(Hd, ff, rows, P + e.w2, rows, D, ff, P + e.b2, AO, D);
-            g.ksteps = ff / 64 / 2; g.c_zstride = (long)(cv.Y - cv.AO);          // halves -> AO, Y (bias rides on the first)
-            if ((rc = launch_gemm(g, st))) return rc;
-            if ((rc = launch_ln_rows(AO, X, P + e.n2g, P + e.n2b, rows, D, st, Y, X))) return rc;
             PT_CHECK_LAUNCH();
             continue;
         }

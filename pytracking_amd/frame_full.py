@@ -63,10 +63,8 @@ class FramePipeline:
         if graph:
             nb = _lib.lib().pt_track_frame_full_dyn_bytes()
             self._dyn_host = torch.zeros(nb, dtype=torch.uint8).pin_memory()
-            # PT_FRAME_DYN_COPY=1 (A/B knob): the block in device memory, refreshed by a copy node at the head of the graph; default: the
-            # kernels read the pinned host block directly (three small reads over the fabric instead of a ~10 us copy node in front of
-            # everything, profiles/r06i_*)
-            self._dyn_dev = torch.zeros(nb, dtype=torch.uint8, device=dev) if os.environ.get("PT_FRAME_DYN_COPY") == "1" else None
+            # the kernels read the pinned host block directly (three small reads over the fabric instead of a ~10 us copy node in
+            # front of everything, profiles/r06i_*)
             self._gstream = torch.cuda.Stream(device=dev)
         self._call = _lib.lib().pt_track_frame_full_f32
         self._ffref = ctypes.byref(f)
@@ -195,7 +193,7 @@ class FramePipeline:
                 dst.copy_(src, non_blocking=True)
         P = self._fill_frame(tracker, gb, slot, (g3, g4), sample_pos, sample_scales, rand_u)
         f = self.ff
-        f.dyn = self._dyn_dev.data_ptr() if self._dyn_dev is not None else self._dyn_host.data_ptr()
+        f.dyn = self._dyn_host.data_ptr()
         self._seq = self._seq + 1.0 if self._seq < 8388000.0 else 1.0
         rc = L.pt_track_frame_full_dyn_fill_f32(self._ffref, self._seq, self._host_ptr, self._ws_ptr, self._ws_len, self._dyn_host.data_ptr())
         if rc:
@@ -210,8 +208,6 @@ class FramePipeline:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.stream(s):
                 with torch.cuda.graph(g, stream=s):
-                    if self._dyn_dev is not None:
-                        self._dyn_dev.copy_(self._dyn_host, non_blocking=True)   # the copy node that refreshes the per-frame block
                     rc = L.pt_track_frame_full_launch_f32(self._ffref, self._host_ptr, self._ws_ptr, self._ws_len, s.cuda_stream)
             cur.wait_stream(s)
             if rc:

@@ -129,7 +129,7 @@ def refine_boxes(net, modulation, iou_features, init_boxes, num_iter, step_lengt
         if rc != _lib.PT_ERR_UNSUPPORTED:
             _lib.check(rc, "pt_iou_refine_sync_f32")
             return host[:4 * P].clone().view(P, 4), host[64:64 + P].clone()
-        # the fused iteration is switched off (PT_IOU_UNFUSED=1) or the stream is being captured: the regular device route
+        # more boxes than the fused iteration serves, or the stream is being captured: the regular device route
         boxes = boxes.to(c3.device)
     out_boxes = torch.empty_like(boxes)
     out_iou = torch.empty(P, dtype=torch.float32, device=c3.device)

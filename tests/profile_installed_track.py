@@ -9,7 +9,7 @@ timed run.  Reported per `track()` call:
   * wall time (device synchronised), update frames and classification-only frames separately;
   * host time by owner from cProfile (tottime, i.e. exclusive): this repo's wrappers (pytracking_amd/), the reference's Python
     (pytracking/, ltr/), the harness (oracle/, tests/), torch and other library code -- and the top functions of each;
-  * device time: sum of kernel durations per call when run under `rocprofv3 --kernel-trace` (tools/r06_run4.sh passes the figure in).
+  * device time: sum of kernel durations per call when run under `rocprofv3 --kernel-trace` (a first run with `--plain` under the profiler gives the figure, a second run takes it as `--device-us-per-call`).
 """
 import argparse
 import cProfile
