@@ -50,6 +50,10 @@ int pt_abi_version(void);
  * OH/OW may be the full correlation size H+2*(KH/2)-KH+1 (reference apply_filter) or anything smaller:
  * the top-left OHxOW corner is produced (pytracking/libs/operation.py:17-32 conv2d(mode='same')).
  * Requires KH*KW <= 16. */
+/* Launch geometry of the XCD-aligned correlation pass for this shape, evaluated on the host, nothing launched:
+ * out[0..9] = usable, tiles, k-step halves per tile, samples per workgroup, mixed pair layout, threads per workgroup, k-steps per wave,
+ * channel ranges, dynamic LDS bytes, leftover-quad tile.  Returns 0, or PT_ERR_NULL. */
+int pt_corr_pass_plan(int n, int C, int H, int W, int KH, int KW, int OH, int OW, int* out);
 size_t pt_apply_filter_ws_bytes(int n, int C, int H, int W, int KH, int KW, int OH, int OW);
 int pt_apply_filter_f32(const float* feat, long feat_stride_n, const float* filt, float* scores,
                         int n, int C, int H, int W, int KH, int KW, int OH, int OW,

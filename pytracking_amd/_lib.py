@@ -76,7 +76,7 @@ class TompDims(ctypes.Structure):
 
 EXPORTS = [
     "pt_strerror", "pt_abi_version",
-    "pt_apply_filter_ws_bytes", "pt_apply_filter_f32",
+    "pt_corr_pass_plan", "pt_apply_filter_ws_bytes", "pt_apply_filter_f32",
     "pt_feat_transpose_ws_bytes", "pt_feat_transpose_f32",
     "pt_sd_ws_bytes", "pt_sd_solve_f32",
     "pt_atom_cg_ws_bytes", "pt_atom_cg_f32", "pt_atom_gn_ws_bytes", "pt_atom_gn_f32",

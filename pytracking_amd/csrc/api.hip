@@ -101,6 +101,15 @@ static int filt_check(int n, int C, int H, int W, int KH, int KW, int OH, int OW
     return PT_OK;
 }
 
+extern "C" int pt_corr_pass_plan(int n, int C, int H, int W, int KH, int KW, int OH, int OW, int* out) {
+    if (!out) return PT_ERR_NULL;
+    const PtFast f = pt_fast_plan(n, C, H, W, KH, KW, OH, OW);
+    const int v[10] = {f.ok, f.ok ? f.tiles : 0, f.ok ? f.nh : 0, f.ok ? f.spw : 0, f.ok ? f.mix : 0, f.ok ? f.corr_threads : 0,
+                       f.ok ? f.NK : 0, f.ok ? f.KSC : 0, f.ok ? (int)f.corr_lds : 0, f.ok ? f.left : 0};
+    for (int k = 0; k < 10; ++k) out[k] = v[k];
+    return PT_OK;
+}
+
 extern "C" size_t pt_apply_filter_ws_bytes(int n, int C, int H, int W, int KH, int KW, int OH, int OW) {
     if (filt_check(n, C, H, W, KH, KW, OH, OW)) return 0;
     PtPlan p = pt_make_plan(n, C, H, W, KH, KW, OH, OW);

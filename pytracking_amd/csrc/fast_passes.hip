@@ -19,6 +19,7 @@
 #include "common.h"
 #include "pt_internal.h"
 #include "sd_common.h"
+#include <type_traits>
 
 #ifndef PT_ADJ_WAVES
 #define PT_ADJ_WAVES 8                     // waves per k_adj2 workgroup (16 measured no better at 18x18, worse at 22x22)
@@ -44,7 +45,8 @@
 #endif
 
 // Phase time stamps (experiments only, -DPT_STAMPS; tools/exp_stamps.py): every wave records the 100 MHz device wall clock at
-// up to 8 points into a buffer registered with pt_debug_set_stamps(); layout [workgroup][wave (16 slots)][8].
+// up to 8 points into a buffer registered with pt_debug_set_stamps(); layout [workgroup][wave (16 slots)][16]: 0..7 the stamps, 8 the
+// wave's hardware id register (HW_ID: SIMD in bits 5:4, CU 11:8, SH 12, SE 15:13), written with stamp 0; the rest unused.
 #ifdef PT_STAMPS
 static unsigned long long* g_pt_stamps = nullptr;
 extern "C" void pt_debug_set_stamps(void* p) { g_pt_stamps = (unsigned long long*)p; }
@@ -52,8 +54,11 @@ extern "C" void pt_debug_set_stamps(void* p) { g_pt_stamps = (unsigned long long
 #define PT_STAMP_SET(a) (a).stamps = g_pt_stamps
 #define PT_STAMP(a, k)                                                                                       \
     do {                                                                                                     \
-        if ((a).stamps && (threadIdx.x & 63) == 0)                                                           \
-            (a).stamps[((long)blockIdx.x * 16 + (threadIdx.x >> 6)) * 8 + (k)] = (unsigned long long)wall_clock64(); \
+        if ((a).stamps && (threadIdx.x & 63) == 0) {                                                         \
+            unsigned long long* sp_ = (a).stamps + ((long)blockIdx.x * 16 + (threadIdx.x >> 6)) * 16;        \
+            sp_[(k)] = (unsigned long long)wall_clock64();                                                   \
+            if ((k) == 0) sp_[8] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) | (1ull << 32); \
+        }                                                                                                    \
     } while (0)
 #else
 #define PT_STAMP_ARG
@@ -104,8 +109,18 @@ PtFast pt_fast_plan(int n, int C, int H, int W, int KH, int KW, int OH, int OW) 
     if (p.nh == 2 && p.KSC == 8 && p.CX / 4 <= 16 && (n % 2) == 0 && 8 * n > 256) { p.nh = 1; p.spw = 2; }
     p.NK = p.CX / 4 / p.nh;
     if (p.NK > 16) return p;
+    // Mixed pairs (5 tiles: 18x18).  A workgroup's waves go to the CU's four SIMDs in turn (wave w and w + 4 share one), so the ten
+    // pair waves sit 3 / 3 / 2 / 2, and the two waves of tile 0 -- which also carry the leftover quads' MFMA -- both land on the
+    // three-wave SIMDs: 208 MFMAs there against 128 on the others, and barrier 2 waits for them (profiles/r07a_*).  Here tile 0 of
+    // each sample is split by POSITIONS over two waves: waves 0..3 = (sample, half) of tile 0 -- half 0: positions 4j, 4j + 1 and the
+    // leftover quads, half 1: positions 4j + 2, 4j + 3, all k-steps each -- and waves 4.. = (sample, tile 1..): 12 waves = one half
+    // wave + two full waves per SIMD, 176 / 160 / 176 / 160 MFMAs.  Every element still runs through ONE accumulator in the same
+    // order: same bits, same tap planes, same shift-and-add.  (Split by k-steps instead -- 168 MFMAs everywhere -- the two parts of
+    // an element have to meet: by ds_add_f32 that took 5 us per pass, profiles/r07a_*.)  Other pair geometries: 4 and 2 tiles give
+    // 8 and 4 waves, even already; 3 tiles (6 waves, 2 / 2 / 1 / 1) would need its own cut and has no tracker shape behind it.
+    p.mix = (p.spw == 2 && p.tiles == 5 && p.KK == 16 && p.NK >= 4) ? 1 : 0;
     p.HWp = 64 * (p.TF + (p.rem > 0 ? 1 : 0)) + 4;
-    p.corr_threads = p.spw * p.nh * p.tiles * 64;
+    p.corr_threads = p.mix ? (2 * p.tiles + 2) * 64 : p.spw * p.nh * p.tiles * 64;
     p.corr_lds = ((size_t)p.CX * 16 + (size_t)p.spw * p.nh * p.KK * p.HWp) * sizeof(float);
     // direct 4x4 shift-and-add (k_corr2): masked taps may read up to 2W+2 floats in front of the first tap plane (the filter operand is
     // there) and behind the last one (its padding, else slack added here)
@@ -196,7 +211,8 @@ __device__ __forceinline__ float corr2_filter_elem(const Corr2Args& a, int KK, i
 // consumer is the next frame's first correlation: here the operand is formed from h_filt = w_{T-1}, h_w = g_T, alpha_T from the n
 // per-sample curvature terms and the channel-range sums of g^2 (h_w + h_aux: anum, 64 floats further: qs) with the expressions of
 // k_fast_final (sd_final_astep / sd_final_apply: same bits), and the workgroups of sample 0 store w_T into a.g_out = the filter.
-template <int NK, bool LEFT, int FUSE, bool K16, int NH>
+// MIX (sample pairs of 5 tiles, NH == 1): waves 0..3 = (sample, position half) of tile 0, waves 4.. = (sample, tile 1..) -- see pt_fast_plan.
+template <int NK, bool LEFT, int FUSE, bool K16, int NH, bool MIX = false>
 __global__ __launch_bounds__(1024, (NK <= 8 && NH == 2 ? PT_C2_MINW : 4)) void k_corr2(const float* h_feat, long h_stride, const float* h_filt, const float* h_w, const float* h_src, int h_slot,
                                                                               unsigned h_dims, unsigned h_geo, unsigned h_aux, Corr2Args a_arg) {
     // The h_* parameters repeat what the prologue needs to REQUEST its operands (13 dwords).  Scalar kernel parameters are
@@ -217,7 +233,7 @@ __global__ __launch_bounds__(1024, (NK <= 8 && NH == 2 ? PT_C2_MINW : 4)) void k
     const int h_KSPL = (int)((h_geo >> 14) & 63u);
     const bool ksc16 = ((h_geo >> 20) & 1u) != 0, ksc1 = ((h_geo >> 21) & 1u) != 0, pair = ((h_geo >> 22) & 1u) != 0;
     const int wps = NH * h_tiles;                                   // waves per sample
-    const int nthreads = (pair ? 2 : 1) * wps * 64;
+    const int nthreads = MIX ? (2 * h_tiles + 2) * 64 : (pair ? 2 : 1) * wps * 64;
     const int hCX = ksc1 ? hC : (ksc16 ? hC >> 4 : hC >> 3), hHWp = 64 * (h_TF + (h_rem > 0 ? 1 : 0)) + 4;
     // 16 ranges: 2x and 2x + 1 both run on XCD x (the adjoint pass owns channels [x C/8, (x+1) C/8) there)
     const int b = blockIdx.x, xc = b & 7, q = b >> 3;
@@ -225,13 +241,17 @@ __global__ __launch_bounds__(1024, (NK <= 8 && NH == 2 ? PT_C2_MINW : 4)) void k
     const int KK = K16 ? 16 : a_arg.KH * a_arg.KW;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: scalar branches
     const int kq = lane >> 4, j = lane & 15;
-    const int ws = (pair && wave >= wps) ? 1 : 0, wl = wave - ws * wps;   // which sample of the pair, wave inside the sample
+    const bool half = MIX && wave < 4;                              // MIX: this wave takes two of the four positions of every lane of tile 0
+    const int ws = MIX ? (half ? wave >> 1 : (wave - 4 >= h_tiles - 1 ? 1 : 0)) : ((pair && wave >= wps) ? 1 : 0);   // which sample of the pair
+    const int wl = wave - ws * wps;                                 // wave inside the sample
     const int i = pair ? 2 * i0 + ws : i0;
-    const int h = wl >= h_tiles ? 1 : 0, t = wl - h * h_tiles;
+    const int h = MIX ? (half ? wave & 1 : 0) : (wl >= h_tiles ? 1 : 0);
+    const int t = MIX ? (half ? 0 : wave - 3 - ws * (h_tiles - 1)) : wl - h * h_tiles;
+    const bool lt = LEFT && t == 0 && (!MIX || h == 0);             // this wave also carries the leftover quads
     const int cx0 = hCX * x;
     const int nsl = hCX * 16;
     float* __restrict__ afilt = lds;
-    float* __restrict__ Tl = lds + nsl + (long)(ws * NH + h) * KK * hHWp;
+    float* __restrict__ Tl = lds + nsl + (long)(ws * NH + (MIX ? 0 : h)) * KK * hHWp;
     const bool over = h_src != nullptr && i == h_slot;
     const float* __restrict__ fi = over ? h_src : h_feat + (long)i * h_stride;
     const bool publish = FUSE != 0 && i0 == 0;                      // uniform per workgroup
@@ -289,28 +309,36 @@ __global__ __launch_bounds__(1024, (NK <= 8 && NH == 2 ? PT_C2_MINW : 4)) void k
     //      cannot issue (the CU accepts ~45 B/clk), so only the first CD k-steps are requested before the filter is
     //      staged; the rest are issued CD k-steps ahead of the MFMAs that consume them.
     constexpr int CD = NK < PT_C2_CD ? NK : PT_C2_CD;    // 6 or 8 ahead: register spills under the 80-VGPR cap, 10.3 vs 10.15 us
-    const int cbase = cx0 + 4 * (h * NK) + kq;
-    const int pos = 64 * t + 4 * j;
+    const int cbase = cx0 + 4 * ((MIX ? 0 : h) * NK) + kq;
+    const int pos = 64 * t + 4 * j + (half ? 2 * h : 0);
     const bool pv = pos < HW;
     const __amdgpu_buffer_rsrc_t fr = pt_rsrc(fi, (unsigned)hC * HW * 4u);
     const unsigned fo = ((unsigned)cbase * HW + (pv ? pos : 0)) * 4u;
     const int lpos = 64 * h_TF + j;
-    const bool lv = LEFT && t == 0 && j < 4 * h_rem;
+    const bool lv = lt && j < 4 * h_rem;
     const unsigned lo = lv ? ((unsigned)cbase * HW + lpos) * 4u : 0xFFFFFFF0u - 64u * (unsigned)HW * 4u;   // no position: reads 0
     f32x4 bq[NK];
     float bl[NK];
+    auto ldf = [&](int k) {                                         // a half wave: its two positions in bq[k][0], bq[k][1]
+        if (MIX && half) {
+            const f32x2 v = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(fr, fo + (unsigned)(4 * k) * HW * 4u, 0, 0));
+            bq[k] = (f32x4){v[0], v[1], 0.f, 0.f};
+        } else {
+            bq[k] = pt_bload4(fr, fo + (unsigned)(4 * k) * HW * 4u);
+        }
+    };
     auto ldq = [&](int k) {
-        bq[k] = pt_bload4(fr, fo + (unsigned)(4 * k) * HW * 4u);
-        if (LEFT && t == 0) bl[k] = pt_bload1(fr, lo + (unsigned)(4 * k) * HW * 4u);
+        ldf(k);
+        if (lt) bl[k] = pt_bload1(fr, lo + (unsigned)(4 * k) * HW * 4u);
     };
     // the leftover-quad scalars first: the filter reduction below then waits for vmcnt(CD) on every wave -- the 16-byte loads stay
     // in flight behind it -- instead of a count that fits the waves without the leftover tile
-    if (LEFT && t == 0) {
+    if (lt) {
 #pragma unroll
         for (int k = 0; k < CD; ++k) bl[k] = pt_bload1(fr, lo + (unsigned)(4 * k) * HW * 4u);
     }
 #pragma unroll
-    for (int k = 0; k < CD; ++k) bq[k] = pt_bload4(fr, fo + (unsigned)(4 * k) * HW * 4u);
+    for (int k = 0; k < CD; ++k) ldf(k);
     __builtin_amdgcn_sched_barrier(0);                              // nothing that needs the argument block above this line
     const Corr2Args a = pt_late_args<Corr2Args>(56);                // 5 pointers / longs + 3 dwords = 52 bytes, 8-aligned
     PT_STAMP(a, 1);
@@ -371,46 +399,65 @@ __global__ __launch_bounds__(1024, (NK <= 8 && NH == 2 ? PT_C2_MINW : 4)) void k
     __syncthreads();
     PT_STAMP(a, 3);
 
-    f32x4 acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0}, acc2 = {0, 0, 0, 0}, acc3 = {0, 0, 0, 0}, accL = {0, 0, 0, 0};
-    // the wave's NK filter-operand values in one batch of LDS reads in front of the loop (round 6: inside the loop every k-step was
-    // read -> wait -> 4 MFMAs, the uniform leftover-tile branches keep the compiler from hoisting the next read over them)
-    float avv[NK];
+    // HALF (MIX, tile 0): two positions per lane (bq[k][0], bq[k][1]) instead of four
+    auto mfma_phase = [&](auto half_c) {
+        constexpr bool HALF = decltype(half_c)::value;
+        f32x4 acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0}, acc2 = {0, 0, 0, 0}, acc3 = {0, 0, 0, 0}, accL = {0, 0, 0, 0};
+        // the wave's NK filter-operand values in one batch of LDS reads in front of the loop (round 6: inside the loop every k-step was
+        // read -> wait -> 4 MFMAs, the uniform leftover-tile branches keep the compiler from hoisting the next read over them)
+        float avv[NK];
 #pragma unroll
-    for (int k = 0; k < NK; ++k) avv[k] = afilt[(4 * (h * NK + k) + kq) * 16 + j];
-    __builtin_amdgcn_sched_barrier(0);
+        for (int k = 0; k < NK; ++k) avv[k] = afilt[(4 * ((MIX ? 0 : h) * NK + k) + kq) * 16 + j];
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int k = 0; k < NK; ++k) {
-        if (k + CD < NK) ldq(k + CD);
-        const float av = avv[k];
-        acc0 = mfma16(av, bq[k][0], acc0);
-        acc1 = mfma16(av, bq[k][1], acc1);
-        acc2 = mfma16(av, bq[k][2], acc2);
-        acc3 = mfma16(av, bq[k][3], acc3);
-        if (LEFT && t == 0) accL = mfma16(av, bl[k], accL);
-    }
-    PT_STAMP(a, 4);
-    // ---- memory insert rides on the pass (pytracking/tracker/dimp/dimp.py:429-441)
-    if (over && a.copy_dst) {
-        const pt_gf dp = a.copy_dst + pos + (long)cbase * HW;
-        if (pv) {
-#pragma unroll
-            for (int k = 0; k < NK; ++k) *(f32x4*)(dp + (long)(4 * k) * HW) = bq[k];
+        for (int k = 0; k < NK; ++k) {
+            if (k + CD < NK) ldq(k + CD);
+            const float av = avv[k];
+            acc0 = mfma16(av, bq[k][0], acc0);
+            acc1 = mfma16(av, bq[k][1], acc1);
+            if constexpr (!HALF) {
+                acc2 = mfma16(av, bq[k][2], acc2);
+                acc3 = mfma16(av, bq[k][3], acc3);
+            }
+            if (lt) accL = mfma16(av, bl[k], accL);
         }
-        if (lv) {
-            const pt_gf dl = a.copy_dst + lpos + (long)cbase * HW;
+        PT_STAMP(a, 4);
+        // ---- memory insert rides on the pass (pytracking/tracker/dimp/dimp.py:429-441)
+        if (over && a.copy_dst) {
+            const pt_gf dp = a.copy_dst + pos + (long)cbase * HW;
+            if (pv) {
 #pragma unroll
-            for (int k = 0; k < NK; ++k) dl[(long)(4 * k) * HW] = bl[k];
+                for (int k = 0; k < NK; ++k) {
+                    if constexpr (HALF) *(f32x2*)(dp + (long)(4 * k) * HW) = (f32x2){bq[k][0], bq[k][1]};
+                    else *(f32x4*)(dp + (long)(4 * k) * HW) = bq[k];
+                }
+            }
+            if (lv) {
+                const pt_gf dl = a.copy_dst + lpos + (long)cbase * HW;
+#pragma unroll
+                for (int k = 0; k < NK; ++k) dl[(long)(4 * k) * HW] = bl[k];
+            }
         }
-    }
 
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int row = 4 * kq + r;
-        if (row < KK) {
-            f32x4 v = {acc0[r], acc1[r], acc2[r], acc3[r]};
-            *(f32x4*)(Tl + row * hHWp + pos) = v;                 // columns >= HW land in the padding
-            if (LEFT && t == 0) Tl[row * hHWp + lpos] = accL[r];  // j >= 4*rem: padding as well (lpos < HWp)
+        for (int r = 0; r < 4; ++r) {
+            const int row = 4 * kq + r;
+            if (row < KK) {
+                if constexpr (HALF) {
+                    *(f32x2*)(Tl + row * hHWp + pos) = (f32x2){acc0[r], acc1[r]};
+                } else {
+                    f32x4 v = {acc0[r], acc1[r], acc2[r], acc3[r]};
+                    *(f32x4*)(Tl + row * hHWp + pos) = v;             // columns >= HW land in the padding
+                }
+                if (lt) Tl[row * hHWp + lpos] = accL[r];              // j >= 4*rem: padding as well (lpos < HWp)
+            }
         }
+    };
+    if constexpr (MIX) {
+        if (half) mfma_phase(std::true_type{});                     // uniform per wave
+        else mfma_phase(std::false_type{});
+    } else {
+        mfma_phase(std::false_type{});
     }
     PT_STAMP(a, 5);
     __syncthreads();
@@ -552,17 +599,17 @@ int pt_launch_corr2(const PtFast& p, const float* feat, long stride_n, const flo
     const unsigned h_geo = (unsigned)p.tiles | ((unsigned)p.TF << 5) | ((unsigned)p.rem << 10) | ((unsigned)a.KSPL << 14) |
                            ((p.KSC == 16 ? 1u : 0u) << 20) | ((p.KSC == 1 ? 1u : 0u) << 21) | ((p.spw == 2 ? 1u : 0u) << 22) | h_nbits;
 #define PT_C2_HOT(FPTR) (const float*)a.feat, a.stride_n, (const float*)(FPTR), (const float*)a.w, (const float*)a.src, a.slot, h_dims, h_geo, h_aux
-#define PT_C2G(NKV, LF, KF, NHV)                                                                                    \
+#define PT_C2G(NKV, LF, KF, NHV, MX)                                                                                  \
     do {                                                                                                         \
-        if (lazy) { if constexpr (KF) hipLaunchKernelGGL((k_corr2<NKV, LF, -1, true, NHV>), grid, block, p.corr_lds, st, PT_C2_HOT(a.filt), a); } \
-        else if (!a.gpart) hipLaunchKernelGGL((k_corr2<NKV, LF, 0, KF, NHV>), grid, block, p.corr_lds, st, PT_C2_HOT(a.filt), a);             \
-        else if (a.KSPL <= 8) hipLaunchKernelGGL((k_corr2<NKV, LF, 8, KF, NHV>), grid, block, p.corr_lds, st, PT_C2_HOT(a.gpart), a);     \
-        else hipLaunchKernelGGL((k_corr2<NKV, LF, 16, KF, NHV>), grid, block, p.corr_lds, st, PT_C2_HOT(a.gpart), a);                     \
+        if (lazy) { if constexpr (KF) hipLaunchKernelGGL((k_corr2<NKV, LF, -1, true, NHV, MX>), grid, block, p.corr_lds, st, PT_C2_HOT(a.filt), a); } \
+        else if (!a.gpart) hipLaunchKernelGGL((k_corr2<NKV, LF, 0, KF, NHV, MX>), grid, block, p.corr_lds, st, PT_C2_HOT(a.filt), a);             \
+        else if (a.KSPL <= 8) hipLaunchKernelGGL((k_corr2<NKV, LF, 8, KF, NHV, MX>), grid, block, p.corr_lds, st, PT_C2_HOT(a.gpart), a);     \
+        else hipLaunchKernelGGL((k_corr2<NKV, LF, 16, KF, NHV, MX>), grid, block, p.corr_lds, st, PT_C2_HOT(a.gpart), a);                     \
     } while (0)
 #define PT_C2H(NKV, LF, KF)              \
     do {                                 \
-        if (p.nh == 2) PT_C2G(NKV, LF, KF, 2); \
-        else PT_C2G(NKV, LF, KF, 1);     \
+        if (p.nh == 2) PT_C2G(NKV, LF, KF, 2, false); \
+        else PT_C2G(NKV, LF, KF, 1, false);     \
     } while (0)
 #define PT_C2F(NKV, LF)                  \
     do {                                 \
@@ -574,7 +621,17 @@ int pt_launch_corr2(const PtFast& p, const float* feat, long stride_n, const flo
         if (p.left) PT_C2F(NKV, true); \
         else PT_C2F(NKV, false);    \
     } while (0)
-    if (p.NK == 2) PT_C2(2);
+#define PT_C2M(NKV)                                  \
+    do {                                             \
+        if (p.left) PT_C2G(NKV, true, true, 1, true);   \
+        else PT_C2G(NKV, false, true, 1, true);      \
+    } while (0)
+    if (p.mix) {                                                    // sample pairs of 5 tiles (the plan: 16 taps, one k-step set per wave)
+        if (p.NK == 4) PT_C2M(4);
+        else if (p.NK == 8) PT_C2M(8);
+        else PT_C2M(16);
+    }
+    else if (p.NK == 2) PT_C2(2);
     else if (p.NK == 4) PT_C2(4);
     else if (p.NK == 8) PT_C2(8);
     else PT_C2(16);
@@ -582,6 +639,7 @@ int pt_launch_corr2(const PtFast& p, const float* feat, long stride_n, const flo
 #undef PT_C2G
 #undef PT_C2H
 #undef PT_C2F
+#undef PT_C2M
 #undef PT_C2
     PT_CHECK_LAUNCH();
     return PT_OK;
