@@ -262,7 +262,7 @@ static int track_frame_impl(const pt_sd_params* prm, float* filter, float* mem_f
     const long CHW = (long)C * H * W;
     float* base = (float*)ws;
     PtFast f = pt_fast_plan(n, C, H, W, K, K, OH, OW);
-    if (pt_fast_usable(f, mem_feat, CHW, filter, test_feat) && f.KSPL <= 16) {      // (the SD solver sums <= 16 gradient partials)
+    if (pt_sd_route_fast(f, mem_feat, CHW, filter, base + cv.w_iters, test_feat, pt_sd_lut_bins(prm), false)) {   // (the solve's own verdict)
         // Fast path: the first correlation of the solve reads sample `slot` from test_feat (and stores it into the
         // memory slot, dimp.py:429-441); its score row under the current filter IS the classification of the test
         // frame (dimp.py:190-194 -> linear_filter.py:75-80).  Localisation runs in the init stage.
@@ -333,7 +333,9 @@ int pt_track_frame_head_impl(const pt_sd_params* prm, float* filter, float* mem_
     hipStream_t st = (hipStream_t)stream;
     const int OH = H + (K + 1) % 2, OW = W + (K + 1) % 2;
     PtFast f = pt_fast_plan(n, C, H, W, K, K, OH, OW);
-    const bool fast = pt_fast_usable(f, mem_feat, CHW, filter) && f.KSPL <= 16;
+    TfCarve cv = tf_carve(n, C, H, W, K);
+    float* fb = base + hc.frame;
+    const bool fast = pt_sd_route_fast(f, mem_feat, CHW, filter, fb + cv.w_iters, nullptr, pt_sd_lut_bins(prm), false);   // (the solve's own verdict)
     // slot_dyn (graph-replayed frame): the slot index lives in device memory -- the head's last kernel and the solve's init stage read
     // it there; only the XCD-aligned path serves that (checked before anything is queued)
     if (slot_dyn && !fast) return PT_ERR_UNSUPPORTED;
@@ -342,8 +344,6 @@ int pt_track_frame_head_impl(const pt_sd_params* prm, float* filter, float* mem_
                               norm_eps, base + hc.head, hc.frame * sizeof(float), stream, slot_dyn, CHW);
     if (rc) return rc;
     // 2. classification of that sample = its score row of the solve's first correlation; localisation; re-optimisation
-    TfCarve cv = tf_carve(n, C, H, W, K);
-    float* fb = base + hc.frame;
     PtClsFin cls = {nullptr, 0, slot, scores_out, peak_out, mem_bb, after_init_event, slot_dyn};
     if (fast)
         return pt_sd_solve_impl(prm, filter, mem_feat, CHW, mem_bb, sample_weight, n, C, H, W, K, num_iter, fb + cv.w_iters,

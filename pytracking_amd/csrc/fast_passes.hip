@@ -680,7 +680,7 @@ static_assert(sizeof(Adj2Late) == 46 * 4, "Adj2Late layout");
 enum { V_PLAIN = 0, V_DIMP_RELU = 1, V_DIMP_BENT = 2, V_L2 = 3, V_PRDIMP = 4 };
 
 // per-lane inputs of the update stage for one sample: E strided elements per lane.
-//   pk : packed by k_fast_init / k_fast_sgq, ONE 16-byte load per element:
+//   pk : packed by k_fast_init2 / k_fast_sgq2 (or the hinge init stage), ONE 16-byte load per element:
 //          DiMP relu / L2 : {sws^2 * s, sws^2 * (F g), sws^2 * label, mask}
 //          DiMP bentpar   : {s, F g, label, mask}  (+ sw)          PrDiMP : {s, F g, label, -}
 //   s, sg : raw scores / F g, only loaded by the wave that owns the sample (it stores s_t; the loss needs more raw maps,
@@ -1247,8 +1247,7 @@ static int adj2_dispatch(const PtFast& p, const Adj2Args& a, hipStream_t st, boo
         }
     } else if (fuse_init) return PT_ERR_UNSUPPORTED;
 #define PT_A2_HOT a.feat, a.stride_n, pkp, qsp, anp, g1, g2, g3, g4, l, Adj2InitLate{}
-    if (p.E == 6 && p.U <= 12 && PT_ADJ_WAVES != 8) hipLaunchKernelGGL((k_adj2<V, 6, 12>), grid, block, p.adj_lds, st, PT_A2_HOT);   // experiment builds only
-    else if (p.E == 6) hipLaunchKernelGGL((k_adj2<V, 6, 16>), grid, block, p.adj_lds, st, PT_A2_HOT);
+    if (p.E == 6) hipLaunchKernelGGL((k_adj2<V, 6, 16>), grid, block, p.adj_lds, st, PT_A2_HOT);
     else if (p.E == 9 && p.U <= 12) hipLaunchKernelGGL((k_adj2<V, 9, 12>), grid, block, p.adj_lds, st, PT_A2_HOT);
     else if (p.E == 9 && p.U <= 16) hipLaunchKernelGGL((k_adj2<V, 9, 16>), grid, block, p.adj_lds, st, PT_A2_HOT);
     else if (p.E == 9) hipLaunchKernelGGL((k_adj2<V, 9, PT_ADJ_UMAX_WIDE>), grid, block, p.adj_lds, st, PT_A2_HOT);

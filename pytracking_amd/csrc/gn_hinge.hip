@@ -140,5 +140,5 @@ extern "C" int pt_gn_hinge_route(const float* feat, long feat_stride_n, const fl
     if (n <= 0 || C <= 0 || H <= 0 || W <= 0 || K <= 0) return PT_ERR_SHAPE;
     const int OH = H + (K + 1) % 2, OW = W + (K + 1) % 2;
     const PtFast f = pt_fast_plan(n, C, H, W, K, K, OH, OW);
-    return pt_sd_route_fast(f, feat, feat_stride_n, w_in, w_iters, nullptr, true) ? 1 : 0;
+    return pt_sd_route_fast(f, feat, feat_stride_n, w_in, w_iters, nullptr, 0, true) ? 1 : 0;
 }

@@ -67,28 +67,36 @@ struct PtFast {
     int spw;                                                    // samples per k_corr2 workgroup (2: sample pairs, see pt_fast_plan)
     int mix;                                                    // pair workgroup of 2 tiles + 2 waves: tile 0 of each sample split by positions over two waves
     int sa_direct;                                              // k_corr2's 4x4 shift-and-add may use uniform tap steps (LDS slack guaranteed)
-    int KSC;                                                    // channel ranges = partial score maps per sample: 8 (one per XCD) or 16
+    int KSC;                                                    // channel ranges = partial score maps per sample: 1 or 8 (one per XCD; k_corr2's 16-range bit is never set: DESIGN.md section 10 T)
     size_t corr_lds;
     int CB, bpx, NG, KSPL, gper, U, PH, PW, ns_max, E, zn; // adj2: grid CB*KSPL, 8 waves x U contiguous groups; zero block
     size_t adj_lds;
 };
 PtFast pt_fast_plan(int n, int C, int H, int W, int KH, int KW, int OH, int OW);
 // The ONE predicate for "this call can take the XCD-aligned path": the shape plan plus what the raw 16-byte buffer loads
-// need from the pointers (shared by pt_apply_filter_f32, pt_feat_transpose_f32, pt_sd_solve_impl, pt_track_frame_f32;
-// when it is false every caller takes its generic branch).  `filt` / `src` may be null.
+// need from the pointers (pt_apply_filter_f32, pt_feat_transpose_f32, the ATOM CG update; the steepest-descent solve and the frame
+// entries ask pt_sd_route_fast below, which includes it; when it is false every caller takes its generic branch).  `filt` / `src` may be null.
 static inline bool pt_fast_usable(const PtFast& f, const void* feat, long stride_n, const void* filt = nullptr,
                                   const void* src = nullptr) {
     return f.ok && ((uintptr_t)feat % 16) == 0 && (stride_n % 4) == 0 && (long)f.n * stride_n * 4 < (1L << 31) &&
            ((uintptr_t)src % 16) == 0 && (f.KK != 16 || ((uintptr_t)filt % 16) == 0);
 }
 // The route of the steepest-descent solve (pt_sd_solve_impl; pt_gn_hinge_route reports it): the XCD-aligned fast path also needs a
-// 16-byte aligned iterate buffer and <= 16 adjoint slices; with a caller-supplied label map (gn_hinge.hip) its init stage runs one
-// element per thread, so maps of more than 1024 elements take the generic route.
+// 16-byte aligned iterate buffer and <= 16 adjoint slices (the fused gradient reduction sums at most 16 partials), and its init
+// stage keeps the three DiMP look-up tables (`lut_bins` entries each; 0: the kind has none) in LDS.  With a caller-supplied label
+// map (gn_hinge.hip) there are no tables, and the init stage runs one element per thread: maps of more than 1024 elements take the
+// generic route.  The frame entries (api.hip) and the replay helper ask HERE too: what they prepare must match what the solve does.
+// (A table count < 1 decides nothing here: pt_sd_solve_impl refuses it with PT_ERR_NULL in front of this predicate, and a frame entry
+// that reaches the solve through the fast branch has queued nothing by then -- as before.)
+#define PT_SD_LUT_LDS_MAX (48 * 1024)
+static inline int pt_sd_lut_bins(const pt_sd_params* prm) { return prm->kind == PT_SD_DIMP ? prm->num_bins : 0; }
 static inline bool pt_sd_route_fast(const PtFast& f, const void* feat, long stride_n, const void* w_in, const void* w_iters,
-                                    const void* src, bool label_map) {
-    return pt_fast_usable(f, feat, stride_n, w_in, src) && ((uintptr_t)w_iters % 16) == 0 && f.KSPL <= 16 && (!label_map || f.OO <= 1024);
+                                    const void* src, int lut_bins, bool label_map) {
+    return pt_fast_usable(f, feat, stride_n, w_in, src) && ((uintptr_t)w_iters % 16) == 0 && f.KSPL <= 16 &&
+           (label_map ? f.OO <= 1024 : (long)3 * lut_bins * (long)sizeof(float) <= PT_SD_LUT_LDS_MAX);
 }
-static inline size_t pt_fast_spart_floats(const PtFast& p) { return (size_t)16 * p.n * p.OO; }   // room for KSC = 16
+// 16 slices although the plan makes 1 or 8 channel ranges: the size is part of every *_ws_bytes result and of the carve behind it
+static inline size_t pt_fast_spart_floats(const PtFast& p) { return (size_t)16 * p.n * p.OO; }
 static inline size_t pt_fast_gpart_floats(const PtFast& p) { return (size_t)p.KSPL * p.C * p.KK; }
 // spart[x][i][OH*OW], x = XCD channel range (8 slices).  `slot`/`src`/`copy_dst`: sample `slot` is read from `src`
 // and stored to `copy_dst` while it streams (src == nullptr: no override).

@@ -230,94 +230,14 @@ static FastCarve fast_carve(const PtFast& f, int max_iter) {
     return c;
 }
 
-// packed operands of the update stage that k_adj2 runs as its prologue (PReg in fast_passes.hip)
-__device__ __forceinline__ void fast_pack(const SdArgs& a, long q, float s, float sg) {
-    f32x4 v;
-    if (a.kind == PT_SD_PRDIMP) {
-        v = (f32x4){s, sg, a.label[q], 0.f};
-    } else {
-        const float sw = a.sws[q], m = a.mask[q], L = a.label[q];
-        if (a.kind == PT_SD_DIMP && a.score_act == PT_ACT_BENTPAR) v = (f32x4){s, sg, L, m};
-        else { const float w2 = sw * sw; v = (f32x4){w2 * s, w2 * sg, w2 * L, m}; }
-    }
-    ((f32x4*)a.pk)[q] = v;
-}
-
-// s_0 = sum of the 8 channel-range slices; classification epilogue of the inserted slot; label/mask/weight maps
-__global__ __launch_bounds__(512) void k_fast_init(SdArgs a) {
-    __shared__ float scratch[16];
-    __shared__ int amin[2];
-    const int i = blockIdx.x;
-    const long base = (long)i * a.OO;
-    for (int o = threadIdx.x; o < a.OO; o += blockDim.x) a.s[base + o] = sd_sum_slices(a, i, o);
-    if (a.cls_spart && i == a.cls_slot) sd_classify_fin(a);     // uniform per workgroup; re-centres bb[slot]
-    sd_maps_sample(a, i, scratch, amin);
-    __syncthreads();                                            // PrDiMP: label is finalised by other threads
-    for (int o = threadIdx.x; o < a.OO; o += blockDim.x) fast_pack(a, base + o, a.s[base + o], 0.f);
-}
-
-// F g = sum of the 8 slices; per-sample curvature term (optimizer.py:151-156 / :416-422); packed operands for k_adj2
-__global__ __launch_bounds__(512) void k_fast_sgq(SdArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    __shared__ float scratch[16];
-    const int i = blockIdx.x;
-    const long base = (long)i * a.OO;
-    float acc = 0.f;
-    if (a.kind != PT_SD_PRDIMP) {
-        const int sact = a.kind == PT_SD_DIMP_L2 ? 2 : a.score_act;
-        for (int o = threadIdx.x; o < a.OO; o += blockDim.x) {
-            const float sgv = sd_sum_slices(a, i, o), sv = a.s[base + o];
-            a.sg[base + o] = sgv;
-            float act, der;
-            act_pair(sact, a.act_param, sv, a.mask[base + o], act, der);
-            const float q = a.sws[base + o] * (der * sgv);
-            acc += q * q;
-            fast_pack(a, base + o, sv, sgv);
-        }
-        const float tot = block_sum(acc, scratch);
-        if (threadIdx.x == 0) a.qs[i] = tot;
-    } else {
-        const float swp = a.has_sw ? a.sw[i] : 1.0f / (float)a.n;
-        float psum = 0.f;
-        for (int o = threadIdx.x; o < a.OO; o += blockDim.x) {
-            const float sgv = sd_sum_slices(a, i, o);
-            a.sg[base + o] = sgv;
-            lds[o] = sgv;
-            psum += a.mask[base + o] * sgv;                                         // :419
-            fast_pack(a, base + o, a.s[base + o], sgv);
-        }
-        const float tot = block_sum(psum, scratch);
-        for (int o = threadIdx.x; o < a.OO; o += blockDim.x) {
-            const float P = a.mask[base + o], sgv = lds[o];
-            acc += sgv * (P * sgv - P * tot);                                       // :420
-        }
-        const float ghg = block_sum(acc, scratch);
-        if (threadIdx.x == 0) a.qs[i] = swp * fmaxf(ghg, 0.f);                      // :421-422
-    }
-}
-
 // ----------------------------------------------------------------------------------------------------
-// Pointwise stages of the fast path, one memory round trip each (round 3).  The first versions above (kept for
-// look-up tables too large for LDS and as the reference of the parity tests' history) read their operands where the reference's statements use them: the
-// compiler must keep a load behind every earlier store that may alias it, so k_fast_sgq was three dependent round trips
-// (slices -> s, mask -> label, sws) and k_fast_init five.  Here every operand of an element is requested before the first
-// wait, values stay in registers between the steps, and all stores come last; one element per thread (blockDim >= OO).
+// Pointwise stages of the fast path, one memory round trip each: one workgroup per sample, one element per thread (blockDim >= OO).
+// Every operand of an element is requested before the first wait, values stay in registers between the steps, and all stores come
+// last (written where the reference's statements use their operands, the compiler must keep a load behind every earlier store that
+// may alias it: three to five dependent round trips).  Both stages leave the packed operands of the update stage that k_adj2 runs as
+// its prologue (PReg in fast_passes.hip).  The slice registers hold up to PT_PW_MAXKS channel ranges; the plan makes 1 or 8.
 // ----------------------------------------------------------------------------------------------------
 #define PT_PW_MAXKS 16
-// sum of the KS (<= 16) channel-range partials of element (i, o): all loads in flight together, fixed summation order
-__device__ __forceinline__ void pw_load_slices(const SdArgs& a, int i, int oc, float (&v)[PT_PW_MAXKS]) {
-    const float* p = a.spart + (long)i * a.OO + oc;
-    const long st = (long)a.n * a.OO;
-#pragma unroll
-    for (int k = 0; k < PT_PW_MAXKS; ++k) v[k] = p[(long)min(k, a.KS - 1) * st];
-}
-__device__ __forceinline__ float pw_sum_slices(const SdArgs& a, const float (&v)[PT_PW_MAXKS]) {
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < PT_PW_MAXKS; ++k) s += k < a.KS ? v[k] : 0.f;
-    return s;
-}
-
 // F g = sum of the slices; per-sample curvature term (optimizer.py:151-156 / :416-422); packed operands for k_adj2.
 // The pointers of the LOADS and the sizes are scalar kernel parameters (preloaded into SGPRs at wave launch, see
 // fast_passes.hip: pt_late_issue); what the stores need comes in the late block.
@@ -621,6 +541,7 @@ static int sd_solve_fast(const PtFast& f, const pt_sd_params* prm, const float* 
     float* sbuf[2];
     int rc = sd_fast_setup(f, prm, w_in, bb, sample_weight, w_iters, w_final, ws, ws_bytes, a, sbuf);
     if (rc) return rc;
+    if (a.KS > PT_PW_MAXKS) return PT_ERR_UNSUPPORTED;              // (no plan makes more channel ranges than the pointwise stages hold)
     const bool have_pending = pend && pend->iters > 0;
     PtCorrLazy lz{};
     if (have_pending || defer) {
@@ -635,8 +556,6 @@ static int sd_solve_fast(const PtFast& f, const pt_sd_params* prm, const float* 
         a.cls_spart = a.spart + (long)slot * a.OO; a.cls_KS = a.KS; a.cls_stride = (long)n * a.OO; a.cls_slot = slot;
         a.cls_scores = cls->scores; a.cls_peak = cls->peak; a.cls_bb = cls->mem_bb;
         a.cls_slot_dyn = cls->slot_dyn;
-        // a device-resident slot is served by k_fast_init2 only: refuse before anything is queued
-        if (cls->slot_dyn && !(a.KS <= PT_PW_MAXKS && (a.kind != PT_SD_DIMP || (size_t)3 * a.num_bins * sizeof(float) <= 48 * 1024))) return PT_ERR_UNSUPPORTED;
     }
     const int want_loss = losses != nullptr;
     const size_t pw_lds = (size_t)a.OO * sizeof(float) * (a.kind == PT_SD_PRDIMP ? 2 : 1);
@@ -660,21 +579,20 @@ static int sd_solve_fast(const PtFast& f, const pt_sd_params* prm, const float* 
     if (rc) return rc;
     if (have_pending) pend->iters = 0;
     const int pw_threads = ((a.OO + 63) / 64) * 64;                 // one element per thread (OO <= 1024 on this path)
-    const size_t lut_lds = a.kind == PT_SD_DIMP ? (size_t)3 * a.num_bins * sizeof(float) : 0;
-    const bool pw2 = a.KS <= PT_PW_MAXKS && lut_lds <= 48 * 1024;
+    const size_t lut_lds = a.kind == PT_SD_DIMP ? (size_t)3 * a.num_bins * sizeof(float) : 0;   // <= PT_SD_LUT_LDS_MAX: pt_sd_route_fast
     // Round 6 (experiment O, LOST -- profiles/r06o_fused_init_stage.txt): with at least one iteration to run, no loss read-out and nobody
     // waiting on an event behind the init stage, the first adjoint pass can do the init stage itself (k_adj2<.., INIT>): one dependent
     // launch less, bit-identical -- but every one of the 32 channel-block workgroups of a position slice then redoes the maps of its
     // 6-7 samples (8 slice loads + the look-up-table arithmetic per element, six elements per lane): that pass is 15.3 us instead of
     // 7.9 and the frame 4.7 us SLOWER.  Opt-in for experiments: PT_SD_FUSE_INIT=1 in the environment (read per solve).
     const bool fuse_env = std::getenv("PT_SD_FUSE_INIT") && std::getenv("PT_SD_FUSE_INIT")[0] == '1';
-    const bool fuse_init = !lmap && PT_SD_FUSE_INIT && fuse_env && pw2 && num_iter > 0 && !want_loss && !(cls && cls->after_init) &&
+    const bool fuse_init = !lmap && PT_SD_FUSE_INIT && fuse_env && num_iter > 0 && !want_loss && !(cls && cls->after_init) &&
                            pt_adj2_init_fusable(f, a);
     if (fuse_init) {
         if (n > 65535 || a.OO > 65535) return PT_ERR_UNSUPPORTED;
     } else if (lmap) {
         if ((rc = pt_launch_gn_hinge_init2(a, *lmap, st))) return rc;
-    } else if (pw2) {
+    } else {
         if (n > 65535 || a.OO > 65535 || a.OW > 4095 || a.K > 15 || a.num_bins > 65535 || n >= 0xfffff) return PT_ERR_UNSUPPORTED;
         InitLate il;
         il.label_lut = (pt_gcf)a.label_lut; il.mask_lut = (pt_gcf)a.mask_lut; il.spatial_lut = (pt_gcf)a.spatial_lut;
@@ -691,8 +609,6 @@ static int sd_solve_fast(const PtFast& f, const pt_sd_params* prm, const float* 
                            (unsigned)n | ((unsigned)a.OO << 16), (unsigned)a.KS | ((unsigned)a.kind << 8) | (cslot << 12),
                            (unsigned)a.OW | ((unsigned)a.K << 12) | ((unsigned)(a.kind == PT_SD_DIMP ? a.num_bins : 0) << 16), a.feat_stride, il);
     }
-    else if (a.cls_slot_dyn) return PT_ERR_UNSUPPORTED;             // (refused before the first correlation: see below)
-    else hipLaunchKernelGGL(k_fast_init, dim3(n), dim3(384), 0, st, a);
     if (!fuse_init) PT_CHECK_LAUNCH();
     if (cls && cls->after_init && hipEventRecord((hipEvent_t)cls->after_init, st) != hipSuccess) return PT_ERR_LAUNCH;
     if (num_iter == 0) {
@@ -709,16 +625,13 @@ static int sd_solve_fast(const PtFast& f, const pt_sd_params* prm, const float* 
         PtCorrFuse fz = {a.gpart, f.KSPL, t == 0 ? w_in : w_iters + (long)t * a.CKK, a.reg, a.g, a.anum, nullptr};
         rc = pt_launch_corr2(f, feat, stride_n, nullptr, a.spart, st, &fz);    // g_t, |g_t|^2, F g_t
         if (rc) return rc;
-        if (pw2) {
-            const bool pr = a.kind == PT_SD_PRDIMP;
-            const SgqLate sl = {(pt_gf)a.sg, (pt_gf)a.pk, (pt_gf)a.qs, (pt_gcf)a.sw};
-            hipLaunchKernelGGL(k_fast_sgq2, dim3(n), dim3(pw_threads), 0, st, (const float*)a.spart, (const float*)a.s,
-                               (const float*)(pr ? a.mask : a.lms), (const float*)(pr ? a.label : nullptr),
-                               (unsigned)n | ((unsigned)a.OO << 16),
-                               (unsigned)a.KS | ((unsigned)a.kind << 8) | ((unsigned)a.score_act << 12) | ((unsigned)(a.has_sw ? 1 : 0) << 16),
-                               a.act_param, sl);
-        }
-        else hipLaunchKernelGGL(k_fast_sgq, dim3(n), dim3(384), pw_lds, st, a);
+        const bool pr = a.kind == PT_SD_PRDIMP;
+        const SgqLate sl = {(pt_gf)a.sg, (pt_gf)a.pk, (pt_gf)a.qs, (pt_gcf)a.sw};
+        hipLaunchKernelGGL(k_fast_sgq2, dim3(n), dim3(pw_threads), 0, st, (const float*)a.spart, (const float*)a.s,
+                           (const float*)(pr ? a.mask : a.lms), (const float*)(pr ? a.label : nullptr),
+                           (unsigned)n | ((unsigned)a.OO << 16),
+                           (unsigned)a.KS | ((unsigned)a.kind << 8) | ((unsigned)a.score_act << 12) | ((unsigned)(a.has_sw ? 1 : 0) << 16),
+                           a.act_param, sl);
         PT_CHECK_LAUNCH();
     }
     if (num_iter > 1 && defer) {
@@ -758,7 +671,7 @@ int pt_sd_solve_impl(const pt_sd_params* prm, const float* w_in, const float* fe
     const int OH = H + (K + 1) % 2, OW = W + (K + 1) % 2;               // optimizer.py:105
     {
         PtFast f = pt_fast_plan(n, C, H, W, K, K, OH, OW);
-        if (pt_sd_route_fast(f, feat, feat_stride_n, w_in, w_iters, src, lmap != nullptr))
+        if (pt_sd_route_fast(f, feat, feat_stride_n, w_in, w_iters, src, pt_sd_lut_bins(prm), lmap != nullptr))
             return sd_solve_fast(f, prm, w_in, feat, feat_stride_n, bb, sample_weight, num_iter, w_iters, losses, ws,
                                  ws_bytes, st, copy_w0, w_final, cls, src, pend, defer, lmap);
     }
@@ -913,7 +826,7 @@ int pt_sd_replay_impl(const pt_sd_params* prm, const float* w_in, const float* f
     if (num_iter < 2 || reps < 1 || which < 0 || which > 1) return PT_ERR_SHAPE;
     const int OH = H + (K + 1) % 2, OW = W + (K + 1) % 2;
     PtFast f = pt_fast_plan(n, C, H, W, K, K, OH, OW);
-    if (!pt_fast_usable(f, feat, feat_stride_n, w_in) || f.KSPL > 16) return PT_ERR_UNSUPPORTED;
+    if (!pt_sd_route_fast(f, feat, feat_stride_n, w_in, w_iters, nullptr, pt_sd_lut_bins(prm), false)) return PT_ERR_UNSUPPORTED;
     SdArgs a;
     float* sbuf[2];
     int rc = sd_fast_setup(f, prm, w_in, bb, sample_weight, w_iters, nullptr, ws, ws_bytes, a, sbuf);

@@ -54,6 +54,6 @@ def test_design_kernel_inventory_points_at_the_kernels():
 def test_every_kernel_is_in_the_inventory():
     text = open(os.path.join(ROOT, "DESIGN.md")).read()
     sec = text[text.index("## 4. Kernel inventory"):text.index("## 5. Launch graphs")]
-    missing = [k for k in _kernel_lines() if k not in sec and k not in ("k_stream_probe", "k_transpose", "k_fast_init", "k_fast_sgq", "k_sd_loss",
-                                                                          "k_frame_mid_dyn", "k_gemv", "k_iou_setup", "k_iou_head", "k_iou_update")]
+    missing = [k for k in _kernel_lines() if k not in sec and k not in ("k_stream_probe", "k_transpose", "k_sd_loss", "k_frame_mid_dyn",
+                                                                          "k_gemv", "k_iou_setup", "k_iou_head", "k_iou_update")]
     assert not missing, missing

@@ -179,6 +179,39 @@ def test_dimp_sd_wide_adjoint_plan_22x22():
     close(adj[0], O.apply_feat_transpose(f64(feat), f64(r), 4), atol=1e-4)
 
 
+def test_dimp_more_bins_than_the_init_stage_stages_vs_oracle():
+    """Look-up tables of more than 4096 bins (3 x 4100 x 4 bytes > 48 KB) do not fit the LDS of the fast route's init stage: the
+    solve AND the frame take the generic route end to end (pt_sd_route_fast) -- on a shape (C = 128, 18x18) that otherwise runs
+    the fast route.  Against the float64 oracle at the neighbouring tests' tolerances; the 4100-bin tables are finer than the
+    100-bin ones of every other test (iterates differ by 7e-4 between the two), so a solve that ignored them would not pass."""
+    from pytracking_amd import bench_frame
+    from oracle import frame_port
+    cfg = dict(synth.DIMP50, C=128, H=18, W=18, num_dist_bins=4100, bin_displacement=0.005)
+    w0, feat, bb, sw = synth.dimp_problem(4100, 7, cfg)
+    its, losses = _run(_dimp_module(cfg), w0, feat, bb, sw, 4)
+    f64 = lambda a: np.asarray(a, np.float64)
+    want, wl = O.dimp_sd(f64(w0), f64(feat), f64(bb), f64(sw), num_iter=4, step_length=cfg["init_step_length"],
+                         filter_reg=cfg["init_filter_reg"], min_filter_reg=cfg["min_filter_reg"], feat_stride=cfg["feat_stride"],
+                         label_w=synth.gauss_lut(cfg["num_dist_bins"], cfg["bin_displacement"], cfg["init_gauss_sigma"]),
+                         mask_w=synth.mask_lut(cfg["num_dist_bins"], cfg["bin_displacement"], cfg["mask_init_factor"]),
+                         spatial_w=np.ones(cfg["num_dist_bins"], np.float32), bin_displacement=cfg["bin_displacement"],
+                         alpha_eps=cfg["alpha_eps"])
+    assert np.isfinite(np.asarray(want)).all() and np.all(np.diff(wl) < 0)
+    close(its, want, atol=2e-5)
+    close(losses, np.array(wl), atol=2e-5, rtol=1e-4)
+    # the frame (pt_track_frame_f32), as test_track_frame_matches_oracle_composition checks it
+    st = bench_frame.TrackState(cfg, 6, seed=77, device=DEV)
+    x = synth.clf_features(np.random.default_rng(78), 1, cfg["C"], cfg["H"], cfg["W"], cfg["K"])
+    mem0, bb0, f0 = st.mem_feat.cpu().numpy().copy(), st.mem_bb.cpu().numpy().copy(), st.filter.cpu().numpy().copy()
+    st.step(T(x)[0], slot=2, num_iter=3)
+    torch.cuda.synchronize()
+    ref = frame_port.oracle_step(cfg, mem0, bb0, st.sample_weight.cpu().numpy(), f0, x[0], slot=2, num_iter=3)
+    close(st.scores, ref["scores"], atol=2e-5)
+    assert tuple(st.peak.cpu().numpy().astype(int)) == tuple(ref["peak"])
+    close(st.mem_bb, ref["bb"], atol=1e-4)
+    close(st.filter, ref["filter"], atol=2e-5)
+
+
 def test_dimp_l2_golden():
     from pytracking_amd import optimizer
     g = load_golden("dimp_l2_small")
