@@ -41,12 +41,19 @@
 #define PT_C2_MINW 6
 #endif
 #ifndef PT_ADJ_PD
-#define PT_ADJ_PD 3      // round 3 sweep: 3 / 4 / 6 / 8 / 12 / 16 ahead -> 8.08 / 8.36 / 8.50 / 8.67 / 8.84 / 9.0 us
+#define PT_ADJ_PD 3      // k_adj2: feature groups requested in FRONT of the prologue's LDS work.  (The round-3 sweep 3 / 4 / 6 / 8 / 12 / 16
+                         // -> 8.08 / 8.36 / 8.50 / 8.67 / 8.84 / 9.0 us measured these prologue requests only: inside the loop the compiler
+                         // placed the loads itself and the knob did not bind, profiles/r09a_adj2_wave_anatomy.txt.)
 #endif
+// k_adj2: feature groups in flight in the MFMA loop.  PT_ADJ_PD of them are requested in front of the LDS work of the prologue (more
+// there delays the update stage, see the sweep above), the rest behind barrier 1 from the quad table, where the wave has the whole
+// update stage to absorb them.  Pinned in the loop: 3 / 5 / 8 in flight -> frame 100.0 / 98.7 / 99.5 us (parent 101.8,
+// profiles/r09a_adj2_wave_anatomy.txt).
+#define PT_ADJ_AHEAD 5
 
 // Phase time stamps (experiments only, -DPT_STAMPS; tools/exp_stamps.py): every wave records the 100 MHz device wall clock at
-// up to 8 points into a buffer registered with pt_debug_set_stamps(); layout [workgroup][wave (16 slots)][16]: 0..7 the stamps, 8 the
-// wave's hardware id register (HW_ID: SIMD in bits 5:4, CU 11:8, SH 12, SE 15:13), written with stamp 0; the rest unused.
+// up to 15 points into a buffer registered with pt_debug_set_stamps(); layout [workgroup][wave (16 slots)][16]: 0..7 the stamps 0..7,
+// 8 the wave's hardware id register (HW_ID: SIMD in bits 5:4, CU 11:8, SH 12, SE 15:13), written with stamp 0, 9..15 the stamps 8..14.
 #ifdef PT_STAMPS
 static unsigned long long* g_pt_stamps = nullptr;
 extern "C" void pt_debug_set_stamps(void* p) { g_pt_stamps = (unsigned long long*)p; }
@@ -56,7 +63,7 @@ extern "C" void pt_debug_set_stamps(void* p) { g_pt_stamps = (unsigned long long
     do {                                                                                                     \
         if ((a).stamps && (threadIdx.x & 63) == 0) {                                                         \
             unsigned long long* sp_ = (a).stamps + ((long)blockIdx.x * 16 + (threadIdx.x >> 6)) * 16;        \
-            sp_[(k)] = (unsigned long long)wall_clock64();                                                   \
+            sp_[(k) < 8 ? (k) : (k) + 1] = (unsigned long long)wall_clock64();                               \
             if ((k) == 0) sp_[8] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) | (1ull << 32); \
         }                                                                                                    \
     } while (0)
@@ -65,12 +72,23 @@ extern "C" void pt_debug_set_stamps(void* p) { g_pt_stamps = (unsigned long long
 #define PT_STAMP_SET(a)
 #define PT_STAMP(a, k)
 #endif
-// second stamp set (-DPT_STAMPS=2): the k_adj2 prologue in detail; the coarse k_adj2 stamps are then off
+// k_adj2 has two stamp sets: A (-DPT_STAMPS), every phase of the pass per wave, and B (-DPT_STAMPS=2), the prologue in detail (A is
+// then off).  PT_STAMP_A_ARRIVED stamps once the registers `v` of a load have arrived (the empty asm makes the compiler wait for them).
 #if defined(PT_STAMPS) && PT_STAMPS == 2
 #define PT_STAMP_A(a, k)
+#define PT_STAMP_A_ARRIVED(a, k, v)
 #define PT_STAMP_B(a, k) PT_STAMP(a, k)
 #else
 #define PT_STAMP_A(a, k) PT_STAMP(a, k)
+#ifdef PT_STAMPS
+#define PT_STAMP_A_ARRIVED(a, k, v)                                                                          \
+    do {                                                                                                     \
+        asm volatile("" ::"v"(v));                                                                           \
+        PT_STAMP(a, k);                                                                                      \
+    } while (0)
+#else
+#define PT_STAMP_A_ARRIVED(a, k, v)
+#endif
 #define PT_STAMP_B(a, k)
 #endif
 
@@ -979,6 +997,7 @@ __global__ __launch_bounds__(PT_ADJ_WAVES * 64) void k_adj2(const float* h_feat,
     const int i_hi = min(hn - 1, fdiv(gend * 16 - 1, inv_hw));
     const int ns = i_hi - i_lo + 1;
     constexpr int PD = UM < 8 ? UM : (UM == 8 ? 8 : (PT_ADJ_PD < UM ? PT_ADJ_PD : UM));
+    constexpr int PDL = PD < PT_ADJ_AHEAD ? (PT_ADJ_AHEAD < UM ? PT_ADJ_AHEAD : UM) : PD;   // groups in flight in the loop
     const int c = cb * 16 + j;
     const __amdgpu_buffer_rsrc_t fr = pt_rsrc(h_feat, (unsigned)(((long)(hn - 1) * h_stride + (long)hC * HW) * 4));
     const unsigned chw4 = 4u * (unsigned)c * (unsigned)HW;
@@ -1023,6 +1042,7 @@ __global__ __launch_bounds__(PT_ADJ_WAVES * 64) void k_adj2(const float* h_feat,
         q_in.head = lane < hn ? h_qs[lane] : 0.f;
         an_in = lane < hKS ? h_anum[lane] : 0.f;
     }
+    PT_STAMP_A(a_arg, 1);
     PT_STAMP_B(a_arg, 1);
     f32x4 av[UM];
 #pragma unroll
@@ -1053,8 +1073,8 @@ __global__ __launch_bounds__(PT_ADJ_WAVES * 64) void k_adj2(const float* h_feat,
     PT_STAMP_B(a_arg, 3);
     // Where a quad of positions lives does not depend on the channel or the tap: the workgroup computes it once per quad
     // (sample, feature offset, the 4 residual-map cells incl. the row wrap inside the quad) into an LDS table instead of
-    // every lane redoing two divisions and the wrap selects per group -- the pass is bound by VALU issue, not by memory
-    // (rocprofv3 counters, profiles/r02j_solver_instruction_mix.txt: 1020 VALU instructions per wave around 64 MFMAs).
+    // every lane redoing two divisions and the wrap selects per group (rocprofv3 counters before the table,
+    // profiles/r02j_solver_instruction_mix.txt: 1020 VALU instructions per wave around 64 MFMAs).
     //   tabA[kq][wave][u]   byte offset of the quad in the feature tensor (channel 0)
     //   tabI[kq][wave][u]   byte offsets of its 4 cells in `maps` for tap (KH-1, KW-1); + tapoff4 per lane.  A masked quad
     //                       re-reads a line already fetched and points at the zero block behind the maps.
@@ -1071,6 +1091,7 @@ __global__ __launch_bounds__(PT_ADJ_WAVES * 64) void k_adj2(const float* h_feat,
 #pragma unroll
         for (int k = 0; k < 4; ++k) tabI[4 * e + k] = 4 * (okk ? base + k + (x0 + k >= hW ? wr : 0) : ZB);
     }
+    PT_STAMP_A(a_arg, 2);
     float* __restrict__ lutl = (float*)(tabI + 16 * PT_ADJ_WAVES * UM);   // INIT: look-up tables behind the quad table
     if constexpr (INIT) {
         if (V != V_L2 && (int)threadIdx.x < 3 * h_bins) lutl[threadIdx.x] = lutv;
@@ -1089,10 +1110,10 @@ __global__ __launch_bounds__(PT_ADJ_WAVES * 64) void k_adj2(const float* h_feat,
             g_prev = pt_global((const float*)a.sd.g)[wge];
         }
     }
-    PT_STAMP_A(a, 1);
+    PT_STAMP_A(a, 3);
     PT_STAMP_B(a, 4);
     pt_lds_barrier();                                               // maps zeroed, quad table written
-    PT_STAMP_A(a, 2);
+    PT_STAMP_A(a, 4);
     PT_STAMP_B(a, 5);
 
     const int tq = (kq * PT_ADJ_WAVES + wave) * UM;
@@ -1107,6 +1128,10 @@ __global__ __launch_bounds__(PT_ADJ_WAVES * 64) void k_adj2(const float* h_feat,
     i32x4 cell[UM];
     auto issue = [&](int u) { av[u] = pt_bload4(fr, (unsigned)foff[u] + chw4); };
     auto cells = [&](int u) { cell[u] = *(const i32x4*)__builtin_assume_aligned(tabI + 4 * (tq + u), 16); };
+    // the rest of the loop's first PDL feature groups, offsets from the table: in flight across the update stage
+#pragma unroll
+    for (int u = PD; u < PDL; ++u) issue(u);
+    __builtin_amdgcn_sched_barrier(0);
     float astep = 0.f;
     if (V != V_PLAIN && a.t > 0) {
         const float a_num = wave_sum(an_in);
@@ -1129,16 +1154,20 @@ __global__ __launch_bounds__(PT_ADJ_WAVES * 64) void k_adj2(const float* h_feat,
         }
         sdp_compute<V, E>(a, i, lane, pr, astep, maps + sl * PHPW, oy, ox, home);
     }
-    PT_STAMP_A(a, 3);
+    PT_STAMP_A(a, 5);
     PT_STAMP_B(a, 6);
     pt_lds_barrier();                                               // residual maps built (the home waves' result stores stay in flight)
-    PT_STAMP_A(a, 4);
+    PT_STAMP_A(a, 6);
 
     // ---- G[c][tap] += feat[c][P] * r[P shifted by tap] over the U contiguous 16-position groups of this wave.
     //      A wave stalls at a load it cannot issue (the CU's memory pipeline accepts ~20-45 B/clk), so the loads are
-    //      software-pipelined PD groups ahead of the MFMAs that consume them instead of being issued all up front.
-    //      The loop is bound by instruction issue (3.3 of the pass's 7.6 us: 11 vector / LDS instructions around 4 MFMAs per group,
-    //      profiles/r04a_pmc_counters.txt).  Gathering a quad's cells as two 8-byte LDS reads at 4-byte alignment (even map
+    //      software-pipelined PDL groups ahead of the MFMAs that consume them instead of being issued all up front.
+    //      Left to itself the compiler sinks each load to one or two groups in front of its use (the loop waited with vmcnt(1): a
+    //      drained pipeline after the three prologue groups, then ~1.5 groups = ~0.2 us of cover against the L2 latency; stamps:
+    //      loop 3.7-4.0 us per wave for 1.7 us of MFMA time, profiles/r09a_adj2_wave_anatomy.txt).  A scheduling barrier behind each
+    //      request pins it at the head of its group: exactly PDL loads in flight, one request per 4 MFMAs.
+    //      (Rounds 3-6 read the loop as bound by instruction issue -- 11 vector / LDS instructions around 4 MFMAs per group,
+    //      profiles/r04a_pmc_counters.txt; the stamps say load latency.)  Gathering a quad's cells as two 8-byte LDS reads at 4-byte alignment (even map
     //      widths) lost: k_adj2 7.6 -> 12.0 us; as two dword-pair reads 7.55 -> 7.94 us (profiles/r04j_adjoint_pair_gather_ab.txt).
     f32x4 accA = {0, 0, 0, 0}, accB = {0, 0, 0, 0};
     auto mfma_loop = [&]() {                                        // (a lambda: written inline the compiler schedules the pass differently)
@@ -1151,9 +1180,11 @@ __global__ __launch_bounds__(PT_ADJ_WAVES * 64) void k_adj2(const float* h_feat,
         gather(0);
 #pragma unroll
         for (int u = 0; u < UM; ++u) {
-            if (u + PD < UM) issue(u + PD);
+            if (u + PDL < UM) issue(u + PDL);
+            __builtin_amdgcn_sched_barrier(0);                      // the load stays here, see above
             if (u + 2 < UM) cells(u + 2);
             if (u + 1 < UM) gather(u + 1);
+            if (u == 0) PT_STAMP_A_ARRIVED(a, 7, av[0]);
             // masked quads multiply a finite, re-read feature value by a gathered zero
             accA = mfma16(av[u][0], bv[u][0], accA);
             accB = mfma16(av[u][1], bv[u][1], accB);
@@ -1162,11 +1193,11 @@ __global__ __launch_bounds__(PT_ADJ_WAVES * 64) void k_adj2(const float* h_feat,
         }
     };
     mfma_loop();
-    PT_STAMP_A(a, 5);
+    PT_STAMP_A(a, 8);
 #pragma unroll
     for (int r = 0; r < 4; ++r) red[wave][(4 * kq + r) * 16 + j] = accA[r] + accB[r];
     __syncthreads();
-    PT_STAMP_A(a, 6);
+    PT_STAMP_A(a, 9);
     if (threadIdx.x < 256) {
         const int e = threadIdx.x, row = e >> 4, tap = e & 15;
         float s = 0.f;
@@ -1174,10 +1205,11 @@ __global__ __launch_bounds__(PT_ADJ_WAVES * 64) void k_adj2(const float* h_feat,
         for (int w = 0; w < PT_ADJ_WAVES; ++w) s += red[w][e];
         if (tap < KK) a.gpart[(long)ks * a.C * KK + (long)(cb * 16 + row) * KK + tap] = s;
     }
+    PT_STAMP_A(a, 10);
     // w_t = w_{t-1} - step*alpha*g (:160): nothing in this launch reads it, so its two loads (requested behind the feature
     // loads, the counter retires in order) are only waited for here
     if (wupd && (int)threadIdx.x < 16 * KK) a.sd.w_iters[(long)a.t * a.sd.CKK + wge] = w_prev - astep * g_prev;
-    PT_STAMP_A(a, 7);
+    PT_STAMP_A(a, 11);
     PT_STAMP_B(a, 7);
 }
 

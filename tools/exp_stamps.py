@@ -18,8 +18,9 @@ if os.environ.get("PT_STAMP_SET") == "2":
 else:
     ADJ = None
 NAMES = {0: ["entry", "loads issued", "filter reduced+staged", "barrier 1", "MFMA loop done", "T written", "barrier 2", "end"],
-         1: ["entry", "tables + update inputs requested", "barrier 1", "update stage done", "barrier 2", "MFMA loop done",
-             "red written + barrier 3", "end"]}
+         1: ["entry", "update inputs requested", "table built", "argument block held", "barrier 1", "update stage done", "barrier 2",
+             "first feature group arrived", "MFMA loop done", "red written + barrier 3", "partial gradient stored", "end"]}
+SLOTS = [0, 1, 2, 3, 4, 5, 6, 7, 9, 10, 11, 12, 13, 14, 15]            # buffer slot of stamp k (slot 8 is HW_ID)
 
 
 def main():
@@ -54,7 +55,7 @@ def main():
                     L.pt_debug_set_stamps(None)
                     raw = buf.cpu().numpy().reshape(nwg, 16, 16)
                     hw = raw[:, :, 8]                                               # HW_ID | 1 << 32 (0: wave slot unused)
-                    t = raw[:, :, :8].astype(np.float64)
+                    t = raw[:, :, SLOTS].astype(np.float64)
                     t[t == 0] = np.nan
                     t = (t - np.nanmin(t[:, :, 0])) * 0.01                      # 100 MHz -> us
                     acc.append(t)
@@ -62,7 +63,8 @@ def main():
                 t = np.nanmean(np.stack(acc), axis=0)
                 print(f"n={n} {'k_corr2 (fused)' if which == 0 else 'k_adj2 (sd)'}: per-stamp over all waves [us since first wave entry]: min / mean / max"
                       f" | per-WORKGROUP last wave: mean")
-                for k in range(8):
+                last = len(NAMES[which]) - 1
+                for k in range(last + 1):
                     col = t[:, :, k]
                     if np.all(np.isnan(col)):
                         continue
@@ -70,7 +72,9 @@ def main():
                     print(f"   {k} {NAMES[which][k]:34s} {np.nanmin(col):6.2f} {np.nanmean(col):6.2f} {np.nanmax(col):6.2f}   | {np.nanmean(wgmax):6.2f}")
                 if which == 0:
                     simd_table(np.concatenate(acc), np.concatenate(acc_hw))       # placement differs from launch to launch
-                dur = np.nanmax(t[:, :, 7], axis=1) - np.nanmin(t[:, :, 0], axis=1)
+                elif last == 11:
+                    adj_table(np.concatenate(acc), np.concatenate(acc_hw), n, c, nwg)
+                dur = np.nanmax(t[:, :, last], axis=1) - np.nanmin(t[:, :, 0], axis=1)
                 print(f"   workgroup duration (entry of first wave -> end of last): min {np.nanmin(dur):.2f} mean {np.nanmean(dur):.2f} max {np.nanmax(dur):.2f}")
 
 
@@ -103,6 +107,61 @@ def simd_table(t, hw):
     wg_last = np.nanmax(t[:, :, 4], axis=1) - np.nanmin(t[:, :, 3], axis=1)
     wg_first = np.nanmin(t[:, :, 4], axis=1) - np.nanmin(t[:, :, 3], axis=1)
     print(f"   per workgroup, first barrier-1 exit -> MFMA loop done: first wave {np.mean(wg_first):5.2f} us, last wave {np.mean(wg_last):5.2f} us")
+
+
+def adj_table(t, hw, n, c, nwg):
+    """k_adj2 (stamp set A): waves per SIMD, the update stage (wave w < ns carries sample w of the slice) and the wait behind it at
+    barrier 2, the MFMA loop per wave, the last wave at each barrier.  Every repeat is a set of `nwg` buffer rows of its own.
+    Which samples a workgroup's slice holds is restated here from pt_fast_plan / k_adj2 (csrc/fast_passes.hip: 8 or 16 position
+    slices, ks = (b >> 3) / bpx, >= 8 channel blocks); the workgroup count is checked against it, change the two together."""
+    reps = t.shape[0] // nwg
+    b = np.tile(np.arange(nwg), reps)
+    live = (hw != 0).any(axis=1)
+    t, hw, b = t[live], hw[live], b[live]
+    used = hw != 0
+    nw = int(used[0].sum())
+    t, hw, used = t[:, :nw], hw[:, :nw], used[:, :nw]
+    simd = (hw >> 4) & 3
+    cu = (hw >> 8) & 0xFF
+    per = np.stack([((simd == s) & used).sum(axis=1) for s in range(4)], axis=1)
+    pat, cnt = np.unique(np.sort(per, axis=1)[:, ::-1], axis=0, return_counts=True)
+    print(f"   waves per workgroup {nw}; waves per SIMD (sorted) : workgroups  " + "  ".join(f"{'/'.join(map(str, p))}: {k}" for p, k in zip(pat, cnt)))
+    print(f"   workgroups whose waves share one CU id: {sum(len(set(cu[k])) == 1 for k in range(hw.shape[0]))} of {hw.shape[0]}")
+    print(f"   workgroup 0: SIMD of wave 0.. = {[int(v) for v in simd[0]]}")
+    # samples of the workgroup's position slice (pt_fast_plan / k_adj2: ks = (b >> 3) / bpx with >= 8 channel blocks)
+    HW = c["H"] * c["W"]
+    NG = (n * HW + 15) // 16
+    gper = next(g for g in (-(-NG // ks) for ks in (8, 16)) if -(-g // nw) <= 128 // nw)
+    assert c["C"] // 16 >= 8 and hw.shape[0] == reps * (c["C"] // 16) * -(-NG // gper), "the restated slice plan does not match the launch"
+    ks = (b >> 3) // (c["C"] // 16 // 8)
+    gbeg, gend = ks * gper, np.minimum(NG, ks * gper + gper)
+    ns = np.minimum(n - 1, (gend * 16 - 1) // HW) - (gbeg * 16) // HW + 1
+    upd = np.arange(nw)[None, :] < ns[:, None]
+    print(f"   samples per slice: {sorted(set(int(v) for v in ns))}; waves with an update stage {int(upd.sum())} of {upd.size}")
+    share = np.take_along_axis(per, simd, axis=1).astype(np.float64)
+    seg = lambda k0, k1: t[:, :, k1] - t[:, :, k0]
+    for name, sel in (("with an update stage", upd), ("without", ~upd)):
+        if sel.any():
+            print(f"   waves {name:21s}: barrier 1 -> update stage done {np.nanmean(seg(4, 5)[sel]):5.2f} us mean {np.nanmax(seg(4, 5)[sel]):5.2f} max, "
+                  f"then at barrier 2 for {np.nanmean(seg(5, 6)[sel]):5.2f} us; barrier 2 -> first features {np.nanmean(seg(6, 7)[sel]):5.2f}; "
+                  f"barrier 2 -> MFMA loop done {np.nanmean(seg(6, 8)[sel]):5.2f} us; at barrier 3 for {np.nanmean(seg(8, 9)[sel]):5.2f} us")
+    for k in sorted(set(share.astype(int).ravel())):
+        sel = share == k
+        print(f"   waves on a SIMD holding {k}: {int(sel.sum()):5d} waves, barrier 2 -> MFMA loop done {np.nanmean(seg(6, 8)[sel]):5.2f} us mean, "
+              f"{np.nanmax(seg(6, 8)[sel]):5.2f} max")
+    for w in range(nw):
+        print(f"   wave {w:2d}: entry {np.nanmean(t[:, w, 0]):5.2f}, args held {np.nanmean(t[:, w, 3]):5.2f}, update {np.nanmean(seg(4, 5)[:, w]):5.2f}, at barrier 2 "
+              f"{np.nanmean(seg(5, 6)[:, w]):5.2f}, first features +{np.nanmean(seg(6, 7)[:, w]):5.2f}, loop {np.nanmean(seg(6, 8)[:, w]):5.2f}, done at "
+              f"{np.nanmean(t[:, w, 8]):5.2f}, at barrier 3 {np.nanmean(seg(8, 9)[:, w]):5.2f}; shares its SIMD with {np.nanmean(share[:, w]) - 1:4.2f} others")
+    for name, k in (("barrier 1", 3), ("barrier 2", 5), ("barrier 3", 8)):
+        lastw = np.nanargmax(t[:, :, k], axis=1)
+        spread = np.nanmax(t[:, :, k], axis=1) - np.nanmin(t[:, :, k], axis=1)
+        print(f"   last wave to reach {name}: " + " ".join(f"w{w}:{int((lastw == w).sum())}" for w in range(nw)) +
+              f"; first -> last arrival {np.mean(spread):5.2f} us mean")
+    ent = np.nanmin(t[:, :, 0], axis=1)
+    print("   per workgroup since its first wave's entry: " + ", ".join(
+        f"{nm} {np.mean(np.nanmax(t[:, :, k], axis=1) - ent):5.2f}" for nm, k in (("barrier 1", 4), ("barrier 2", 6), ("loop done (last wave)", 8),
+                                                                                 ("barrier 3", 9), ("end", 11))))
 
 
 if ADJ:
