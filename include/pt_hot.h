@@ -643,6 +643,63 @@ int pt_tcm_match_f32(const pt_tcm_match_params* p, const float* weights, const f
                      float* log_assignment, long long* matches0, long long* matches1, float* match_scores0,
                      float* match_scores1, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * KYS state-aware response prediction (pytracking/tracker/kys/kys.py:314), kys.hip.
+ *
+ * pt_kys_cost_volume_f32: CostVolume.forward (ltr/models/kys/cost_volume.py:15-26) for kernel_size 3, stride 1, any
+ *   max_displacement md >= 1.  feat_cur, feat_prev (B, C, H, W) contiguous.  For a current position (r, c), a previous position
+ *   (r', c') and taps i, j in {-1, 0, 1}, a tap contributing only where BOTH indices lie inside the map:
+ *       v(r, c, r', c') = sum_ch sum_{i,j} cur[b, ch, r+i, c+j] * prev[b, ch, r'+i, c'+j]          (no normalisation)
+ *   remap != 0 (abs_coordinate_output): out (B, H*W, H, W), out[b, r' W + c', r, c] = v if |r'-r| <= md and |c'-c| <= md, else 0
+ *   remap == 0: out (B, (2 md + 1)^2, H, W), out[b, di (2 md + 1) + dj, r, c] = v(r, c, r + di - md, c + dj - md)
+ *   This is SpatialCorrelationSampler(3, 2 md + 1, 1, 1) (+ remap_cost_volume); parity with that CUDA extension is UNPINNED (it
+ *   is not installable here; the definition above is written from its documented behaviour).
+ *   Two launches: channel Gram matrix in up to 8 K slices on the matrix cores (ws: pt_kys_cost_volume_ws_bytes), then the 9-tap
+ *   diagonal sum over the slices in double precision, window mask and store.  H*W <= PT_KYS_CV_MAX_HW.  Repeated calls are
+ *   bit-identical.
+ *
+ * pt_kys_predict_response_f32: ResponsePredictor.forward (ltr/models/kys/response_predictor.py:65-159) in eval mode, with the
+ *   shift_features calls PredictorWrapper.predict_response puts around it (predictor_wrapper.py:113-148): four launches, no host
+ *   synchronisation.  state_dim 8, representation_predictor_dims (64, 32), gru_ksz 3, prev_max_pool_ksz 1 only; with_conf: 1 for
+ *   conf_measure 'max', 0 for 'none'.  H*W <= PT_KYS_PRED_MAX_HW.
+ *   Inputs: cost_volume (B, H*W, H, W); state_prev (B, 8, H, W) or NULL, then label_prev (B, H, W) (shifted by -shift_px and fed
+ *   to init_hidden_state_predictor); dimp_score (B, H, W) unshifted; window NULL or (H, W) (window_stride 0) / (B, H, W)
+ *   (window_stride H*W).  shift_px: the pixel offset of the reference's +-0.5 / size translation (0.25 at the defaults of
+ *   affine_grid / grid_sample: bilinear, zero padding, align_corners False); inputs are sampled at -shift_px, outputs at +shift_px.
+ *   Outputs: response (B, H, W) shifted back; state_cur (B, 8, H, W); propagation_weights (B, H*W, H, W) (= cost_volume_processed);
+ *   propagated_h (B, 8, H, W); propagation_conf (B, H, W) (with_conf only, else may be NULL); fused_score_orig (B, H, W) (before
+ *   threshold, window and shift); is_target, is_target_after_prop, is_target_new (B, H, W) shifted back.
+ *
+ *   Weight pack (float32, conv weights (out, in, 3, 3) row-major, eval BatchNorm folded as for pt_tcm_match_f32), in this order:
+ *     cost_volume_proc1  W 8x1, b 8 (BN folded, ReLU), W 1x8, b 1 (BN folded);  cost_volume_proc2 the same
+ *     init_hidden_state_predictor  W 8x1 (no bias, tanh)
+ *     is_target_predictor  W 4x8, b 4 (ReLU), W 1x4, b 1
+ *     representation_predictor  W 64x(9 + with_conf), b 64, W 32x64, b 32 (ReLU);  response_predictor  W 1x32, b 1 (sigmoid)
+ *     state_predictor (ConvGRU, input = [score, response, max score, max response, state])  reset W 8x12, b 8; update; state_new
+ * ---------------------------------------------------------------------------------------------- */
+#define PT_KYS_CV_MAX_HW 1024
+#define PT_KYS_PRED_MAX_HW 400
+typedef struct pt_kys_predict_params {
+    int B, H, W;
+    int state_dim, rep_dim0, rep_dim1, gru_ksz;
+    int with_conf;           /* conf_measure 'max': 1, 'none': 0 */
+    int has_thresh;          /* dimp_thresh is not None */
+    float dimp_thresh;
+    float shift_px;
+    long window_stride;      /* floats between the windows of consecutive sequences: 0 or H*W */
+    size_t weight_floats;    /* size of the pack handed in (checked against pt_kys_weight_floats) */
+} pt_kys_predict_params;
+size_t pt_kys_cost_volume_ws_bytes(int B, int C, int H, int W);
+int pt_kys_cost_volume_f32(const float* feat_cur, const float* feat_prev, int B, int C, int H, int W, int kernel_size,
+                           int max_displacement, int stride, int remap, float* out, void* ws, size_t ws_bytes, void* stream);
+size_t pt_kys_weight_floats(int state_dim, int rep_dim0, int rep_dim1, int gru_ksz, int with_conf);   /* 0: dims not covered */
+size_t pt_kys_predict_ws_bytes(int B, int H, int W);
+int pt_kys_predict_response_f32(const pt_kys_predict_params* p, const float* weights, const float* cost_volume,
+                                const float* state_prev, const float* label_prev, const float* dimp_score, const float* window,
+                                float* response, float* state_cur, float* propagation_weights, float* propagated_h,
+                                float* propagation_conf, float* fused_score_orig, float* is_target, float* is_target_after_prop,
+                                float* is_target_new, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PT_HOT_LIB", os.path.join(_HERE, "libpt_hot.so"))   # override: experiments only
-SOURCES = ["filter_kernels.hip", "fast_passes.hip", "sd_solver.hip", "mf_kernels.hip", "lwl_solver.hip", "atom_cg.hip", "atom_gn.hip", "tomp.hip", "localize.hip", "iou_refine.hip", "prroi.hip", "patch.hip", "frame_full.hip", "api.hip", "gn_hinge.hip", "tcm.hip"]
+SOURCES = ["filter_kernels.hip", "fast_passes.hip", "sd_solver.hip", "mf_kernels.hip", "lwl_solver.hip", "atom_cg.hip", "atom_gn.hip", "tomp.hip", "localize.hip", "iou_refine.hip", "prroi.hip", "patch.hip", "frame_full.hip", "api.hip", "gn_hinge.hip", "tcm.hip", "kys.hip"]
 HEADERS = ["common.h", "pt_internal.h", "rbuild.h", "sd_common.h", "mfma_gemm.h", "prroi_dev.h", "localize_dev.h", "frame_mid.h", os.path.join("..", "..", "include", "pt_hot.h")]
 # kernarg preload: leading scalar kernel parameters arrive in SGPRs at wave launch (kernels that take them that way only)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-pass-failed", "-mllvm", "-amdgpu-kernarg-preload-count=14"]
@@ -96,6 +96,7 @@ EXPORTS = [
     "pt_gn_hinge_ws_bytes", "pt_gn_hinge_solve_f32", "pt_gn_hinge_route",
     "pt_tcm_peaks_f32", "pt_tcm_desc_ws_bytes", "pt_tcm_desc_f32",
     "pt_tcm_match_weight_floats", "pt_tcm_match_ws_bytes", "pt_tcm_match_f32",
+    "pt_kys_cost_volume_ws_bytes", "pt_kys_cost_volume_f32", "pt_kys_weight_floats", "pt_kys_predict_ws_bytes", "pt_kys_predict_response_f32",
 ]
 
 PT_TCM_MAX_POINTS, PT_TCM_MAX_LAYERS = 64, 32       # include/pt_hot.h
@@ -107,6 +108,16 @@ class TcmMatchParams(ctypes.Structure):
                 + [(n, ctypes.c_int) for n in ("skip_gnn", "sinkhorn_iters")] + [("filter_threshold", ctypes.c_float)]
                 + [("kpt_center0", ctypes.c_float * 2), ("kpt_scale0", ctypes.c_float), ("kpt_center1", ctypes.c_float * 2),
                    ("kpt_scale1", ctypes.c_float), ("weight_floats", ctypes.c_size_t)])
+
+
+PT_KYS_CV_MAX_HW, PT_KYS_PRED_MAX_HW = 1024, 400    # include/pt_hot.h
+
+
+class KysPredictParams(ctypes.Structure):
+    """`pt_kys_predict_params` of include/pt_hot.h."""
+    _fields_ = ([(n, ctypes.c_int) for n in ("B", "H", "W", "state_dim", "rep_dim0", "rep_dim1", "gru_ksz", "with_conf", "has_thresh")]
+                + [("dimp_thresh", ctypes.c_float), ("shift_px", ctypes.c_float), ("window_stride", ctypes.c_long),
+                   ("weight_floats", ctypes.c_size_t)])
 
 
 class GnHingeParams(ctypes.Structure):
@@ -369,6 +380,16 @@ def lib():
     L.pt_tcm_match_ws_bytes.argtypes = [ctypes.POINTER(TcmMatchParams)]
     L.pt_tcm_match_f32.restype = i
     L.pt_tcm_match_f32.argtypes = [ctypes.POINTER(TcmMatchParams)] + [vp] * 14 + [sz, vp]
+    L.pt_kys_cost_volume_ws_bytes.restype = sz
+    L.pt_kys_cost_volume_ws_bytes.argtypes = [i] * 4
+    L.pt_kys_cost_volume_f32.restype = i
+    L.pt_kys_cost_volume_f32.argtypes = [vp, vp] + [i] * 8 + [vp, vp, sz, vp]
+    L.pt_kys_weight_floats.restype = sz
+    L.pt_kys_weight_floats.argtypes = [i] * 5
+    L.pt_kys_predict_ws_bytes.restype = sz
+    L.pt_kys_predict_ws_bytes.argtypes = [i] * 3
+    L.pt_kys_predict_response_f32.restype = i
+    L.pt_kys_predict_response_f32.argtypes = [ctypes.POINTER(KysPredictParams)] + [vp] * 16 + [sz, vp]
     L.pt_sample_patch_f32.restype = i
     L.pt_sample_patch_f32.argtypes = [vp, i, i, i, ctypes.POINTER(PatchGeom), i, vp, i, i, vp]
     L.pt_augment_patches_f32.restype = i

@@ -30,6 +30,9 @@ What gets rebound (import path = contract; nothing in the reference tree is edit
   ltr.data.processing_utils.find_local_maxima, ltr.models.target_candidate_matching.target_candidate_matching
   .DescriptorExtractor.get_descriptors, ltr.models.target_candidate_matching.superglue.SuperGlue._forward
                                                   (KeepTrack candidate matching)      -> pytracking_amd.candidate_matching
+  spatial_correlation_sampler  (module is CREATED when nothing importable is there: a CUDA extension without a ROCm build),
+  ltr.models.kys.predictor_wrapper.PredictorWrapper.predict_response, ltr.models.kys.cost_volume.CostVolume.forward
+                                                  (KYS response prediction)           -> pytracking_amd.kys
   pytracking.libs.dcf.max2d, pytracking.tracker.dimp.dimp.DiMP.localize_advanced (and DiMPSimple's, KeepTrack's),
   pytracking.tracker.tomp.tomp.ToMP.localize_advanced  (score-map localisation)       -> pytracking_amd.localization
   pytracking.tracker.dimp.dimp.DiMP.optimize_boxes_default / optimize_boxes_relative (and DiMPSimple's, KeepTrack's),
@@ -529,6 +532,62 @@ def _install_candidate_matching(orig, strict):
     scls._forward = _forward
 
 
+def provide_correlation_sampler(orig=None):
+    """Register pytracking_amd.kys as `spatial_correlation_sampler` (the CUDA extension ltr/models/kys/cost_volume.py:5 imports; it has
+    no ROCm build) when nothing importable is there, so that `import ltr.models.tracking.kysnet` works.  An installed package or a module
+    somebody else registered under that name (a CPU stand-in in a test harness) is left alone."""
+    import importlib.util
+    name = "spatial_correlation_sampler"
+    if name in sys.modules:
+        return sys.modules[name]
+    try:
+        found = importlib.util.find_spec(name) is not None
+    except (ImportError, ValueError):
+        found = False
+    if found:
+        return None
+    from . import kys as _kys
+    sys.modules[name] = _kys
+    if orig is not None:
+        orig["correlation_sampler"] = name
+    return _kys
+
+
+def _install_kys(orig, strict):
+    """KYS (kys.py:314): `PredictorWrapper.predict_response` and `CostVolume.forward`.  CPU tensors, grad-enabled calls, training mode, a
+    list of reference frames, conf_measure 'entropy', other channel counts and maps above 20 x 20 keep the reference's code."""
+    from . import kys as _kys
+    provide_correlation_sampler(orig)
+    try:
+        wmod = importlib.import_module("ltr.models.kys.predictor_wrapper")
+        cmod = importlib.import_module("ltr.models.kys.cost_volume")
+    except Exception:
+        return
+    wcls, ccls = wmod.PredictorWrapper, cmod.CostVolume
+    ref_pr, ref_cv = wcls.predict_response, ccls.forward
+    orig["kys"] = (wcls, ref_pr, ccls, ref_cv)
+
+    def predict_response(self, data, dimp_thresh=None, output_window=None):
+        if _hit("PredictorWrapper.predict_response", _kys.covered_predict_response(self, data, dimp_thresh, output_window)):
+            return _kys.predict_response(self, data, dimp_thresh, output_window, checked=True)
+        if strict:
+            raise NotImplementedError("PredictorWrapper.predict_response: call outside the gfx950 hot path")
+        return ref_pr(self, data, dimp_thresh, output_window)
+
+    def forward(self, feat1, feat2):
+        assert feat1.dim() == 4 and feat2.dim() == 4, 'Expect 4 dimensional inputs'
+        if _hit("CostVolume.forward", _kys.covered_cost_volume(self, feat1, feat2)):
+            return _kys.cost_volume_forward(self, feat1, feat2)
+        if strict:
+            raise NotImplementedError("CostVolume.forward: call outside the gfx950 hot path")
+        return ref_cv(self, feat1, feat2)
+
+    for fn, ref in ((predict_response, ref_pr), (forward, ref_cv)):
+        fn.__doc__, fn.__wrapped__ = ref.__doc__, ref
+    wcls.predict_response = predict_response
+    ccls.forward = forward
+
+
 def _install_gn_hinge(orig, strict, smod):
     """`GNSteepestDescent` on an exact reference `LinearFilterHinge` with parameter_batch_dim=0, residual_batch_dim=1
     (dimpnet.py:236-242, rts_net.py:325-333) -> the fused solver (pytracking_amd.gn_hinge); the residual object stays the reference's.
@@ -596,7 +655,7 @@ def _install_rts_residual(orig, strict, mirror):
 
 
 def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=True, iou_refine=True, preprocessing=True,
-            candidate_matching=True):
+            candidate_matching=True, kys=True):
     """Rebind the boundary symbols.  Call after the reference is importable (`sys.path`) and before networks or
     trackers are constructed.  Idempotent."""
     if _state["installed"]:
@@ -688,6 +747,8 @@ def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=T
         _install_preprocessing(orig, strict)
     if candidate_matching:
         _install_candidate_matching(orig, strict)
+    if kys:
+        _install_kys(orig, strict)
     if atom_cg:
         try:
             pmod = importlib.import_module("pytracking.libs.optimization")
@@ -801,5 +862,12 @@ def uninstall():
     if "candidate_matching" in orig:
         pmod, ref_flm, dcls, ref_desc, scls, ref_fwd = orig["candidate_matching"]
         pmod.find_local_maxima, dcls.get_descriptors, scls._forward = ref_flm, ref_desc, ref_fwd
+    if "kys" in orig:
+        wcls, ref_pr, ccls, ref_cv = orig["kys"]
+        wcls.predict_response, ccls.forward = ref_pr, ref_cv
+    if "correlation_sampler" in orig:                      # only the entry install() created
+        from . import kys as _kys
+        if sys.modules.get(orig["correlation_sampler"]) is _kys:
+            del sys.modules[orig["correlation_sampler"]]
     _state["installed"] = False
     orig.clear()

@@ -436,3 +436,75 @@ def tcm_match_inputs(seed, M, N, image_shape=(480, 640)):
         out["img_coords" + s] = np.stack([rng.uniform(0, h, n), rng.uniform(0, w, n)], 1).astype(np.float32)
         out["scores" + s] = rng.uniform(0.05, 1.0, (1, n)).astype(np.float32)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# KYS response prediction (ltr/models/kys): motion features, module state, per-frame inputs
+KYS = dict(C=1024, H=18, W=18, md=9, state_dim=8, rep_dims=(64, 32))    # kysnet.py:120-123 at the deployed search area
+
+
+def kys_features(seed, B, C, H, W, shift=(1, -1)):
+    """(cur, prev) layer3-like motion features (B, C, H, W): `prev` is `cur` displaced by `shift` plus noise, scaled so that a
+    matching 3x3 window correlates to about 10 and a non-matching one to about 0.1 (a trained net's BatchNorm sees such a range)."""
+    rng = np.random.default_rng(seed)
+    a = np.float32(np.sqrt(10.0 / (9.0 * C)))
+    cur = rng.standard_normal((B, C, H, W), dtype=np.float32) * a
+    prev = np.roll(cur, shift, axis=(2, 3)) * np.float32(0.8) + rng.standard_normal((B, C, H, W), dtype=np.float32) * (a * np.float32(0.6))
+    return cur.astype(np.float32), prev.astype(np.float32)
+
+
+def kys_predictor_state(seed, conf_measure="max", state_dim=8, rep_dims=(64, 32)):
+    """A ResponsePredictor state_dict (numpy, float32): kaiming-like conv weights, small biases, and BatchNorm running statistics,
+    gains and shifts away from their defaults (the second cost-volume stack sees softmax outputs: its statistics are small)."""
+    rng = np.random.default_rng(seed)
+    sd = {}
+
+    def conv(name, o, i, bias=True, gain=1.0):
+        sd[name + ".weight"] = (rng.standard_normal((o, i, 3, 3), dtype=np.float32) * np.float32(gain * np.sqrt(2.0 / (9 * i)))).astype(np.float32)
+        if bias:
+            sd[name + ".bias"] = (rng.standard_normal(o, dtype=np.float32) * np.float32(0.1)).astype(np.float32)
+
+    def bn(name, c, mean=0.2, var=(0.5, 2.0)):
+        sd[name + ".weight"] = rng.uniform(0.5, 1.5, c).astype(np.float32)
+        sd[name + ".bias"] = (rng.standard_normal(c) * 0.1).astype(np.float32)
+        sd[name + ".running_mean"] = (rng.standard_normal(c) * mean).astype(np.float32)
+        sd[name + ".running_var"] = rng.uniform(var[0], var[1], c).astype(np.float32)
+        sd[name + ".num_batches_tracked"] = np.array(100, dtype=np.int64)
+
+    for stack, mean, var in (("cost_volume_proc1", 0.2, (0.5, 2.0)), ("cost_volume_proc2", 0.002, (1e-4, 4e-4))):
+        conv(stack + ".0.0", 8, 1)
+        bn(stack + ".0.1", 8, mean, var)
+        conv(stack + ".1.0", 1, 8)
+        bn(stack + ".1.1", 1)
+    in_dim = state_dim + 1 + (conf_measure != "none")
+    for k, out_dim in enumerate(rep_dims):
+        conv(f"representation_predictor.{k}.0", out_dim, in_dim)
+        in_dim = out_dim
+    conv("response_predictor.0.0", 1, in_dim)
+    for g in ("conv_reset", "conv_update", "conv_state_new"):
+        conv("state_predictor." + g, state_dim, 4 + state_dim)
+    conv("init_hidden_state_predictor.0.0", state_dim, 1, bias=False, gain=2.0)
+    conv("is_target_predictor.0.0", 4, state_dim)
+    conv("is_target_predictor.1.0", 1, 4)
+    return sd
+
+
+def kys_frame_inputs(seed, B, H, W, state_dim=8):
+    """Per-frame inputs: dimp_score (B, 1, H, W) (a peak near the centre, a distractor, noise), label_prev (B, 1, H, W) (a Gaussian
+    label), state_prev (B, state_dim, H, W) in (-1, 1), window (1, H, W) (a Hann-like output window)."""
+    rng = np.random.default_rng(seed)
+    y, x = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+
+    def bump(cy, cx, s):
+        return np.exp(-((y - cy) ** 2 + (x - cx) ** 2) / (2 * s * s))
+
+    score = np.zeros((B, 1, H, W))
+    label = np.zeros((B, 1, H, W))
+    for b in range(B):
+        cy, cx = (H - 1) / 2 + rng.uniform(-1, 1), (W - 1) / 2 + rng.uniform(-1, 1)
+        score[b, 0] = 0.9 * bump(cy, cx, 1.2) + 0.5 * bump(rng.uniform(0, H - 1), rng.uniform(0, W - 1), 1.0) + 0.03 * rng.standard_normal((H, W))
+        label[b, 0] = bump(cy + rng.uniform(-1, 1), cx + rng.uniform(-1, 1), 1.0)
+    state = np.tanh(rng.standard_normal((B, state_dim, H, W)) * 0.7)
+    win = (0.5 - 0.5 * np.cos(2 * np.pi * (y + 1) / (H + 1))) * (0.5 - 0.5 * np.cos(2 * np.pi * (x + 1) / (W + 1)))
+    return dict(dimp_score_cur=score.astype(np.float32), label_prev=label.astype(np.float32), state_prev=state.astype(np.float32),
+                window=win[None].astype(np.float32))
