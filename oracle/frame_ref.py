@@ -28,7 +28,7 @@ class ReferenceTracker:
         import ltr.models.layers.filter as rfilter
         import ltr.models.target_classifier.optimizer as roptim
         from pytracking_amd import install as amd
-        if amd._state["installed"]:
+        if amd.installed():
             raise RuntimeError("ReferenceTracker is the baseline: pytracking_amd.install() must not be active")
         self.torch, self.rfilter = torch, rfilter
         if threads:

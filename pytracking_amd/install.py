@@ -42,10 +42,18 @@ What gets rebound (import path = contract; nothing in the reference tree is edit
 Dispatch rule of the rebound *functions*: device fp32 tensors of a shape the gfx950 kernels cover go to the C ABI;
 everything else (CPU tensors, dilations, grouped filters, K*K > 16, more than 16 filters) is outside the hot path and
 is handed to the reference's ORIGINAL function object -- its own stock-PyTorch code, not a re-implementation --
-unless `strict=True`, in which case it raises.  The rebound *classes* have no such escape: they run the fused
-solver or raise.
+unless `strict=True`, in which case it raises (`_outside` is the one place that decides).  The rebound optimiser /
+learner *classes* follow the same rule per call of their `forward`; the classes that choose an implementation when they
+are constructed (`Transformer`, `LWTLResidual`, `ConjugateGradient` ...) follow it per construction.
+
+Every rebinding -- module attributes, class attributes, names other modules imported by value, `sys.modules` entries --
+goes through `_rebind` / `_rebind_module`, which record `(owner, name, previous binding or _MISSING, new binding)` in one
+ordered ledger.  `uninstall()` replays the ledger backwards (set the previous binding, delete what did not exist) and has
+no per-family knowledge; an `install()` that raises replays what it had recorded, so nothing stays half installed.
+`installed()` and `original(owner, name)` are the public view of that state.
 """
 import collections
+import functools
 import importlib
 import sys
 import types
@@ -58,7 +66,8 @@ from . import optimizer as _optimizer
 from . import prroi_pool as _prroi
 from . import steepestdescent as _sd
 
-_state = {"installed": False, "originals": {}}
+_MISSING = object()
+_state = {"installed": False, "strict": False, "ledger": []}
 
 # which branch every rebound symbol took, per call: "<symbol>.fast" (gfx950 path) / "<symbol>.reference" (handed to the
 # reference's own code).  tests/test_trackers_on_device.py asserts on it that a tracker running on the GPU really went
@@ -66,9 +75,92 @@ _state = {"installed": False, "originals": {}}
 stats = collections.Counter()
 
 
+def installed():
+    """True from a successful `install()` to the next `uninstall()`."""
+    return _state["installed"]
+
+
+def original(owner, name):
+    """The object `owner.name` was bound to before install() rebound it: the reference's own function, method or class."""
+    for o, n, prev, _ in _state["ledger"]:
+        if o is owner and n == name and prev is not _MISSING:
+            return prev
+    raise KeyError(f"{name}: not rebound by install()")
+
+
+def _rebind(owner, name, value):
+    """`owner.name = value` (module or class), recorded in the ledger."""
+    _state["ledger"].append((owner, name, vars(owner).get(name, _MISSING), value))
+    setattr(owner, name, value)
+
+
+def _rebind_module(name, module):
+    """`sys.modules[name] = module`, recorded in the ledger."""
+    _state["ledger"].append((sys.modules, name, sys.modules.get(name, _MISSING), module))
+    sys.modules[name] = module
+
+
+def _replay(keep=0):
+    """Undo the ledger's entries beyond the first `keep`, last first."""
+    ledger = _state["ledger"]
+    while len(ledger) > keep:
+        owner, name, prev, new = ledger.pop()
+        if owner is not sys.modules:
+            if prev is _MISSING:
+                delattr(owner, name)
+            else:
+                setattr(owner, name, prev)
+        elif prev is not _MISSING:
+            sys.modules[name] = prev
+        elif sys.modules.get(name) is new:                   # an entry we created: removed only while it is still ours
+            del sys.modules[name]
+
+
 def _hit(name, fast):
     stats[name + (".fast" if fast else ".reference")] += 1
     return fast
+
+
+def _outside(message):
+    """A call or configuration outside the gfx950 hot path: raises under `install(strict=True)`; otherwise returns, and the caller
+    hands the call to the reference's own code."""
+    if _state["strict"]:
+        raise NotImplementedError(message)
+
+
+def _dispatcher(ref, name, covered, fast, message):
+    """The function bound in place of `ref` (a function, a method, or the `forward` of a dispatching class): calls that `covered`
+    accepts go to `fast`, the others to `ref` (or raise under strict).  `covered` and `fast` take the reference's arguments."""
+    hit, miss = name + ".fast", name + ".reference"
+
+    def wrapper(*args, **kw):
+        if covered(*args, **kw):
+            stats[hit] += 1
+            return fast(*args, **kw)
+        stats[miss] += 1
+        _outside(message)
+        return ref(*args, **kw)
+
+    wrapper.__name__, wrapper.__doc__, wrapper.__wrapped__ = ref.__name__, ref.__doc__, ref
+    return wrapper
+
+
+def _choosing_class(ref, covered, ours, message=None, doc=None):
+    """The class bound under the name of the reference class `ref`: constructor arguments that `covered` accepts build `ours`
+    (the gfx950 module), the others the reference class (or raise under strict, when there is a `message`).  It subclasses `ref`,
+    so the reference's own `isinstance` / `issubclass` checks keep working."""
+    class Choosing(ref):
+        __doc__ = doc
+
+        def __new__(cls, *args, **kw):
+            if covered(*args, **kw):
+                return ours(*args, **kw)
+            if message:
+                _outside(message)
+            return ref.__new__(cls)
+
+    Choosing.__name__ = Choosing.__qualname__ = ref.__name__
+    return Choosing
 
 
 def _covered(feat, filt, dilation_factors=None):
@@ -83,46 +175,36 @@ def _covered(feat, filt, dilation_factors=None):
     return filt.dim() == 4 and filt.shape[-1] * filt.shape[-2] <= 16
 
 
-def _make_dispatchers(orig_mod, strict):
-    o_apply, o_adj, o_grad = orig_mod.apply_filter, orig_mod.apply_feat_transpose, orig_mod.filter_gradient
+def _install_filter_layer():
+    """`apply_filter` / `apply_feat_transpose` / `filter_gradient`: modules that did `import ltr.models.layers.filter as filter_layer`
+    see the rebinding through the module object; nothing in the hot path does `from ... import apply_filter`."""
+    fmod = importlib.import_module("ltr.models.layers.filter")
 
-    def apply_filter(feat, filter, dilation_factors=None):
-        if _hit("apply_filter", _covered(feat, filter, dilation_factors)):
-            return _filter.apply_filter(feat, filter)
-        if strict:
-            raise NotImplementedError("apply_filter: configuration outside the gfx950 hot path")
-        return o_apply(feat, filter, dilation_factors)
-
-    def apply_feat_transpose(feat, input, filter_ksz, training=True, groups=1):
+    def covered_transpose(feat, input, filter_ksz, training=True, groups=1):
         ksz = (filter_ksz, filter_ksz) if isinstance(filter_ksz, int) else tuple(filter_ksz)
         mf = input.dim() == 5 and input.shape[2] <= 16 and ksz[0] == ksz[1] and ksz[0] in (1, 3) and feat.shape[-1] <= 256
-        if _hit("apply_feat_transpose", feat.is_cuda and feat.dtype == torch.float32 and groups == 1
+        return (feat.is_cuda and feat.dtype == torch.float32 and groups == 1
                 and (mf or (input.dim() == 4 and ksz[0] * ksz[1] <= 16))
-                and not (torch.is_grad_enabled() and feat.requires_grad)):
-            return _filter.apply_feat_transpose(feat, input, ksz, training=training, groups=groups)
-        if strict:
-            raise NotImplementedError("apply_feat_transpose: configuration outside the gfx950 hot path")
-        return o_adj(feat, input, filter_ksz, training=training, groups=groups)
+                and not (torch.is_grad_enabled() and feat.requires_grad))
 
-    def filter_gradient(feat, filter, label=None, training=True):
-        if _hit("filter_gradient", _covered(feat, filter)):
-            return _filter.filter_gradient(feat, filter, label=label, training=training)
-        if strict:
-            raise NotImplementedError("filter_gradient: configuration outside the gfx950 hot path")
-        return o_grad(feat, filter, label=label, training=training)
-
-    for fn, o in ((apply_filter, o_apply), (apply_feat_transpose, o_adj), (filter_gradient, o_grad)):
-        fn.__doc__ = o.__doc__
-        fn.__wrapped__ = o
-    return apply_filter, apply_feat_transpose, filter_gradient
+    for name, covered in (("apply_filter", _covered), ("apply_feat_transpose", covered_transpose),
+                          ("filter_gradient", lambda feat, filter, label=None, training=True: _covered(feat, filter))):
+        _rebind(fmod, name, _dispatcher(getattr(fmod, name), name, covered, getattr(_filter, name),
+                                        name + ": configuration outside the gfx950 hot path"))
 
 
-def _optimizer_class(fused_cls, ref_cls, strict):
+def _optimizer_class(fused_cls, ref_cls):
     """The class bound under the reference's name: the gfx950 module (same parameters, same state_dict keys) whose
     forward runs the fused solver for device tensors under no_grad and hands every other call (CPU tensors, offline
     training with requires_grad inputs, K*K > 16) to the reference class's own forward on the same parameters."""
     import ltr.models.layers.activation as ract
     import ltr.models.layers.distance as rdist
+
+    def covered(self, weights, feat, bb, sample_weight=None, num_iter=None, compute_losses=True):
+        return (feat.is_cuda and weights.is_cuda and feat.dtype == torch.float32
+                and weights.shape[-1] == weights.shape[-2] and weights.shape[-1] ** 2 <= 16
+                and (sample_weight is None or isinstance(sample_weight, torch.Tensor))
+                and not (torch.is_grad_enabled() and (weights.requires_grad or feat.requires_grad)))
 
     class Dispatching(fused_cls):
         __doc__ = ref_cls.__doc__
@@ -139,18 +221,8 @@ def _optimizer_class(fused_cls, ref_cls, strict):
                     self.score_activation = ract.LeakyReluPar()
                     self.score_activation_deriv = ract.LeakyReluParDeriv()
 
-        def forward(self, weights, feat, bb, sample_weight=None, num_iter=None, compute_losses=True):
-            fused = (feat.is_cuda and weights.is_cuda and feat.dtype == torch.float32
-                     and weights.shape[-1] == weights.shape[-2] and weights.shape[-1] ** 2 <= 16
-                     and (sample_weight is None or isinstance(sample_weight, torch.Tensor))
-                     and not (torch.is_grad_enabled() and (weights.requires_grad or feat.requires_grad)))
-            if _hit(ref_cls.__name__, fused):
-                return fused_cls.forward(self, weights, feat, bb, sample_weight=sample_weight, num_iter=num_iter,
-                                         compute_losses=compute_losses)
-            if strict:
-                raise NotImplementedError(f"{ref_cls.__name__}: call outside the gfx950 hot path")
-            return ref_cls.forward(self, weights, feat, bb, sample_weight=sample_weight, num_iter=num_iter,
-                                   compute_losses=compute_losses)
+        forward = _dispatcher(ref_cls.forward, ref_cls.__name__, covered, fused_cls.forward,
+                              f"{ref_cls.__name__}: call outside the gfx950 hot path")
 
     for name, member in vars(ref_cls).items():           # helper methods the reference forward calls (get_label_density ...)
         if callable(member) and not name.startswith("__") and not hasattr(fused_cls, name):
@@ -159,20 +231,25 @@ def _optimizer_class(fused_cls, ref_cls, strict):
     return Dispatching
 
 
-def provide_prroi_module(orig=None):
+def _install_optimizer_classes():
+    omod = importlib.import_module("ltr.models.target_classifier.optimizer")
+    for n in ("DiMPSteepestDescentGN", "DiMPL2SteepestDescentGN", "PrDiMPSteepestDescentNewton"):
+        _rebind(omod, n, _optimizer_class(getattr(_optimizer, n), getattr(omod, n)))
+
+
+def provide_prroi_module():
     """Create `ltr.external.PreciseRoIPooling.pytorch.prroi_pool` (an empty git submodule in the reference) in
     sys.modules so that `from ltr.external.PreciseRoIPooling.pytorch.prroi_pool import PrRoIPool2D`
     (initializer.py:4, atom_iou_net.py:4) resolves to the HIP implementation.  If an implementation was already
     registered under that name (a CPU stand-in in a test harness), CPU tensors keep going to it; modules that imported
-    the class by name before this call are re-pointed."""
+    the class by name before this call are re-pointed.  `uninstall()` undoes it."""
     for pkg in ("ltr.external", "ltr.external.PreciseRoIPooling", "ltr.external.PreciseRoIPooling.pytorch"):
         if pkg not in sys.modules:
             m = types.ModuleType(pkg)
             m.__path__ = []
-            sys.modules[pkg] = m
+            _rebind_module(pkg, m)
     name = "ltr.external.PreciseRoIPooling.pytorch.prroi_pool"
-    prev = sys.modules.get(name)
-    prev_cls = getattr(prev, "PrRoIPool2D", None)
+    prev_cls = getattr(sys.modules.get(name), "PrRoIPool2D", None)
 
     class PrRoIPool2D(_prroi.PrRoIPool2D):
         __doc__ = _prroi.PrRoIPool2D.__doc__
@@ -185,23 +262,17 @@ def provide_prroi_module(orig=None):
     pm = types.ModuleType(name)
     pm.PrRoIPool2D = PrRoIPool2D
     pm.prroi_pool2d = _prroi.prroi_pool2d
-    sys.modules[name] = pm
-    parent = sys.modules["ltr.external.PreciseRoIPooling.pytorch"]
-    prev_attr = getattr(parent, "prroi_pool", None)
-    parent.prroi_pool = pm
-    importers = []
+    _rebind_module(name, pm)
+    _rebind(sys.modules["ltr.external.PreciseRoIPooling.pytorch"], "prroi_pool", pm)
     if prev_cls is not None:
         for modname in ("ltr.models.target_classifier.initializer", "ltr.models.bbreg.atom_iou_net"):
             mod = sys.modules.get(modname)
             if mod is not None and getattr(mod, "PrRoIPool2D", None) is prev_cls:
-                mod.PrRoIPool2D = PrRoIPool2D
-                importers.append((mod, prev_cls))
-    if orig is not None:
-        orig["prroi"] = (name, prev, prev_attr, importers)
+                _rebind(mod, "PrRoIPool2D", PrRoIPool2D)
     return pm
 
 
-def _install_tomp(orig, strict):
+def _install_tomp():
     """ToMP model predictor (inference): the reference's tompnet constructors (ltr/models/tracking/tompnet.py:106-118)
     reach these classes through module attributes, so rebinding the attributes is enough."""
     from . import transformer as _tm
@@ -211,8 +282,6 @@ def _install_tomp(orig, strict):
         hmod = importlib.import_module("ltr.models.transformer.heads")
     except Exception:                   # torchvision (heads.py:3) missing: leave the transformer family alone
         return
-    orig["tomp"] = (tmod.Transformer, pmod.FilterPredictor, hmod.LinearFilterClassifier, hmod.DenseBoxRegressor)
-    ref_tr, ref_fp, ref_cls, ref_reg = orig["tomp"]
 
     def covered(d_model=512, nhead=8, num_encoder_layers=6, num_decoder_layers=6, dim_feedforward=2048, dropout=0.1,
                 activation="relu", normalize_before=False, return_intermediate_dec=False):
@@ -221,39 +290,19 @@ def _install_tomp(orig, strict):
                 and d_model <= 512 and d_model % nhead == 0 and hd in (16, 32, 64) and nhead <= 16
                 and dim_feedforward % 64 == 0 and num_encoder_layers <= 16 and num_decoder_layers <= 16)
 
-    class Transformer(ref_tr):
-        """Covered configuration -> gfx950 parameter container; anything else -> the reference class."""
-
-        def __new__(cls, *args, **kw):
-            if covered(*args, **kw):
-                return _tm.Transformer(*args, **kw)
-            if strict:
-                raise NotImplementedError("Transformer: configuration outside the gfx950 hot path")
-            return ref_tr.__new__(cls)
-
-    class FilterPredictor(ref_fp):
-        def __new__(cls, transformer, *args, **kw):
-            if isinstance(transformer, _tm.Transformer):
-                return _tm.FilterPredictor(transformer, *args, **kw)
-            if strict:
-                raise NotImplementedError("FilterPredictor: transformer outside the gfx950 hot path")
-            return ref_fp.__new__(cls)
-
-    class DenseBoxRegressor(ref_reg):
-        def __new__(cls, num_channels, *args, **kw):
-            if num_channels % 64 == 0 and num_channels <= 512:
-                return _tm.DenseBoxRegressor(num_channels, *args, **kw)
-            if strict:
-                raise NotImplementedError("DenseBoxRegressor: channel count outside the gfx950 hot path")
-            return ref_reg.__new__(cls)
-
-    tmod.Transformer = Transformer
-    pmod.FilterPredictor = FilterPredictor
-    hmod.LinearFilterClassifier = _tm.LinearFilterClassifier
-    hmod.DenseBoxRegressor = DenseBoxRegressor
+    _rebind(tmod, "Transformer", _choosing_class(
+        tmod.Transformer, covered, _tm.Transformer, "Transformer: configuration outside the gfx950 hot path",
+        doc="Covered configuration -> gfx950 parameter container; anything else -> the reference class."))
+    _rebind(pmod, "FilterPredictor", _choosing_class(
+        pmod.FilterPredictor, lambda transformer, *args, **kw: isinstance(transformer, _tm.Transformer), _tm.FilterPredictor,
+        "FilterPredictor: transformer outside the gfx950 hot path"))
+    _rebind(hmod, "LinearFilterClassifier", _tm.LinearFilterClassifier)
+    _rebind(hmod, "DenseBoxRegressor", _choosing_class(
+        hmod.DenseBoxRegressor, lambda num_channels, *args, **kw: num_channels % 64 == 0 and num_channels <= 512,
+        _tm.DenseBoxRegressor, "DenseBoxRegressor: channel count outside the gfx950 hot path"))
 
 
-def _install_clf_head(orig, strict):
+def _install_clf_head():
     """Classification-feature head: `clf_features.residual_bottleneck(...)` is reached through the module attribute by
     every network constructor (dimpnet.py:169, tompnet.py:99).  Covered argument sets build the fused module around the
     reference's own layer objects; on a CPU tensor / in training it runs those layers as `nn.Sequential` would."""
@@ -263,32 +312,28 @@ def _install_clf_head(orig, strict):
     except Exception:                   # torchvision (features.py:4) missing
         return
     ref_fn = fmod.residual_bottleneck
-    orig["clf_head"] = ref_fn
+
+    def fused(self, x):
+        return (x.is_cuda and x.dtype == torch.float32 and not self.training
+                and not (torch.is_grad_enabled() and (x.requires_grad or self[0].weight.requires_grad)))
 
     class ClfHead(_fm.ClfHead):
-        def forward(self, x):
-            fused = (x.is_cuda and x.dtype == torch.float32 and not self.training
-                     and not (torch.is_grad_enabled() and (x.requires_grad or self[0].weight.requires_grad)))
-            if _hit("residual_bottleneck", fused):
-                return _fm.ClfHead.forward(self, x)
-            if strict:
-                raise NotImplementedError("clf feature head: call outside the gfx950 hot path")
-            return torch.nn.Sequential.forward(self, x)
+        forward = _dispatcher(torch.nn.Sequential.forward, "residual_bottleneck", fused, _fm.ClfHead.forward,
+                              "clf feature head: call outside the gfx950 hot path")
 
     def residual_bottleneck(*args, **kw):
         seq = ref_fn(*args, **kw)
         if _fm.covered(*args, **kw) and len(seq) == 2:
             return ClfHead(seq[0], seq[1])                # the reference's Conv2d and InstanceL2Norm objects
-        if strict:
-            raise NotImplementedError("residual_bottleneck: configuration outside the gfx950 hot path")
+        _outside("residual_bottleneck: configuration outside the gfx950 hot path")
         return seq
 
     residual_bottleneck.__doc__ = ref_fn.__doc__
     residual_bottleneck.__wrapped__ = ref_fn
-    fmod.residual_bottleneck = residual_bottleneck
+    _rebind(fmod, "residual_bottleneck", residual_bottleneck)
 
 
-def _install_localization(orig, strict):
+def _install_localization():
     """`dcf.max2d` (function, reached as `dcf.max2d` by the trackers) and the `localize_advanced` methods of DiMP / ToMP:
     one launch + one 32-byte copy per frame instead of ~10 host synchronisations."""
     from . import localization as _loc
@@ -296,41 +341,25 @@ def _install_localization(orig, strict):
         dmod = importlib.import_module("pytracking.libs.dcf")
     except Exception:
         return
-    ref_max2d = dmod.max2d
-    orig["localization"] = {"max2d": ref_max2d}
+    _rebind(dmod, "max2d", _dispatcher(dmod.max2d, "max2d", lambda a: a.is_cuda and a.dtype == torch.float32, _loc.max2d,
+                                       "max2d: tensor outside the gfx950 hot path"))
 
-    def max2d(a):
-        if _hit("max2d", a.is_cuda and a.dtype == torch.float32):
-            return _loc.max2d(a)
-        if strict:
-            raise NotImplementedError("max2d: tensor outside the gfx950 hot path")
-        return ref_max2d(a)
+    def covered(self, scores, sample_pos, sample_scales):
+        return scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 3 and scores.shape[0] <= 8
 
-    max2d.__doc__, max2d.__wrapped__ = ref_max2d.__doc__, ref_max2d
-    dmod.max2d = max2d
-    for modname, clsname, fn in (("pytracking.tracker.dimp.dimp", "DiMP", _loc.localize_advanced),
-                                 ("pytracking.tracker.dimp_simple.dimp_simple", "DiMPSimple", _loc.localize_advanced),   # = DiMP's
-                                 ("pytracking.tracker.keep_track.keep_track", "KeepTrack", _loc.localize_advanced),      # = DiMP's
-                                 ("pytracking.tracker.tomp.tomp", "ToMP", _loc.localize_advanced_tomp)):
+    for modname, clsname, fast in (("pytracking.tracker.dimp.dimp", "DiMP", _loc.localize_advanced),
+                                   ("pytracking.tracker.dimp_simple.dimp_simple", "DiMPSimple", _loc.localize_advanced),   # = DiMP's
+                                   ("pytracking.tracker.keep_track.keep_track", "KeepTrack", _loc.localize_advanced),      # = DiMP's
+                                   ("pytracking.tracker.tomp.tomp", "ToMP", _loc.localize_advanced_tomp)):
         try:
             cls = getattr(importlib.import_module(modname), clsname)
         except Exception:               # tracker module not importable here (cv2 ...): nothing to patch
             continue
-        ref_method = cls.localize_advanced
-        orig["localization"][(modname, clsname)] = ref_method
-
-        def method(self, scores, sample_pos, sample_scales, _fast=fn, _ref=ref_method, _name=clsname + ".localize_advanced"):
-            if _hit(_name, scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 3 and scores.shape[0] <= 8):
-                return _fast(self, scores, sample_pos, sample_scales)
-            if strict:
-                raise NotImplementedError("localize_advanced: scores outside the gfx950 hot path")
-            return _ref(self, scores, sample_pos, sample_scales)
-
-        method.__doc__, method.__wrapped__ = ref_method.__doc__, ref_method
-        cls.localize_advanced = method
+        _rebind(cls, "localize_advanced", _dispatcher(cls.localize_advanced, clsname + ".localize_advanced", covered, fast,
+                                                      "localize_advanced: scores outside the gfx950 hot path"))
 
 
-def _install_iou_refine(orig, strict):
+def _install_iou_refine():
     """`DiMP.optimize_boxes_default` / `optimize_boxes_relative` (dimp.py:725-788): all refinement iterations in one
     device-side sequence instead of one autograd graph per iteration."""
     from . import iou_refine as _ir
@@ -338,10 +367,8 @@ def _install_iou_refine(orig, strict):
         cls = importlib.import_module("pytracking.tracker.dimp.dimp").DiMP
     except Exception:
         return
-    orig["iou_refine"] = [(cls, "optimize_boxes_default", cls.optimize_boxes_default),
-                          (cls, "optimize_boxes_relative", cls.optimize_boxes_relative)]
-    targets = [(cls, "optimize_boxes_default", _ir.optimize_boxes_default, lambda t: t.net.bb_regressor),
-               (cls, "optimize_boxes_relative", _ir.optimize_boxes_relative, lambda t: t.net.bb_regressor)]
+    both = (("optimize_boxes_default", _ir.optimize_boxes_default), ("optimize_boxes_relative", _ir.optimize_boxes_relative))
+    targets = [(cls, name, fast, lambda t: t.net.bb_regressor) for name, fast in both]
     # DiMPSimple's two methods are DiMP's, byte for byte (dimp_simple.py vs dimp.py); KeepTrack's differ from DiMP's in comments and
     # docstrings only (keep_track.py vs dimp.py)
     for modname, clsname in (("pytracking.tracker.dimp_simple.dimp_simple", "DiMPSimple"),
@@ -350,12 +377,9 @@ def _install_iou_refine(orig, strict):
             scls = getattr(importlib.import_module(modname), clsname)
         except Exception:
             continue
-        for name, fast in (("optimize_boxes_default", _ir.optimize_boxes_default), ("optimize_boxes_relative", _ir.optimize_boxes_relative)):
-            orig["iou_refine"].append((scls, name, getattr(scls, name)))
-            targets.append((scls, name, fast, lambda t: t.net.bb_regressor))
+        targets += [(scls, name, fast, lambda t: t.net.bb_regressor) for name, fast in both]
     try:
         acls = importlib.import_module("pytracking.tracker.atom.atom").ATOM
-        orig["iou_refine"].append((acls, "optimize_boxes", acls.optimize_boxes))
         targets.append((acls, "optimize_boxes", _ir.optimize_boxes_atom, lambda t: t.iou_predictor))
     except Exception:
         pass
@@ -372,19 +396,18 @@ def _install_iou_refine(orig, strict):
                     out = _fast(self, feats, init_boxes)
                     _hit(_name, True)
                     return out
-                except NotImplementedError:
-                    if strict:
-                        raise
+                except NotImplementedError as exc:
+                    _outside(str(exc))
             _hit(_name, False)
-            if strict and not ok:
-                raise NotImplementedError(f"{_ref.__name__}: call outside the gfx950 hot path")
+            if not ok:
+                _outside(f"{_ref.__name__}: call outside the gfx950 hot path")
             return _ref(self, iou_features, init_boxes)
 
         method.__doc__, method.__wrapped__ = ref_method.__doc__, ref_method
-        setattr(cls, name, method)
+        _rebind(cls, name, method)
 
 
-def _install_operation(orig, strict):
+def _install_operation():
     """`pytracking.libs.operation.conv2d` (operation.py:6-33; TensorList-lifted): ATOM classifies every frame with
     `operation.conv2d(sample_x, self.filter, mode='same')` (atom.py:300-302).  A single-output-channel 'same'
     correlation on device tensors goes to the gfx950 correlation pass; every other use (full inner products of
@@ -398,7 +421,6 @@ def _install_operation(orig, strict):
     ref_single = getattr(ref_conv2d, "__wrapped__", None)     # functools.wraps keeps the un-lifted function
     if ref_single is None:
         return
-    orig["operation"] = ref_conv2d
 
     def conv2d(input, weight, bias=None, stride=1, padding=0, dilation=1, groups=1, mode=None):
         fused = (weight is not None and mode == 'same' and bias is None and stride == 1 and dilation == 1 and groups == 1
@@ -406,48 +428,49 @@ def _install_operation(orig, strict):
                  and input.dim() == 4 and weight.dim() == 4 and weight.shape[0] == 1 and weight.shape[1] == input.shape[1]
                  and weight.shape[2] * weight.shape[3] <= 16 and weight.is_cuda
                  and not (torch.is_grad_enabled() and (input.requires_grad or weight.requires_grad)))
-        if mode == 'same' and isinstance(input, torch.Tensor) and input.is_cuda:       # the classification call; the 1x1 projection
-            _hit("operation.conv2d[same]", fused)                                       # (mode None) is stock PyTorch by design
+        same_on_device = mode == 'same' and isinstance(input, torch.Tensor) and input.is_cuda
+        if same_on_device:                                    # the classification call; the 1x1 projection (mode None) is stock
+            _hit("operation.conv2d[same]", fused)             # PyTorch by design
         if fused:
             return _filter.corr_raw(input, weight[0], out_hw=tuple(input.shape[-2:])).unsqueeze(1)
-        if strict and isinstance(input, torch.Tensor) and input.is_cuda and mode == 'same':
-            raise NotImplementedError("operation.conv2d(mode='same'): configuration outside the gfx950 hot path")
+        if same_on_device:
+            _outside("operation.conv2d(mode='same'): configuration outside the gfx950 hot path")
         return ref_single(input, weight, bias=bias, stride=stride, padding=padding, dilation=dilation, groups=groups,
                           mode=mode)
 
     conv2d.__doc__ = ref_single.__doc__
     lifted = tl.tensor_operation(conv2d)
     lifted.__wrapped_reference__ = ref_conv2d
-    omod.conv2d = lifted
+    _rebind(omod, "conv2d", lifted)
 
 
-def _install_preprocessing(orig, strict):
+def _install_preprocessing():
     """`sample_patch` / `sample_patch_multiscale` (pytracking/features/preprocessing.py:33-148): for an image tensor that
     lives on the device, crop + replicate padding + bilinear resize become one gather launch.  The reference trackers
     build the image with `numpy_to_torch` on the CPU, so this route is taken when the caller uploads the frame first;
-    CPU images and masks keep the reference's functions; the first-frame augmentation set (`sample_patch_transformed`) runs on
-    the device for the transforms pytracking_amd/preprocessing.py covers and falls back to the reference for the rest."""
+    CPU images and masks keep the reference's functions (also under strict, which refuses device images only); the first-frame
+    augmentation set (`sample_patch_transformed`) runs on the device for the transforms pytracking_amd/preprocessing.py covers and
+    falls back to the reference for the rest."""
     from . import preprocessing as _pp
     try:
         pmod = importlib.import_module("pytracking.features.preprocessing")
     except Exception:
         return
     ref_sp, ref_ms, ref_tr = pmod.sample_patch, pmod.sample_patch_multiscale, pmod.sample_patch_transformed
-    orig["preprocessing"] = {"functions": (ref_sp, ref_ms, ref_tr), "importers": []}
 
     def sample_patch(im, pos, sample_sz, output_sz=None, mode='replicate', max_scale_change=None, is_mask=False):
         if _hit("sample_patch", im.is_cuda and im.dtype == torch.float32 and not is_mask and im.dim() == 4 and im.shape[0] == 1):
             return _pp.sample_patch(im, pos, sample_sz, output_sz, mode=mode, max_scale_change=max_scale_change)
-        if strict and im.is_cuda:
-            raise NotImplementedError("sample_patch: call outside the gfx950 hot path")
+        if im.is_cuda:
+            _outside("sample_patch: call outside the gfx950 hot path")
         return ref_sp(im, pos, sample_sz, output_sz, mode=mode, max_scale_change=max_scale_change, is_mask=is_mask)
 
     def sample_patch_multiscale(im, pos, scales, image_sz, mode='replicate', max_scale_change=None):
         n = 1 if isinstance(scales, (int, float)) else len(scales)
         if _hit("sample_patch_multiscale", im.is_cuda and im.dtype == torch.float32 and im.dim() == 4 and im.shape[0] == 1 and n <= 8):
             return _pp.sample_patch_multiscale(im, pos, scales, image_sz, mode=mode, max_scale_change=max_scale_change)
-        if strict and im.is_cuda:
-            raise NotImplementedError("sample_patch_multiscale: call outside the gfx950 hot path")
+        if im.is_cuda:
+            _outside("sample_patch_multiscale: call outside the gfx950 hot path")
         return ref_ms(im, pos, scales, image_sz, mode=mode, max_scale_change=max_scale_change)
 
     def sample_patch_transformed(im, pos, scale, image_sz, transforms, is_mask=False):
@@ -457,38 +480,34 @@ def _install_preprocessing(orig, strict):
                 out = _pp.sample_patch_transformed(im, pos, scale, image_sz, transforms)
                 _hit("sample_patch_transformed", True)
                 return out
-            except NotImplementedError:                       # a transform the device path does not cover (RandomAffine, ...)
-                if strict:
-                    raise
-        elif strict and im.is_cuda:
-            raise NotImplementedError("sample_patch_transformed: call outside the gfx950 hot path")
+            except NotImplementedError as exc:                # a transform the device path does not cover (RandomAffine, ...)
+                _outside(str(exc))
+        elif im.is_cuda:
+            _outside("sample_patch_transformed: call outside the gfx950 hot path")
         _hit("sample_patch_transformed", False)
         return ref_tr(im, pos, scale, image_sz, transforms, is_mask=is_mask)
 
-    for fn, ref in ((sample_patch, ref_sp), (sample_patch_multiscale, ref_ms), (sample_patch_transformed, ref_tr)):
+    wrappers = (("sample_patch", sample_patch, ref_sp), ("sample_patch_multiscale", sample_patch_multiscale, ref_ms),
+                ("sample_patch_transformed", sample_patch_transformed, ref_tr))
+    for name, fn, ref in wrappers:
         fn.__doc__, fn.__wrapped__ = ref.__doc__, ref
-    pmod.sample_patch, pmod.sample_patch_multiscale = sample_patch, sample_patch_multiscale
-    pmod.sample_patch_transformed = sample_patch_transformed
+        _rebind(pmod, name, fn)
     # the trackers import the names (`from pytracking.features.preprocessing import sample_patch_multiscale, ...`)
     # ... and ATOM reaches them through its feature extractors (`pytracking/features/extractor.py:3,112`)
     for modname in ("pytracking.tracker.dimp.dimp", "pytracking.tracker.dimp_simple.dimp_simple", "pytracking.tracker.keep_track.keep_track",
                     "pytracking.tracker.atom.atom", "pytracking.tracker.tomp.tomp",
                     "pytracking.tracker.kys.kys", "pytracking.tracker.lwl.lwl", "pytracking.features.extractor",
                     "pytracking.features.featurebase"):
-        tmod = sys.modules.get(modname)
-        if tmod is None:
-            try:
-                tmod = importlib.import_module(modname)
-            except Exception:
-                continue
-        for name, fn, ref in (("sample_patch", sample_patch, ref_sp), ("sample_patch_multiscale", sample_patch_multiscale, ref_ms),
-                              ("sample_patch_transformed", sample_patch_transformed, ref_tr)):
+        try:
+            tmod = importlib.import_module(modname)
+        except Exception:
+            continue
+        for name, fn, ref in wrappers:
             if getattr(tmod, name, None) is ref:
-                setattr(tmod, name, fn)
-                orig["preprocessing"]["importers"].append((tmod, name, ref))
+                _rebind(tmod, name, fn)
 
 
-def _install_candidate_matching(orig, strict):
+def _install_candidate_matching():
     """KeepTrack's target-candidate matching (keep_track.py:437-475): `ltr.data.processing_utils.find_local_maxima` (reached as
     `prutils.find_local_maxima`), `DescriptorExtractor.get_descriptors` and `SuperGlue._forward`.  CPU tensors, grad-enabled
     calls, training mode, the bottleneck / input-projection / double-softmax variants, more than 64 candidates on a side and the
@@ -500,42 +519,19 @@ def _install_candidate_matching(orig, strict):
         gmod = importlib.import_module("ltr.models.target_candidate_matching.superglue")
     except Exception:
         return
-    ref_flm, dcls, scls = pmod.find_local_maxima, tmod.DescriptorExtractor, gmod.SuperGlue
-    ref_desc, ref_fwd = dcls.get_descriptors, scls._forward
-    orig["candidate_matching"] = (pmod, ref_flm, dcls, ref_desc, scls, ref_fwd)
-
-    def find_local_maxima(scores, th, ks):
-        if _hit("find_local_maxima", _cm.covered_find_local_maxima(scores, th, ks)):
-            return _cm.find_local_maxima(scores, th, ks)
-        if strict:
-            raise NotImplementedError("find_local_maxima: call outside the gfx950 hot path")
-        return ref_flm(scores, th, ks)
-
-    def get_descriptors(self, x, coords):
-        if _hit("DescriptorExtractor.get_descriptors", _cm.covered_get_descriptors(self, x, coords)):
-            return _cm.get_descriptors(self, x, coords)
-        if strict:
-            raise NotImplementedError("DescriptorExtractor.get_descriptors: call outside the gfx950 hot path")
-        return ref_desc(self, x, coords)
-
-    def _forward(self, data):
-        if _hit("SuperGlue._forward", _cm.covered_match(self, data)):
-            return _cm.match(self, data, checked=True)
-        if strict:
-            raise NotImplementedError("SuperGlue._forward: call outside the gfx950 hot path")
-        return ref_fwd(self, data)
-
-    for fn, ref in ((find_local_maxima, ref_flm), (get_descriptors, ref_desc), (_forward, ref_fwd)):
-        fn.__doc__, fn.__wrapped__ = ref.__doc__, ref
-    pmod.find_local_maxima = find_local_maxima
-    dcls.get_descriptors = get_descriptors
-    scls._forward = _forward
+    for owner, attr, name, covered, fast in (
+            (pmod, "find_local_maxima", "find_local_maxima", _cm.covered_find_local_maxima, _cm.find_local_maxima),
+            (tmod.DescriptorExtractor, "get_descriptors", "DescriptorExtractor.get_descriptors", _cm.covered_get_descriptors,
+             _cm.get_descriptors),
+            (gmod.SuperGlue, "_forward", "SuperGlue._forward", _cm.covered_match, functools.partial(_cm.match, checked=True))):
+        _rebind(owner, attr, _dispatcher(getattr(owner, attr), name, covered, fast, name + ": call outside the gfx950 hot path"))
 
 
-def provide_correlation_sampler(orig=None):
+def provide_correlation_sampler():
     """Register pytracking_amd.kys as `spatial_correlation_sampler` (the CUDA extension ltr/models/kys/cost_volume.py:5 imports; it has
     no ROCm build) when nothing importable is there, so that `import ltr.models.tracking.kysnet` works.  An installed package or a module
-    somebody else registered under that name (a CPU stand-in in a test harness) is left alone."""
+    somebody else registered under that name (a CPU stand-in in a test harness) is left alone.  `uninstall()` removes the entry this
+    call created, and only while it is still this module."""
     import importlib.util
     name = "spatial_correlation_sampler"
     if name in sys.modules:
@@ -547,327 +543,196 @@ def provide_correlation_sampler(orig=None):
     if found:
         return None
     from . import kys as _kys
-    sys.modules[name] = _kys
-    if orig is not None:
-        orig["correlation_sampler"] = name
+    _rebind_module(name, _kys)
     return _kys
 
 
-def _install_kys(orig, strict):
+def _install_kys():
     """KYS (kys.py:314): `PredictorWrapper.predict_response` and `CostVolume.forward`.  CPU tensors, grad-enabled calls, training mode, a
     list of reference frames, conf_measure 'entropy', other channel counts and maps above 20 x 20 keep the reference's code."""
     from . import kys as _kys
-    provide_correlation_sampler(orig)
+    provide_correlation_sampler()
     try:
         wmod = importlib.import_module("ltr.models.kys.predictor_wrapper")
         cmod = importlib.import_module("ltr.models.kys.cost_volume")
     except Exception:
         return
-    wcls, ccls = wmod.PredictorWrapper, cmod.CostVolume
-    ref_pr, ref_cv = wcls.predict_response, ccls.forward
-    orig["kys"] = (wcls, ref_pr, ccls, ref_cv)
 
-    def predict_response(self, data, dimp_thresh=None, output_window=None):
-        if _hit("PredictorWrapper.predict_response", _kys.covered_predict_response(self, data, dimp_thresh, output_window)):
-            return _kys.predict_response(self, data, dimp_thresh, output_window, checked=True)
-        if strict:
-            raise NotImplementedError("PredictorWrapper.predict_response: call outside the gfx950 hot path")
-        return ref_pr(self, data, dimp_thresh, output_window)
-
-    def forward(self, feat1, feat2):
+    def covered_cost_volume(self, feat1, feat2):
         assert feat1.dim() == 4 and feat2.dim() == 4, 'Expect 4 dimensional inputs'
-        if _hit("CostVolume.forward", _kys.covered_cost_volume(self, feat1, feat2)):
-            return _kys.cost_volume_forward(self, feat1, feat2)
-        if strict:
-            raise NotImplementedError("CostVolume.forward: call outside the gfx950 hot path")
-        return ref_cv(self, feat1, feat2)
+        return _kys.covered_cost_volume(self, feat1, feat2)
 
-    for fn, ref in ((predict_response, ref_pr), (forward, ref_cv)):
-        fn.__doc__, fn.__wrapped__ = ref.__doc__, ref
-    wcls.predict_response = predict_response
-    ccls.forward = forward
+    for cls, attr, name, covered, fast in (
+            (wmod.PredictorWrapper, "predict_response", "PredictorWrapper.predict_response", _kys.covered_predict_response,
+             functools.partial(_kys.predict_response, checked=True)),
+            (cmod.CostVolume, "forward", "CostVolume.forward", covered_cost_volume, _kys.cost_volume_forward)):
+        _rebind(cls, attr, _dispatcher(getattr(cls, attr), name, covered, fast, name + ": call outside the gfx950 hot path"))
 
 
-def _install_gn_hinge(orig, strict, smod):
+def _install_gn_hinge():
     """`GNSteepestDescent` on an exact reference `LinearFilterHinge` with parameter_batch_dim=0, residual_batch_dim=1
     (dimpnet.py:236-242, rts_net.py:325-333) -> the fused solver (pytracking_amd.gn_hinge); the residual object stays the reference's.
     CPU tensors, grad-enabled inputs and uncovered shapes run the reference forward (or raise under strict=True).  Does not depend on
     the LWL modules importing."""
     from . import gn_hinge as _gh
-    ref_gn = smod.GNSteepestDescent
-    orig["gn_hinge"] = ref_gn
     try:
+        smod = importlib.import_module("ltr.models.meta.steepestdescent")
         hinge_cls = importlib.import_module("ltr.models.target_classifier.residual_modules").LinearFilterHinge
     except Exception:
         return
+    ref_gn = smod.GNSteepestDescent
 
-    class GNSteepestDescent(ref_gn):
-        """LinearFilterHinge -> fused hinge solver; any other residual module -> the reference class."""
-
-        def __new__(cls, residual_module=None, *args, **kw):
-            if (type(residual_module) is hinge_cls and kw.get("residual_batch_dim", 0) == 1
-                    and kw.get("parameter_batch_dim", 0) == 0):
-                return _FusedHinge(residual_module, *args, **kw)
-            return ref_gn.__new__(cls)
+    def covered(self, meta_parameter, num_iter=None, *args, **kwargs):
+        n_it = self.num_iter if num_iter is None else num_iter
+        return (not args and set(kwargs) <= {"feat", "bb", "train_label", "sample_weight", "is_distractor"}
+                and kwargs.get("is_distractor") is None
+                and _gh.covered(self.residual_module, meta_parameter, dict(kwargs, _num_iter=n_it),
+                                self._parameter_batch_dim, self._residual_batch_dim))
 
     class _FusedHinge(_gh.GNSteepestDescent):
         _compute_loss = ref_gn._compute_loss
         _sqr_norm = ref_gn._sqr_norm
+        forward = _dispatcher(ref_gn.forward, "GNSteepestDescent.hinge", covered, _gh.GNSteepestDescent.forward,
+                              "GNSteepestDescent (hinge residual): call outside the gfx950 hot path")
 
-        def forward(self, meta_parameter, num_iter=None, *args, **kwargs):
-            n_it = self.num_iter if num_iter is None else num_iter
-            fast = (not args and set(kwargs) <= {"feat", "bb", "train_label", "sample_weight", "is_distractor"}
-                    and kwargs.get("is_distractor") is None
-                    and _gh.covered(self.residual_module, meta_parameter, dict(kwargs, _num_iter=n_it),
-                                    self._parameter_batch_dim, self._residual_batch_dim))
-            if _hit("GNSteepestDescent.hinge", fast):
-                return _gh.GNSteepestDescent.forward(self, meta_parameter, num_iter, **kwargs)
-            if strict:
-                raise NotImplementedError("GNSteepestDescent (hinge residual): call outside the gfx950 hot path")
-            return ref_gn.forward(self, meta_parameter, num_iter, *args, **kwargs)
-
-    smod.GNSteepestDescent = GNSteepestDescent
+    _rebind(smod, "GNSteepestDescent", _choosing_class(
+        ref_gn, lambda residual_module=None, *args, **kw: (type(residual_module) is hinge_cls and kw.get("residual_batch_dim", 0) == 1
+                                                            and kw.get("parameter_batch_dim", 0) == 0),
+        _FusedHinge, doc="LinearFilterHinge -> fused hinge solver; any other residual module -> the reference class."))
 
 
-def _install_rts_residual(orig, strict, mirror):
-    """`ltr.models.rts.loss_residual_modules.RTSResidual` (forward identical to LWTLResidual's): undilated -> the LWTL mirror, so that the
-    LWL fused solver (which reads filter_reg through the mirror's scalar cache) takes the RTS segmentation learner."""
+def _install_lwl():
+    """LWL few-shot learner: the residual module is replaced outright (same parameters); the generic optimiser class dispatches on it.
+    The hinge residual (dimp_simple, RTS classifier) is recognised by `_install_gn_hinge`'s class, which this one chains to, and kept as
+    the reference's object; the RTS segmentation residual (RTSResidual, the same forward as LWTLResidual) is replaced by the LWTL mirror
+    like LWTLResidual.  Any other residual module keeps the reference implementation."""
+    try:
+        smod = importlib.import_module("ltr.models.meta.steepestdescent")
+        rmod = importlib.import_module("ltr.models.lwl.loss_residual_modules")
+    except Exception:
+        return
+    ref_gn, ref_res = smod.GNSteepestDescent, rmod.LWTLResidual
+    hinge_new = ref_gn.__new__
+
+    class _ResMirror(_sd.LWTLResidual):
+        # the residual vectors themselves (only the reference's generic forward asks for them): the reference's
+        # own method on the rebound filter layer, so CPU tensors and autograd behave as upstream
+        forward = ref_res.forward
+
+    def covered(self, meta_parameter, num_iter=None, *args, **kwargs):
+        w = meta_parameter[0] if isinstance(meta_parameter, (list, tuple)) else meta_parameter
+        feat = kwargs.get("feat")
+        return (isinstance(feat, torch.Tensor) and feat.is_cuda and w.is_cuda and not args
+                and not (torch.is_grad_enabled() and (w.requires_grad or feat.requires_grad)))
+
+    class _FusedGN(_sd.GNSteepestDescent):
+        _compute_loss = ref_gn._compute_loss
+        _sqr_norm = ref_gn._sqr_norm
+        forward = _dispatcher(ref_gn.forward, "GNSteepestDescent", covered, _sd.GNSteepestDescent.forward,
+                              "GNSteepestDescent: call outside the gfx950 hot path")
+
+    class GNSteepestDescent(ref_gn):
+        """LWTLResidual (gfx950 mirror) at inference -> fused solver; any other residual module, a training call
+        (grad-enabled inputs) or CPU tensors -> the reference class / the reference forward."""
+
+        def __new__(cls, residual_module=None, *args, **kw):
+            if (isinstance(residual_module, _sd.LWTLResidual) and residual_module.filter_dilation_factors is None
+                    and kw.get("residual_batch_dim", 0) == 1 and kw.get("parameter_batch_dim", 0) == 0):
+                return _FusedGN(residual_module, *args, **kw)
+            return hinge_new(cls, residual_module, *args, **kw)
+
+    def undilated(init_filter_reg=1e-2, filter_dilation_factors=None):
+        return filter_dilation_factors is None
+
+    _rebind(rmod, "LWTLResidual", _choosing_class(
+        ref_res, undilated, _ResMirror, "LWTLResidual: dilated filters are outside the gfx950 hot path",
+        doc="No dilation factors -> the gfx950 mirror (same parameter); dilated filters -> the reference class."))
+    _rebind(smod, "GNSteepestDescent", GNSteepestDescent)
+    # `ltr.models.rts.loss_residual_modules.RTSResidual` (forward identical to LWTLResidual's): undilated -> the LWTL mirror, so that the
+    # LWL fused solver (which reads filter_reg through the mirror's scalar cache) takes the RTS segmentation learner
     try:
         rts = importlib.import_module("ltr.models.rts.loss_residual_modules")
     except Exception:
         return
-    ref_rts = getattr(rts, "RTSResidual", None)
-    if ref_rts is None:
+    if hasattr(rts, "RTSResidual"):
+        _rebind(rts, "RTSResidual", _choosing_class(
+            rts.RTSResidual, undilated, _ResMirror, "RTSResidual: dilated filters are outside the gfx950 hot path",
+            doc="No dilation factors -> the gfx950 LWTL mirror (same parameter); dilated filters -> the reference class."))
+
+
+def _install_atom_cg():
+    """ATOM's optimisers (`pytracking.libs.optimization`) and its per-frame classification call (`_install_operation`).  `atom.atom`
+    imports the two classes by name, so its names are re-pointed too."""
+    try:
+        pmod = importlib.import_module("pytracking.libs.optimization")
+        amod = importlib.import_module("pytracking.tracker.atom.optim")
+    except Exception:          # pytracking side not importable (missing cv2 ...): the ltr side is still installed
         return
-    orig["rts_residual"] = (rts, ref_rts)
+    ak = _optimization.activation_kind
 
-    class RTSResidual(ref_rts):
-        """No dilation factors -> the gfx950 LWTL mirror (same parameter); dilated filters -> the reference class."""
+    def covered_cg(problem, variable, *args, **kw):
+        kind = ak(getattr(problem, "response_activation", None))[0]
+        return _hit("ConjugateGradient", (
+            isinstance(problem, amod.ConvProblem) and kind == "mlu" and len(variable) == 1
+            and variable[0].is_cuda and variable[0].shape[-1] == variable[0].shape[-2]
+            and variable[0].shape[-1] ** 2 <= 16 and not kw.get("debug", False)
+            and kw.get("standard_alpha", True) and kw.get("cg_eps", 0.0) == 0.0))
 
-        def __new__(cls, init_filter_reg=1e-2, filter_dilation_factors=None):
-            if filter_dilation_factors is None:
-                return mirror(init_filter_reg, filter_dilation_factors)
-            if strict:
-                raise NotImplementedError("RTSResidual: dilated filters are outside the gfx950 hot path")
-            return ref_rts.__new__(cls)
+    def covered_gn(problem, variable, *args, **kw):
+        return _hit("GaussNewtonCG", (
+            isinstance(problem, amod.FactorizedConvProblem) and len(variable) == 2 and variable[0].is_cuda
+            and ak(getattr(problem, "response_activation", None))[0] == "mlu"
+            and ak(getattr(problem, "projection_activation", None))[0] == "identity"
+            and variable[0].shape[-1] == variable[0].shape[-2] and variable[0].shape[-1] ** 2 <= 16
+            and not any(kw.get(k, False) for k in ("debug", "analyze", "plotting"))
+            and kw.get("standard_alpha", True) and kw.get("cg_eps", 0.0) == 0.0
+            and kw.get("direction_forget_factor", 0) == 0))
 
-    rts.RTSResidual = RTSResidual
+    classes = (
+        ("ConjugateGradient", _choosing_class(
+            pmod.ConjugateGradient, covered_cg, _optimization.ConjugateGradient, "ConjugateGradient: problem outside the gfx950 hot path",
+            doc="ConvProblem + MLU on device -> fused gfx950 CG; any other problem -> the reference class.")),
+        ("GaussNewtonCG", _choosing_class(
+            pmod.GaussNewtonCG, covered_gn, _optimization.GaussNewtonCG, "GaussNewtonCG: problem outside the gfx950 hot path",
+            doc="FactorizedConvProblem, MLU response + identity projection activation, one feature block on device -> fused gfx950 joint "
+                "Gauss-Newton; any other problem -> the reference class.")))
+    for name, cls in classes:
+        _rebind(pmod, name, cls)
+    _install_operation()
+    tmod = sys.modules.get("pytracking.tracker.atom.atom")
+    for name, cls in classes:
+        if tmod is not None and hasattr(tmod, name):
+            _rebind(tmod, name, cls)
 
 
 def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=True, iou_refine=True, preprocessing=True,
             candidate_matching=True, kys=True):
     """Rebind the boundary symbols.  Call after the reference is importable (`sys.path`) and before networks or
-    trackers are constructed.  Idempotent."""
+    trackers are constructed.  Idempotent.  If an installer raises, what was rebound so far is undone before the exception
+    propagates (an optional reference module that does not import is not a failure: its family is skipped)."""
     if _state["installed"]:
         return
-    provide_prroi_module(_state["originals"])                     # must precede `import ltr.models...`
-    fmod = importlib.import_module("ltr.models.layers.filter")
-    omod = importlib.import_module("ltr.models.target_classifier.optimizer")
-    orig = _state["originals"]
-    orig["filter"] = (fmod.apply_filter, fmod.apply_feat_transpose, fmod.filter_gradient)
-    a, t, g = _make_dispatchers(fmod, strict)
-    fmod.apply_filter, fmod.apply_feat_transpose, fmod.filter_gradient = a, t, g
-    # modules that did `import ltr.models.layers.filter as filter_layer` see the rebinding through the module
-    # object; nothing in the hot path does `from ... import apply_filter`.
-    names = ("DiMPSteepestDescentGN", "DiMPL2SteepestDescentGN", "PrDiMPSteepestDescentNewton")
-    orig["optimizer"] = tuple(getattr(omod, n) for n in names)
-    for n in names:
-        setattr(omod, n, _optimizer_class(getattr(_optimizer, n), getattr(omod, n), strict))
-    # LWL few-shot learner: the residual module is replaced outright (same parameters); the generic optimiser class
-    # dispatches on it.  The hinge residual (dimp_simple, RTS classifier) is recognised and kept as the reference's object;
-    # the RTS segmentation residual (RTSResidual, the same forward as LWTLResidual) is replaced by the LWTL mirror like LWTLResidual.
-    # Any other residual module keeps the reference implementation.
+    mark = len(_state["ledger"])
+    _state["strict"] = strict
     try:
-        smod = importlib.import_module("ltr.models.meta.steepestdescent")
-    except Exception:
-        smod = None
-    try:
-        rmod = importlib.import_module("ltr.models.lwl.loss_residual_modules")
-    except Exception:
-        rmod = None
-    if smod is not None:
-        _install_gn_hinge(orig, strict, smod)
-    if rmod is not None and smod is not None:
-        orig["lwl"] = (rmod.LWTLResidual, smod.GNSteepestDescent)
-        ref_gn, ref_res = smod.GNSteepestDescent, rmod.LWTLResidual
-        hinge_new = smod.GNSteepestDescent.__new__
-
-        class LWTLResidual(ref_res):
-            """No dilation factors -> the gfx950 mirror (same parameter); dilated filters -> the reference class."""
-
-            def __new__(cls, init_filter_reg=1e-2, filter_dilation_factors=None):
-                if filter_dilation_factors is None:
-                    return _ResMirror(init_filter_reg, filter_dilation_factors)
-                if strict:
-                    raise NotImplementedError("LWTLResidual: dilated filters are outside the gfx950 hot path")
-                return ref_res.__new__(cls)
-
-        class _ResMirror(_sd.LWTLResidual):
-            # the residual vectors themselves (only the reference's generic forward asks for them): the reference's
-            # own method on the rebound filter layer, so CPU tensors and autograd behave as upstream
-            forward = ref_res.forward
-
-        class GNSteepestDescent(ref_gn):
-            """LWTLResidual (gfx950 mirror) at inference -> fused solver; any other residual module, a training call
-            (grad-enabled inputs) or CPU tensors -> the reference class / the reference forward."""
-
-            def __new__(cls, residual_module=None, *args, **kw):
-                if (isinstance(residual_module, _sd.LWTLResidual) and residual_module.filter_dilation_factors is None
-                        and kw.get("residual_batch_dim", 0) == 1 and kw.get("parameter_batch_dim", 0) == 0):
-                    return _FusedGN(residual_module, *args, **kw)
-                return hinge_new(cls, residual_module, *args, **kw)
-
-        class _FusedGN(_sd.GNSteepestDescent):
-            _compute_loss = ref_gn._compute_loss
-            _sqr_norm = ref_gn._sqr_norm
-
-            def forward(self, meta_parameter, num_iter=None, *args, **kwargs):
-                w = meta_parameter[0] if isinstance(meta_parameter, (list, tuple)) else meta_parameter
-                feat = kwargs.get("feat")
-                fused = (isinstance(feat, torch.Tensor) and feat.is_cuda and w.is_cuda and not args
-                         and not (torch.is_grad_enabled() and (w.requires_grad or feat.requires_grad)))
-                if _hit("GNSteepestDescent", fused):
-                    return _sd.GNSteepestDescent.forward(self, meta_parameter, num_iter, **kwargs)
-                if strict:
-                    raise NotImplementedError("GNSteepestDescent: call outside the gfx950 hot path")
-                return ref_gn.forward(self, meta_parameter, num_iter, *args, **kwargs)
-
-        rmod.LWTLResidual = LWTLResidual
-        smod.GNSteepestDescent = GNSteepestDescent
-        _install_rts_residual(orig, strict, _ResMirror)
-    if tomp:
-        _install_tomp(orig, strict)
-    if clf_head:
-        _install_clf_head(orig, strict)
-    if localization:
-        _install_localization(orig, strict)
-    if iou_refine:
-        _install_iou_refine(orig, strict)
-    if preprocessing:
-        _install_preprocessing(orig, strict)
-    if candidate_matching:
-        _install_candidate_matching(orig, strict)
-    if kys:
-        _install_kys(orig, strict)
-    if atom_cg:
-        try:
-            pmod = importlib.import_module("pytracking.libs.optimization")
-            amod = importlib.import_module("pytracking.tracker.atom.optim")
-        except Exception:          # pytracking side not importable (missing cv2 ...): the ltr side is still installed
-            pmod = amod = None
-        if pmod is not None:
-            orig["cg"] = pmod.ConjugateGradient
-            ref_cg, ref_problem = pmod.ConjugateGradient, amod.ConvProblem
-
-            class ConjugateGradient(ref_cg):
-                """ConvProblem + MLU on device -> fused gfx950 CG; any other problem -> the reference class."""
-
-                def __new__(cls, problem, variable, *args, **kw):
-                    kind = _optimization.activation_kind(getattr(problem, "response_activation", None))[0]
-                    fast = (isinstance(problem, ref_problem) and kind == "mlu" and len(variable) == 1
-                            and variable[0].is_cuda and variable[0].shape[-1] == variable[0].shape[-2]
-                            and variable[0].shape[-1] ** 2 <= 16 and not kw.get("debug", False)
-                            and kw.get("standard_alpha", True) and kw.get("cg_eps", 0.0) == 0.0)
-                    if _hit("ConjugateGradient", fast):
-                        return _optimization.ConjugateGradient(problem, variable, *args, **kw)
-                    if strict:
-                        raise NotImplementedError("ConjugateGradient: problem outside the gfx950 hot path")
-                    return ref_cg.__new__(cls)
-
-            orig["gn"] = pmod.GaussNewtonCG
-            ref_gn_cg, ref_fact = pmod.GaussNewtonCG, amod.FactorizedConvProblem
-
-            class GaussNewtonCG(ref_gn_cg):
-                """FactorizedConvProblem, MLU response + identity projection activation, one feature block on device
-                -> fused gfx950 joint Gauss-Newton; any other problem -> the reference class."""
-
-                def __new__(cls, problem, variable, *args, **kw):
-                    ak = _optimization.activation_kind
-                    fast = (isinstance(problem, ref_fact) and len(variable) == 2 and variable[0].is_cuda
-                            and ak(getattr(problem, "response_activation", None))[0] == "mlu"
-                            and ak(getattr(problem, "projection_activation", None))[0] == "identity"
-                            and variable[0].shape[-1] == variable[0].shape[-2] and variable[0].shape[-1] ** 2 <= 16
-                            and not any(kw.get(k, False) for k in ("debug", "analyze", "plotting"))
-                            and kw.get("standard_alpha", True) and kw.get("cg_eps", 0.0) == 0.0
-                            and kw.get("direction_forget_factor", 0) == 0)
-                    if _hit("GaussNewtonCG", fast):
-                        return _optimization.GaussNewtonCG(problem, variable, *args, **kw)
-                    if strict:
-                        raise NotImplementedError("GaussNewtonCG: problem outside the gfx950 hot path")
-                    return ref_gn_cg.__new__(cls)
-
-            pmod.ConjugateGradient = ConjugateGradient
-            pmod.GaussNewtonCG = GaussNewtonCG
-            _install_operation(orig, strict)
-            tmod = sys.modules.get("pytracking.tracker.atom.atom")
-            if tmod is not None and hasattr(tmod, "ConjugateGradient"):
-                tmod.ConjugateGradient = ConjugateGradient
-            if tmod is not None and hasattr(tmod, "GaussNewtonCG"):
-                tmod.GaussNewtonCG = GaussNewtonCG
+        provide_prroi_module()                                # must precede `import ltr.models...`
+        _install_filter_layer()
+        _install_optimizer_classes()
+        _install_gn_hinge()
+        _install_lwl()                                        # chains to the hinge class: after _install_gn_hinge
+        # in this order: iou_refine imports `atom.atom` before _install_atom_cg re-points the names it imported
+        for flag, installer in ((tomp, _install_tomp), (clf_head, _install_clf_head), (localization, _install_localization),
+                                (iou_refine, _install_iou_refine), (preprocessing, _install_preprocessing),
+                                (candidate_matching, _install_candidate_matching), (kys, _install_kys), (atom_cg, _install_atom_cg)):
+            if flag:
+                installer()
+    except BaseException:
+        _replay(mark)
+        raise
     _state["installed"] = True
 
 
 def uninstall():
-    if not _state["installed"]:
-        return
-    orig = _state["originals"]
-    fmod = importlib.import_module("ltr.models.layers.filter")
-    omod = importlib.import_module("ltr.models.target_classifier.optimizer")
-    fmod.apply_filter, fmod.apply_feat_transpose, fmod.filter_gradient = orig["filter"]
-    for n, c in zip(("DiMPSteepestDescentGN", "DiMPL2SteepestDescentGN", "PrDiMPSteepestDescentNewton"), orig["optimizer"]):
-        setattr(omod, n, c)
-    if "cg" in orig:
-        importlib.import_module("pytracking.libs.optimization").ConjugateGradient = orig["cg"]
-    if "gn" in orig:
-        importlib.import_module("pytracking.libs.optimization").GaussNewtonCG = orig["gn"]
-    if "operation" in orig:
-        importlib.import_module("pytracking.libs.operation").conv2d = orig["operation"]
-    if "tomp" in orig:
-        importlib.import_module("ltr.models.transformer.transformer").Transformer = orig["tomp"][0]
-        importlib.import_module("ltr.models.transformer.filter_predictor").FilterPredictor = orig["tomp"][1]
-        hm = importlib.import_module("ltr.models.transformer.heads")
-        hm.LinearFilterClassifier, hm.DenseBoxRegressor = orig["tomp"][2], orig["tomp"][3]
-    if "clf_head" in orig:
-        importlib.import_module("ltr.models.target_classifier.features").residual_bottleneck = orig["clf_head"]
-    if "iou_refine" in orig:
-        for cls, name, ref in orig["iou_refine"]:
-            setattr(cls, name, ref)
-    if "localization" in orig:
-        for key, ref in orig["localization"].items():
-            if key == "max2d":
-                importlib.import_module("pytracking.libs.dcf").max2d = ref
-            else:
-                getattr(importlib.import_module(key[0]), key[1]).localize_advanced = ref
-    if "prroi" in orig:
-        name, prev, prev_attr, importers = orig["prroi"]
-        if prev is not None:
-            sys.modules[name] = prev
-        else:
-            sys.modules.pop(name, None)
-        if prev_attr is not None:
-            sys.modules["ltr.external.PreciseRoIPooling.pytorch"].prroi_pool = prev_attr
-        for mod, cls in importers:
-            mod.PrRoIPool2D = cls
-    if "preprocessing" in orig:
-        pm = importlib.import_module("pytracking.features.preprocessing")
-        pm.sample_patch, pm.sample_patch_multiscale, pm.sample_patch_transformed = orig["preprocessing"]["functions"]
-        for tmod, name, ref in orig["preprocessing"]["importers"]:
-            setattr(tmod, name, ref)
-    if "rts_residual" in orig:
-        orig["rts_residual"][0].RTSResidual = orig["rts_residual"][1]
-    if "lwl" in orig:
-        importlib.import_module("ltr.models.lwl.loss_residual_modules").LWTLResidual = orig["lwl"][0]
-    if "gn_hinge" in orig:
-        importlib.import_module("ltr.models.meta.steepestdescent").GNSteepestDescent = orig["gn_hinge"]
-    if "candidate_matching" in orig:
-        pmod, ref_flm, dcls, ref_desc, scls, ref_fwd = orig["candidate_matching"]
-        pmod.find_local_maxima, dcls.get_descriptors, scls._forward = ref_flm, ref_desc, ref_fwd
-    if "kys" in orig:
-        wcls, ref_pr, ccls, ref_cv = orig["kys"]
-        wcls.predict_response, ccls.forward = ref_pr, ref_cv
-    if "correlation_sampler" in orig:                      # only the entry install() created
-        from . import kys as _kys
-        if sys.modules.get(orig["correlation_sampler"]) is _kys:
-            del sys.modules[orig["correlation_sampler"]]
+    """Restore every binding the ledger holds, last first: an `install()`, and a `provide_*` call made on its own."""
+    _replay()
     _state["installed"] = False
-    orig.clear()

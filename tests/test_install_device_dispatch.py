@@ -121,3 +121,38 @@ def test_patch_sampling_and_max2d_on_device(installed):
     v, i = dcf.max2d(a.cuda())
     assert torch.equal(v.cpu(), v_ref) and torch.equal(i.cpu(), i_ref)
     assert amd.stats["sample_patch.fast"] >= 1 and amd.stats["sample_patch_multiscale.fast"] == 1 and amd.stats["max2d.fast"] == 1
+
+
+def test_strict_mode_on_device():
+    """install(strict=True), the smallest shapes that take each branch: a covered device call runs the gfx950 path, an uncovered one
+    raises and is counted as handed back; the patch samplers refuse device images only."""
+    ref_harness.install()
+    from pytracking_amd import install as amd
+    import ltr.models.layers.filter as fl
+    import pytracking.features.preprocessing as pp
+    ref_apply, ref_sample = fl.apply_filter, pp.sample_patch
+    g = torch.Generator().manual_seed(7)
+    feat = torch.randn(2, 1, 16, 6, 6, generator=g)
+    f4, f5 = torch.randn(1, 16, 4, 4, generator=g) * 0.1, torch.randn(1, 16, 5, 5, generator=g) * 0.1
+    im = (torch.rand(1, 3, 24, 32, generator=g) * 255).float()
+    pos, sz = torch.Tensor([12.0, 16.0]), torch.Tensor([16.0, 16.0])
+    amd.install(strict=True)
+    amd.stats.clear()
+    try:
+        with torch.no_grad():
+            s = fl.apply_filter(feat.cuda(), f4.cuda())
+        _close(s, ref_apply(feat, f4), 2e-6, scaled=True)
+        assert dict(amd.stats) == {"apply_filter.fast": 1}
+        with pytest.raises(NotImplementedError) as exc, torch.no_grad():
+            fl.apply_filter(feat.cuda(), f5.cuda())                   # 25 taps > 16
+        assert str(exc.value) == "apply_filter: configuration outside the gfx950 hot path"
+        assert dict(amd.stats) == {"apply_filter.fast": 1, "apply_filter.reference": 1}
+        with pytest.raises(NotImplementedError) as exc:
+            pp.sample_patch(im.cuda(), pos, sz, is_mask=True)
+        assert str(exc.value) == "sample_patch: call outside the gfx950 hot path"
+        got, got_c = pp.sample_patch(im, pos, sz, is_mask=True)       # the CPU copy: the reference's own function
+        want, want_c = ref_sample(im, pos, sz, is_mask=True)
+        assert torch.equal(got, want) and torch.equal(got_c, want_c)
+        assert amd.stats["sample_patch.reference"] == 2 and amd.stats["sample_patch.fast"] == 0
+    finally:
+        amd.uninstall()

@@ -36,7 +36,7 @@ def test_install_rebinds_boundary_symbols_and_restores():
         mine.load_state_dict(ref_mod.state_dict(), strict=True)
         torch.testing.assert_close(mine.label_map_predictor.weight, ref_mod.label_map_predictor.weight)
         import pytracking.libs.optimization as po
-        assert po.ConjugateGradient is not amd._state["originals"]["cg"]
+        assert po.ConjugateGradient is not amd.original(po, "ConjugateGradient")
     finally:
         amd.uninstall()
         if saved_prroi is not None:
@@ -201,7 +201,7 @@ def test_installed_optimizers_fall_back_to_the_reference_forward_off_the_hot_pat
                            TensorList([torch.ones(2)]), activation.MLU(0.05))
         cg = po.ConjugateGradient(prob, TensorList([torch.zeros(1, 4, 2, 4)]), fletcher_reeves=False)
         from pytracking_amd import optimization as OM
-        assert not isinstance(cg, OM.ConjugateGradient) and isinstance(cg, amd._state["originals"]["cg"])
+        assert not isinstance(cg, OM.ConjugateGradient) and isinstance(cg, amd.original(po, "ConjugateGradient"))
         # TensorList with more than one feature block (multi-resolution ATOM): the fused path takes single-block
         # problems only, so such a variable gets the reference class
         prob2 = ConvProblem(TensorList([torch.zeros(2, 4, 6, 6)] * 2), TensorList([torch.zeros(2, 1, 6, 6)] * 2),
