@@ -700,6 +700,33 @@ int pt_kys_predict_response_f32(const pt_kys_predict_params* p, const float* wei
                                 float* propagation_conf, float* fused_score_orig, float* is_target, float* is_target_after_prop,
                                 float* is_target_new, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * IoU feature extraction -- AtomIoUNet.get_iou_feat (ltr/models/bbreg/atom_iou_net.py:172-179), iou_feat.hip.
+ *
+ *   c3_out (n, Cout3, H3, W3) = conv3_2t(conv3_1t(feat3)),  c4_out (n, Cout4, H4, W4) = conv4_2t(conv4_1t(feat4));
+ *   every block = Conv2d(3x3, stride 1, padding 1, bias) -> BatchNorm2d in eval mode -> ReLU (atom_iou_net.py:7-12).
+ *   feat3 (n, Cin3, H3, W3), feat4 (n, Cin4, H4, W4), fp32, contiguous; the two maps need not be related.
+ *   fp32 MFMA with fp32 accumulation; the channel-split partial maps are summed in a fixed order: repeated calls are bit-identical.
+ *   Six launches on the banded-correlation route (per layer: one correlation per tower, one epilogue for both towers); a layer whose
+ *   rows are wider than the banded kernel takes (W > 170) goes through the per-tap split-K GEMM like pt_clf_head_f32.
+ *
+ * `pack` (pt_iou_feat_pack_floats floats, 16-byte aligned), the four blocks in the order conv3_1t, conv3_2t, conv4_1t, conv4_2t, per
+ *   block:  weight (Cout, 3, 3, Cin) tap-major = Conv2d.weight.permute(0, 2, 3, 1), as for pt_clf_head_f32
+ *           scale  (Cout) = bn.weight / sqrt(bn.running_var + bn.eps)
+ *           shift  (Cout) = (conv.bias - bn.running_mean) * scale + bn.bias
+ *   and a block computes relu(conv_without_bias(x) * scale + shift): BatchNorm is NOT folded into the weights.
+ *
+ * Covered: Cin % 64 == 0, Cmid % 16 == 0, Cout % 16 == 0 (each <= 4096), H * W <= 4096, n <= 8, operands 16-byte aligned.
+ * Status: NULL pointer PT_ERR_NULL, non-positive size PT_ERR_SHAPE, uncovered shape / misaligned operand PT_ERR_UNSUPPORTED,
+ * workspace too small or not 256-byte aligned PT_ERR_WORKSPACE -- all before anything is queued.  pt_iou_feat_ws_bytes and
+ * pt_iou_feat_pack_floats return 0 for sizes that are not covered.
+ * ---------------------------------------------------------------------------------------------- */
+size_t pt_iou_feat_pack_floats(int Cin3, int Cmid3, int Cout3, int Cin4, int Cmid4, int Cout4);
+size_t pt_iou_feat_ws_bytes(int n, int Cin3, int Cmid3, int Cout3, int H3, int W3, int Cin4, int Cmid4, int Cout4, int H4, int W4);
+int pt_iou_feat_f32(const float* feat3, const float* feat4, const float* pack, float* c3_out, float* c4_out, int n, int Cin3,
+                    int Cmid3, int Cout3, int H3, int W3, int Cin4, int Cmid4, int Cout4, int H4, int W4, void* ws, size_t ws_bytes,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

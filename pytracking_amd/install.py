@@ -38,6 +38,8 @@ What gets rebound (import path = contract; nothing in the reference tree is edit
   pytracking.tracker.dimp.dimp.DiMP.optimize_boxes_default / optimize_boxes_relative (and DiMPSimple's, KeepTrack's),
   pytracking.tracker.atom.atom.ATOM.optimize_boxes                                    (IoU-guided box refinement)
                                                                                       -> pytracking_amd.iou_refine
+  ltr.models.bbreg.atom_iou_net.AtomIoUNet.get_iou_feat  (both IoU feature towers; only with install(iou_feat=True))
+                                                                                      -> pytracking_amd.iou_feat
 
 Dispatch rule of the rebound *functions*: device fp32 tensors of a shape the gfx950 kernels cover go to the C ABI;
 everything else (CPU tensors, dilations, grouped filters, K*K > 16, more than 16 filters) is outside the hot path and
@@ -569,6 +571,20 @@ def _install_kys():
         _rebind(cls, attr, _dispatcher(getattr(cls, attr), name, covered, fast, name + ": call outside the gfx950 hot path"))
 
 
+def _install_iou_feat():
+    """`AtomIoUNet.get_iou_feat` (atom_iou_net.py:172-179): both towers of two Conv2d + BatchNorm2d + ReLU blocks in one call.  CPU
+    tensors, training mode, grad-enabled calls, blocks of another structure (dilation ...) and uncovered shapes keep the reference's code.
+    Off unless `install(iou_feat=True)`: the set a default install() rebinds is pinned."""
+    from . import iou_feat as _if
+    try:
+        cls = importlib.import_module("ltr.models.bbreg.atom_iou_net").AtomIoUNet
+    except Exception:
+        return
+    name = "AtomIoUNet.get_iou_feat"
+    _rebind(cls, "get_iou_feat", _dispatcher(cls.get_iou_feat, name, _if.covered, functools.partial(_if.get_iou_feat, checked=True),
+                                             name + ": call outside the gfx950 hot path"))
+
+
 def _install_gn_hinge():
     """`GNSteepestDescent` on an exact reference `LinearFilterHinge` with parameter_batch_dim=0, residual_batch_dim=1
     (dimpnet.py:236-242, rts_net.py:325-333) -> the fused solver (pytracking_amd.gn_hinge); the residual object stays the reference's.
@@ -706,7 +722,7 @@ def _install_atom_cg():
 
 
 def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=True, iou_refine=True, preprocessing=True,
-            candidate_matching=True, kys=True):
+            candidate_matching=True, kys=True, iou_feat=False):
     """Rebind the boundary symbols.  Call after the reference is importable (`sys.path`) and before networks or
     trackers are constructed.  Idempotent.  If an installer raises, what was rebound so far is undone before the exception
     propagates (an optional reference module that does not import is not a failure: its family is skipped)."""
@@ -723,7 +739,8 @@ def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=T
         # in this order: iou_refine imports `atom.atom` before _install_atom_cg re-points the names it imported
         for flag, installer in ((tomp, _install_tomp), (clf_head, _install_clf_head), (localization, _install_localization),
                                 (iou_refine, _install_iou_refine), (preprocessing, _install_preprocessing),
-                                (candidate_matching, _install_candidate_matching), (kys, _install_kys), (atom_cg, _install_atom_cg)):
+                                (candidate_matching, _install_candidate_matching), (kys, _install_kys), (atom_cg, _install_atom_cg),
+                                (iou_feat, _install_iou_feat)):
             if flag:
                 installer()
     except BaseException:

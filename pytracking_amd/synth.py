@@ -508,3 +508,41 @@ def kys_frame_inputs(seed, B, H, W, state_dim=8):
     win = (0.5 - 0.5 * np.cos(2 * np.pi * (y + 1) / (H + 1))) * (0.5 - 0.5 * np.cos(2 * np.pi * (x + 1) / (W + 1)))
     return dict(dimp_score_cur=score.astype(np.float32), label_prev=label.astype(np.float32), state_prev=state.astype(np.float32),
                 window=win[None].astype(np.float32))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# IoU feature extraction (ltr/models/bbreg/atom_iou_net.py:172-179): the four test-branch blocks and their backbone inputs
+IOU_FEAT_CASES = {   # name: (n, (Cin3, Cmid3, Cout3, H3, W3), (Cin4, Cmid4, Cout4, H4, W4))
+    "a": (1, (64, 16, 16, 1, 1), (64, 16, 16, 1, 1)),
+    "b": (2, (64, 32, 16, 5, 7), (128, 16, 32, 3, 2)),
+    "c": (1, (128, 48, 32, 11, 13), (64, 32, 48, 9, 4)),
+    "d": (3, (64, 16, 16, 4, 33), (64, 16, 16, 33, 4)),
+    "wide": (1, (64, 16, 16, 2, 172), (64, 64, 16, 1, 200)),      # rows wider than a band of the correlation kernel: the GEMM route
+    "dimp50": (1, (512, 256, 256, 36, 36), (1024, 256, 256, 18, 18)),
+    "prdimp50": (1, (512, 256, 256, 44, 44), (1024, 256, 256, 22, 22)),
+    "atom18": (1, (128, 256, 256, 36, 36), (256, 256, 256, 18, 18)),
+}
+
+
+def iou_feat_state(seed, cin3, cin4, cmid3=256, cout3=256, cmid4=256, cout4=256):
+    """A state dict (numpy, float32) for conv3_1t, conv3_2t, conv4_1t, conv4_2t of an AtomIoUNet: kaiming (fan-in) weights, non-zero
+    biases, and BatchNorm gains, shifts and running statistics away from their defaults so that the epilogue constants are exercised."""
+    rng = np.random.default_rng(seed)
+    sd = {}
+    for name, i, o in (("conv3_1t", cin3, cmid3), ("conv3_2t", cmid3, cout3), ("conv4_1t", cin4, cmid4), ("conv4_2t", cmid4, cout4)):
+        sd[name + ".0.weight"] = (rng.standard_normal((o, i, 3, 3), dtype=np.float32) * np.float32(np.sqrt(2.0 / (9 * i)))).astype(np.float32)
+        sd[name + ".0.bias"] = (rng.standard_normal(o, dtype=np.float32) * np.float32(0.1)).astype(np.float32)
+        sd[name + ".1.weight"] = rng.uniform(0.5, 1.5, o).astype(np.float32)
+        sd[name + ".1.bias"] = (rng.standard_normal(o) * 0.1).astype(np.float32)
+        sd[name + ".1.running_mean"] = (rng.standard_normal(o) * 0.2).astype(np.float32)
+        sd[name + ".1.running_var"] = rng.uniform(0.5, 2.0, o).astype(np.float32)
+        sd[name + ".1.num_batches_tracked"] = np.array(100, dtype=np.int64)
+    return sd
+
+
+def iou_feat_inputs(seed, n, cin3, h3, w3, cin4, h4, w4):
+    """(layer2 (n, cin3, h3, w3), layer3 (n, cin4, h4, w4)): non-negative maps, as the outputs of ResNet blocks are."""
+    rng = np.random.default_rng(seed)
+    f3 = np.maximum(rng.standard_normal((n, cin3, h3, w3), dtype=np.float32), 0.0).astype(np.float32)
+    f4 = np.maximum(rng.standard_normal((n, cin4, h4, w4), dtype=np.float32), 0.0).astype(np.float32)
+    return f3, f4
