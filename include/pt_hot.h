@@ -727,6 +727,13 @@ int pt_iou_feat_f32(const float* feat3, const float* feat4, const float* pack, f
                     int Cmid3, int Cout3, int H3, int W3, int Cin4, int Cmid4, int Cout4, int H4, int W4, void* ws, size_t ws_bytes,
                     void* stream);
 
+/* The geometry the banded tap-major 3x3 correlation (the convolutions of pt_clf_head_f32 and pt_iou_feat_f32) would run for n images,
+ * Ftot filters (% 16), C input channels (% 16) on H x W maps.  Host only: launches nothing, touches no device.
+ *   out[0..5] = ks (channel splits), br (rows per band), npg (4: 8 waves, 6: 12 waves), nb (bands), rows of the last band, Wp (LDS row).
+ * PT_ERR_UNSUPPORTED with out zeroed when the banded kernel does not cover the shape (the callers then take their GEMM route);
+ * PT_ERR_NULL for a null `out`. */
+int pt_mf_corr_tm_plan(int n, int Ftot, int C, int H, int W, int* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,7 +97,7 @@ EXPORTS = [
     "pt_tcm_peaks_f32", "pt_tcm_desc_ws_bytes", "pt_tcm_desc_f32",
     "pt_tcm_match_weight_floats", "pt_tcm_match_ws_bytes", "pt_tcm_match_f32",
     "pt_kys_cost_volume_ws_bytes", "pt_kys_cost_volume_f32", "pt_kys_weight_floats", "pt_kys_predict_ws_bytes", "pt_kys_predict_response_f32",
-    "pt_iou_feat_pack_floats", "pt_iou_feat_ws_bytes", "pt_iou_feat_f32",
+    "pt_iou_feat_pack_floats", "pt_iou_feat_ws_bytes", "pt_iou_feat_f32", "pt_mf_corr_tm_plan",
 ]
 
 PT_TCM_MAX_POINTS, PT_TCM_MAX_LAYERS = 64, 32       # include/pt_hot.h
@@ -397,6 +397,8 @@ def lib():
     L.pt_iou_feat_ws_bytes.argtypes = [i] * 11
     L.pt_iou_feat_f32.restype = i
     L.pt_iou_feat_f32.argtypes = [vp] * 5 + [i] * 11 + [vp, sz, vp]
+    L.pt_mf_corr_tm_plan.restype = i
+    L.pt_mf_corr_tm_plan.argtypes = [i] * 5 + [ctypes.POINTER(ctypes.c_int)]
     L.pt_sample_patch_f32.restype = i
     L.pt_sample_patch_f32.argtypes = [vp, i, i, i, ctypes.POINTER(PatchGeom), i, vp, i, i, vp]
     L.pt_augment_patches_f32.restype = i

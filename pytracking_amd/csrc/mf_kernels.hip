@@ -984,6 +984,20 @@ int pt_mf_corr_tm_splits(int n, int Ftot, int C, int H, int W) {
     if (ks == 0 || br == 0 || !mf_plan(n, 16, C, H, W, 3, br, npg).ok) return 0;
     return ks;
 }
+// The plan pt_launch_mf_corr_tm would run, host only (nothing is launched, no device is touched): out = {ks, br, npg, nb, rows of the
+// last band, Wp}.  PT_ERR_UNSUPPORTED with out all zero exactly when pt_mf_corr_tm_splits() returns 0.  The staging width and the store
+// mode are the launcher's choice from the pointers (mf_vec_width), not part of the plan.
+extern "C" int pt_mf_corr_tm_plan(int n, int Ftot, int C, int H, int W, int* out) {
+    if (!out) return PT_ERR_NULL;
+    for (int k = 0; k < 6; ++k) out[k] = 0;
+    int br = 0, npg = 4;
+    const int ks = mf_tm_config(n, Ftot, C, H, W, &br, &npg);
+    if (ks == 0 || br == 0) return PT_ERR_UNSUPPORTED;
+    const MfPlan p = mf_plan(n, 16, C, H, W, 3, br, npg);
+    if (!p.ok) return PT_ERR_UNSUPPORTED;
+    out[0] = ks; out[1] = p.g.BR; out[2] = npg; out[3] = p.g.NB; out[4] = H - (p.g.NB - 1) * p.g.BR; out[5] = p.g.Wp;
+    return PT_OK;
+}
 // what the shape costs on this launcher, in chunk times of the 8-wave kernel (~2.7 us each on an 18x18 map), fixed part included
 int pt_mf_corr_tm_cost(int n, int Ftot, int C, int H, int W) {
     int br = 0, npg = 4;

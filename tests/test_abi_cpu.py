@@ -115,6 +115,11 @@ def test_clf_head_argument_checks(L):
     assert L.pt_clf_head_f32(one, one, one, 0, 1024, 512, 18, 18, 1.0, 1e-5, one, 1 << 30, n) == -2
     assert L.pt_clf_head_f32(one, one, one, 1, 1000, 512, 18, 18, 1.0, 1e-5, one, 1 << 30, n) == -3
     assert L.pt_clf_head_f32(one, one, one, 1, 1024, 512, 18, 18, 1.0, 1e-5, one, 0, n) == -4
+    # the plan query of the head's banded correlation: host only, {ks, br, npg, nb, rows of the last band, Wp}
+    out = (ctypes.c_int * 6)()
+    assert L.pt_mf_corr_tm_plan(1, 512, 1024, 18, 18, n) == -1
+    assert L.pt_mf_corr_tm_plan(1, 512, 1024, 18, 18, out) == 0 and out[0] >= 1 and out[1] * out[3] >= 18 and out[5] == 20
+    assert L.pt_mf_corr_tm_plan(1, 512, 1000, 18, 18, out) == -3 and list(out) == [0] * 6
 
 
 def test_localize_argument_checks(L):
