@@ -734,6 +734,40 @@ int pt_iou_feat_f32(const float* feat3, const float* feat4, const float* pack, f
  * PT_ERR_NULL for a null `out`. */
 int pt_mf_corr_tm_plan(int n, int Ftot, int C, int H, int W, int* out);
 
+/* ------------------------------------------------------------------------------------------------
+ * Mask label encoder -- ResidualDS16SW.forward (ltr/models/lwl/label_encoder.py:9-55, ltr/models/rts/label_encoder.py:9-55),
+ * label_enc.hip.  LWL and RTS run it on every stored mask on every frame (lwl.py:560-564, rts.py:688).
+ *
+ *   x (n,1,H,W) -> conv3x3 s2 p1 (1->c0) [BN] ReLU -> maxpool3x3 s2 p1 -> BasicBlock(c0->c1, s2) -> BasicBlock(c1->c2, s2)
+ *               -> label_enc (n,f,h,w) = relu([BN](conv3x3(c2->f)))  and  sample_w (n,f,h,w) = conv3x3(c2->f);
+ *   BasicBlock(x) = relu([bn2](conv2(relu([bn1](conv1 x)))) + downsample(x)), conv1 and downsample 3x3 stride 2 (downsample with bias).
+ *   Each of the four stride-2 stages maps a size i to (i - 1) / 2 + 1 (integer division); h, w are H, W after all four.
+ *   masks (n, H, W) fp32 contiguous.  fp32 throughout: the stem on the vector ALU with the pooled convolution outputs kept on chip, every
+ *   other convolution on the exact fp32 MFMA; no atomics and no split sums, so repeated calls are bit-identical.  Six launches.
+ *
+ * `pack` (pt_label_enc_pack_floats floats, 16-byte aligned): six layers in the order
+ *       stem                      Cout = c0,   Cin = 1
+ *       res1.conv1 | downsample   Cout = 2 c1, Cin = c0    (conv1's c1 output channels first, then the downsample's)
+ *       res1.conv2                Cout = c1,   Cin = c1
+ *       res2.conv1 | downsample   Cout = 2 c2, Cin = c1
+ *       res2.conv2                Cout = c2,   Cin = c2
+ *       label_pred | samp_w_pred  Cout = 2 f,  Cin = c2    (label_pred's f output channels first)
+ *   per layer:  weight (Cout, 3, 3, Cin) tap-major = Conv2d.weight.permute(0, 2, 3, 1)
+ *               scale  (Cout)   1, or bn.weight / sqrt(bn.running_var + bn.eps) where a BatchNorm follows the convolution
+ *               shift  (Cout)   the convolution's bias (0 without one), or (bias - bn.running_mean) * scale + bn.bias
+ *   and a layer computes conv_without_bias(x) * scale + shift; BatchNorm is NOT folded into the weights.  ReLU follows the stem, the conv1
+ *   half of a block's first layer, conv2 + residual (the residual is the downsample half, added behind scale / shift) and label_pred.
+ *
+ * Covered: c0, c1, c2, f multiples of 16 up to 64; H, W <= 8192; n <= 65535; pack 16-byte aligned.
+ * Status: NULL pointer PT_ERR_NULL, non-positive size PT_ERR_SHAPE, uncovered size / misaligned pack PT_ERR_UNSUPPORTED, workspace too
+ * small or not 256-byte aligned PT_ERR_WORKSPACE -- all before anything is queued.  pt_label_enc_ws_bytes and pt_label_enc_pack_floats
+ * return 0 for sizes that are not covered.
+ * ---------------------------------------------------------------------------------------------- */
+size_t pt_label_enc_pack_floats(int c0, int c1, int c2, int f);
+size_t pt_label_enc_ws_bytes(int n, int H, int W, int c0, int c1, int c2, int f);
+int pt_label_enc_f32(const float* masks, const float* pack, float* label_enc, float* sample_w, int n, int H, int W, int c0, int c1,
+                     int c2, int f, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

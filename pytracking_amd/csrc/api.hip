@@ -404,3 +404,15 @@ extern "C" int pt_stream_probe_f32(const float* mem, size_t floats, float* scrat
     PT_CHECK_LAUNCH();
     return PT_OK;
 }
+
+// mask label encoder: ResidualDS16SW.forward (label_enc.hip)
+extern "C" size_t pt_label_enc_pack_floats(int c0, int c1, int c2, int f) { return pt_label_enc_pack_floats_impl(c0, c1, c2, f); }
+
+extern "C" size_t pt_label_enc_ws_bytes(int n, int H, int W, int c0, int c1, int c2, int f) {
+    return pt_label_enc_ws_bytes_impl(n, H, W, c0, c1, c2, f);
+}
+
+extern "C" int pt_label_enc_f32(const float* masks, const float* pack, float* label_enc, float* sample_w, int n, int H, int W, int c0,
+                                int c1, int c2, int f, void* ws, size_t ws_bytes, void* stream) {
+    return pt_label_enc_impl(masks, pack, label_enc, sample_w, n, H, W, c0, c1, c2, f, ws, ws_bytes, (hipStream_t)stream);
+}

@@ -235,6 +235,12 @@ int pt_iou_refine_launch(const pt_iou_dims* d, const float* params, const float*
 int pt_clf_head_impl(const float* feat, const float* weight_tap_major, float* out, int n, int Cin, int Cout, int H, int W,
                      float norm_scale, float eps, void* ws, size_t ws_bytes, void* stream, const int* slot_dyn, long slot_stride);
 
+// mask label encoder (label_enc.hip); exported as pt_label_enc_* by api.hip
+size_t pt_label_enc_pack_floats_impl(int c0, int c1, int c2, int f);
+size_t pt_label_enc_ws_bytes_impl(int n, int H, int W, int c0, int c1, int c2, int f);
+int pt_label_enc_impl(const float* masks, const float* pack, float* label_enc, float* sample_w, int n, int H, int W, int c0, int c1,
+                      int c2, int f, void* ws, size_t ws_bytes, hipStream_t stream);
+
 // the argument / shape / route checks of a refinement call, nothing queued (iou_refine.hip)
 int pt_iou_refine_validate(const pt_iou_dims* d, const float* params, const float* prepared, const float* c3, const float* c4,
                            const float* mod3, const float* mod4, bool have_init_boxes, const float* boxes_out, const float* iou_out, int P,

@@ -40,6 +40,9 @@ What gets rebound (import path = contract; nothing in the reference tree is edit
                                                                                       -> pytracking_amd.iou_refine
   ltr.models.bbreg.atom_iou_net.AtomIoUNet.get_iou_feat  (both IoU feature towers; only with install(iou_feat=True))
                                                                                       -> pytracking_amd.iou_feat
+  ltr.models.lwl.label_encoder.ResidualDS16SW.forward, ltr.models.rts.label_encoder.ResidualDS16SW.forward
+                                                  (mask label encoder; only with install(label_encoder=True))
+                                                                                      -> pytracking_amd.label_encoder
 
 Dispatch rule of the rebound *functions*: device fp32 tensors of a shape the gfx950 kernels cover go to the C ABI;
 everything else (CPU tensors, dilations, grouped filters, K*K > 16, more than 16 filters) is outside the hot path and
@@ -585,6 +588,21 @@ def _install_iou_feat():
                                              name + ": call outside the gfx950 hot path"))
 
 
+def _install_label_encoder():
+    """`ResidualDS16SW.forward` of LWL and of RTS (label_encoder.py:38-55, the same code in both packages): stem, two BasicBlocks and both
+    heads in six launches.  CPU tensors, training mode, grad-enabled calls, modules of another structure and uncovered channel counts keep
+    the reference's code.  Off unless `install(label_encoder=True)`: the set a default install() rebinds is pinned."""
+    from . import label_encoder as _le
+    name = "ResidualDS16SW.forward"
+    for modname in ("ltr.models.lwl.label_encoder", "ltr.models.rts.label_encoder"):
+        try:
+            cls = importlib.import_module(modname).ResidualDS16SW
+        except Exception:
+            continue
+        _rebind(cls, "forward", _dispatcher(cls.forward, name, _le.covered, functools.partial(_le.forward, checked=True),
+                                            name + ": call outside the gfx950 hot path"))
+
+
 def _install_gn_hinge():
     """`GNSteepestDescent` on an exact reference `LinearFilterHinge` with parameter_batch_dim=0, residual_batch_dim=1
     (dimpnet.py:236-242, rts_net.py:325-333) -> the fused solver (pytracking_amd.gn_hinge); the residual object stays the reference's.
@@ -722,7 +740,7 @@ def _install_atom_cg():
 
 
 def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=True, iou_refine=True, preprocessing=True,
-            candidate_matching=True, kys=True, iou_feat=False):
+            candidate_matching=True, kys=True, iou_feat=False, label_encoder=False):
     """Rebind the boundary symbols.  Call after the reference is importable (`sys.path`) and before networks or
     trackers are constructed.  Idempotent.  If an installer raises, what was rebound so far is undone before the exception
     propagates (an optional reference module that does not import is not a failure: its family is skipped)."""
@@ -740,7 +758,7 @@ def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=T
         for flag, installer in ((tomp, _install_tomp), (clf_head, _install_clf_head), (localization, _install_localization),
                                 (iou_refine, _install_iou_refine), (preprocessing, _install_preprocessing),
                                 (candidate_matching, _install_candidate_matching), (kys, _install_kys), (atom_cg, _install_atom_cg),
-                                (iou_feat, _install_iou_feat)):
+                                (iou_feat, _install_iou_feat), (label_encoder, _install_label_encoder)):
             if flag:
                 installer()
     except BaseException:

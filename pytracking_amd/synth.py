@@ -546,3 +546,64 @@ def iou_feat_inputs(seed, n, cin3, h3, w3, cin4, h4, w4):
     f3 = np.maximum(rng.standard_normal((n, cin3, h3, w3), dtype=np.float32), 0.0).astype(np.float32)
     f4 = np.maximum(rng.standard_normal((n, cin4, h4, w4), dtype=np.float32), 0.0).astype(np.float32)
     return f3, f4
+
+
+LABEL_ENC_DIMS = (16, 32, 64, 16)       # layer_dims of the deployed label encoders (lwl_stage2.py:94-99, rts50.py:130-135)
+LABEL_ENC_CASES = {   # name: (n, H, W, layer_dims, use_bn)
+    "one": (1, 7, 9, LABEL_ENC_DIMS, False),                 # every stage collapses to 1 x 1: all taps but the centre are padding
+    "sixteen": (1, 16, 16, LABEL_ENC_DIMS, False),           # exact / 16
+    "odd": (3, 33, 50, LABEL_ENC_DIMS, False),               # odd sizes, output 3 x 4, per-mask indexing
+    "bands": (2, 40, 72, LABEL_ENC_DIMS, False),             # several row bands of the stem and of the first block
+    "wide": (1, 24, 300, LABEL_ENC_DIMS, False),             # wider than a workgroup's tile at every stage (75 / 38 / 19 / 19 columns)
+    "deployed": (2, 480, 832, LABEL_ENC_DIMS, False),        # lwl_ytvos.py image_sample_size; the tracker runs up to 32 of them
+    "bn_odd": (3, 33, 50, LABEL_ENC_DIMS, True),
+    "bn_wide": (1, 24, 300, LABEL_ENC_DIMS, True),
+    "dims": (2, 37, 70, (16, 16, 32, 32), False),            # channel counts other than the deployed ones
+}
+
+
+def label_enc_state(seed, dims=LABEL_ENC_DIMS, use_bn=False):
+    """A state dict (numpy, float32) of a ResidualDS16SW(dims, use_bn): kaiming (fan-in) weights, non-zero biases, a non-zero
+    samp_w_pred.weight (the reference initialises it to 0, which would hide a broken head) and, with use_bn, BatchNorm gains, shifts and
+    running statistics away from their defaults."""
+    rng = np.random.default_rng(seed)
+    c0, c1, c2, f = dims
+    sd = {}
+
+    def conv(name, i, o, bias):
+        sd[name + ".weight"] = (rng.standard_normal((o, i, 3, 3), dtype=np.float32) * np.float32(np.sqrt(2.0 / (9 * i)))).astype(np.float32)
+        if bias:
+            sd[name + ".bias"] = (rng.standard_normal(o, dtype=np.float32) * np.float32(0.1)).astype(np.float32)
+
+    def bn(name, o):
+        if not use_bn:
+            return
+        sd[name + ".weight"] = rng.uniform(0.5, 1.5, o).astype(np.float32)
+        sd[name + ".bias"] = (rng.standard_normal(o) * 0.1).astype(np.float32)
+        sd[name + ".running_mean"] = (rng.standard_normal(o) * 0.2).astype(np.float32)
+        sd[name + ".running_var"] = rng.uniform(0.5, 2.0, o).astype(np.float32)
+        sd[name + ".num_batches_tracked"] = np.array(100, dtype=np.int64)
+
+    conv("conv_block.0", 1, c0, True); bn("conv_block.1", c0)
+    for blk, i, o in (("res1", c0, c1), ("res2", c1, c2)):
+        conv(blk + ".conv1", i, o, False); bn(blk + ".bn1", o)
+        conv(blk + ".conv2", o, o, False); bn(blk + ".bn2", o)
+        conv(blk + ".downsample", i, o, True)
+    conv("label_pred.0", c2, f, True); bn("label_pred.1", f)
+    conv("samp_w_pred", c2, f, True)
+    return sd
+
+
+def label_enc_masks(seed, n, H, W):
+    """(n, H, W) float32 soft masks in [0, 1] as `sample_patch(..., is_mask=True)` yields them: an elliptical blob per mask with an exact-1
+    interior, an exact-0 background and a bilinear-looking edge a few pixels wide in between."""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    out = np.empty((n, H, W), dtype=np.float32)
+    for k in range(n):
+        cy, cx = rng.uniform(0.3, 0.7) * H, rng.uniform(0.3, 0.7) * W
+        ry, rx = rng.uniform(0.15, 0.35) * H + 1.0, rng.uniform(0.15, 0.35) * W + 1.0
+        edge = rng.uniform(1.5, 4.0)
+        d = (np.sqrt(((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2) - 1.0) * min(ry, rx)      # signed distance to the ellipse, about px
+        out[k] = np.clip(0.5 - d / edge, 0.0, 1.0).astype(np.float32)
+    return out
