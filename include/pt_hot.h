@@ -768,6 +768,50 @@ size_t pt_label_enc_ws_bytes(int n, int H, int W, int c0, int c1, int c2, int f)
 int pt_label_enc_f32(const float* masks, const float* pack, float* label_enc, float* sample_w, int n, int H, int W, int c0, int c1,
                      int c2, int f, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Segmentation decoder -- LWTLDecoder.forward (ltr/models/lwl/decoder.py:130-160) = RTSDecoder.forward (ltr/models/rts/decoder.py),
+ * lwl_decoder.hip.  LWL and RTS run it once per frame (lwl_net.py segment_target) on the target-model scores and the backbone features.
+ * fp32, eval mode, num_objects = None.
+ *
+ *   `levels` = 4 (layer4, layer3, layer2, layer1) or 3 (layer3, layer2, layer1); fc[l], hw[2l], hw[2l+1] = feature channels, height and
+ *   width of level l IN EXECUTION ORDER (deepest first); oc = {4,2,2,1} * mdim (4 levels) or {2,2,1} * mdim (3 levels), nc = oc + ic.
+ *   scores (n, ic, score_hw) and feats[l] (n, fc[l], H_l, W_l) fp32 contiguous; mask_out (n, 1, image_hw); dec_out (nullable) holds
+ *   `levels` pointers, each nullable: a non-null dec_out[l] (n, oc_l, H_l, W_l), 16-byte aligned, receives level l's output x
+ *   (the reference's '{L}_dec'), written by the launch that produces it -- no extra work.  feats and dec_out are HOST arrays of device
+ *   pointers, read before the call returns.
+ *   Per level: s = bilinear(scores); x = relu(proj(x_prev)) (not on the first level); h = reduce1(relu(reduce0(ft)));
+ *   hpool = mean(h) on the first level, else x; h = 3 x relu(conv3x3(cat(h, s))); h = RRB1(h); h = h * gate + resize(hpool),
+ *   gate = sigmoid(cab1(relu(cab0(cat(mean(h), mean(hpool)))))); x = RRB2(h); RRB(x) = relu(h + conv_b(relu(affine(conv_a(h))))), h = conv1x1(x).
+ *   Then bicubic x2, relu(conv3x3 mdim -> mdim/2), bicubic to image_hw, conv3x3 -> 1 channel.  bilinear / bicubic are PyTorch's
+ *   align_corners=False rules (bicubic A = -0.75, source not clamped, taps clamped).  No atomics: repeated calls are bit-identical.
+ *
+ * `pack` (pt_lwl_decoder_pack_floats floats, 16-byte aligned), per level in execution order:
+ *       proj[L].0 (not on the first level)   1x1
+ *       TSE[L].reduce.0, TSE[L].reduce.2     1x1, 1x1
+ *       TSE[L].transform.0 / .2 / .4         3x3 nc->nc, nc->nc, nc->oc
+ *       RRB1[L]: conv1x1, bblock.0 (+ BatchNorm), bblock's last convolution (no bias)      1x1, 3x3, 3x3
+ *       CAB[L].convreluconv.0, .2            1x1 (2 oc -> oc), 1x1
+ *       RRB2[L]                              as RRB1
+ *   then project.conv1 (3x3 mdim -> mdim/2) and project.conv2: weight (9, mdim/2) tap-major, bias (1).
+ *   1x1: weight (Cout, Cin), bias (Cout).
+ *   3x3: weight (Cout, 3, 3, Cin) tap-major = Conv2d.weight.permute(0, 2, 3, 1)
+ *        scale  (Cout)   1, or bn.weight / sqrt(bn.running_var + bn.eps) where a BatchNorm follows the convolution
+ *        shift  (Cout)   the convolution's bias (0 without one), or (bias - bn.running_mean) * scale + bn.bias
+ *   and a 3x3 layer computes conv_without_bias(x) * scale + shift; BatchNorm is NOT folded into the weights.  The layout does not depend
+ *   on use_bn.
+ *
+ * Covered: levels 3 or 4 with the oc table above; ic % 16 == 0 (<= 256), mdim % 32 == 0 (<= 256), fc % 16 == 0 (<= 8192); n <= 8; every
+ * map, partial-map set and token matrix below 2^32 - 32 bytes (the launchers' 32-bit byte offsets); pack 16-byte aligned.
+ * Status: NULL pointer PT_ERR_NULL, non-positive size PT_ERR_SHAPE, uncovered structure / size / misaligned pointer PT_ERR_UNSUPPORTED,
+ * workspace too small or not 256-byte aligned PT_ERR_WORKSPACE -- all before anything is queued.  pt_lwl_decoder_ws_bytes and
+ * pt_lwl_decoder_pack_floats return 0 for what is not covered.
+ * ---------------------------------------------------------------------------------------------- */
+size_t pt_lwl_decoder_pack_floats(int levels, const int* fc, int ic, int mdim, int use_bn);
+size_t pt_lwl_decoder_ws_bytes(int n, int levels, const int* fc, const int* hw, const int* score_hw, const int* image_hw, int ic, int mdim);
+int pt_lwl_decoder_f32(const float* scores, const float* const* feats, const float* pack, float* mask_out, float* const* dec_out, int n,
+                       int levels, const int* fc, const int* hw, const int* score_hw, const int* image_hw, int ic, int mdim, void* ws,
+                       size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

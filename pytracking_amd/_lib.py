@@ -9,8 +9,8 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PT_HOT_LIB", os.path.join(_HERE, "libpt_hot.so"))   # override: experiments only
-SOURCES = ["filter_kernels.hip", "fast_passes.hip", "sd_solver.hip", "mf_kernels.hip", "lwl_solver.hip", "atom_cg.hip", "atom_gn.hip", "tomp.hip", "localize.hip", "iou_refine.hip", "prroi.hip", "patch.hip", "frame_full.hip", "api.hip", "gn_hinge.hip", "tcm.hip", "kys.hip", "iou_feat.hip", "label_enc.hip"]
-HEADERS = ["common.h", "pt_internal.h", "rbuild.h", "sd_common.h", "mfma_gemm.h", "prroi_dev.h", "localize_dev.h", "frame_mid.h", os.path.join("..", "..", "include", "pt_hot.h")]
+SOURCES = ["filter_kernels.hip", "fast_passes.hip", "sd_solver.hip", "mf_kernels.hip", "lwl_solver.hip", "atom_cg.hip", "atom_gn.hip", "tomp.hip", "localize.hip", "iou_refine.hip", "prroi.hip", "patch.hip", "frame_full.hip", "api.hip", "gn_hinge.hip", "tcm.hip", "kys.hip", "iou_feat.hip", "label_enc.hip", "lwl_decoder.hip"]
+HEADERS = ["common.h", "pt_internal.h", "rbuild.h", "sd_common.h", "mfma_gemm.h", "conv_tokens.h", "prroi_dev.h", "localize_dev.h", "frame_mid.h", os.path.join("..", "..", "include", "pt_hot.h")]
 # kernarg preload: leading scalar kernel parameters arrive in SGPRs at wave launch (kernels that take them that way only)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-pass-failed", "-mllvm", "-amdgpu-kernarg-preload-count=14"]
 
@@ -99,6 +99,7 @@ EXPORTS = [
     "pt_kys_cost_volume_ws_bytes", "pt_kys_cost_volume_f32", "pt_kys_weight_floats", "pt_kys_predict_ws_bytes", "pt_kys_predict_response_f32",
     "pt_iou_feat_pack_floats", "pt_iou_feat_ws_bytes", "pt_iou_feat_f32", "pt_mf_corr_tm_plan",
     "pt_label_enc_pack_floats", "pt_label_enc_ws_bytes", "pt_label_enc_f32",
+    "pt_lwl_decoder_pack_floats", "pt_lwl_decoder_ws_bytes", "pt_lwl_decoder_f32",
 ]
 
 PT_TCM_MAX_POINTS, PT_TCM_MAX_LAYERS = 64, 32       # include/pt_hot.h
@@ -404,6 +405,13 @@ def lib():
     L.pt_label_enc_ws_bytes.argtypes = [i] * 7
     L.pt_label_enc_f32.restype = i
     L.pt_label_enc_f32.argtypes = [vp] * 4 + [i] * 7 + [vp, sz, vp]
+    ip = ctypes.POINTER(ctypes.c_int)
+    L.pt_lwl_decoder_pack_floats.restype = sz
+    L.pt_lwl_decoder_pack_floats.argtypes = [i, ip, i, i, i]
+    L.pt_lwl_decoder_ws_bytes.restype = sz
+    L.pt_lwl_decoder_ws_bytes.argtypes = [i, i, ip, ip, ip, ip, i, i]
+    L.pt_lwl_decoder_f32.restype = i
+    L.pt_lwl_decoder_f32.argtypes = [vp, ctypes.POINTER(vp), vp, vp, ctypes.POINTER(vp), i, i, ip, ip, ip, ip, i, i, vp, sz, vp]
     L.pt_mf_corr_tm_plan.restype = i
     L.pt_mf_corr_tm_plan.argtypes = [i] * 5 + [ctypes.POINTER(ctypes.c_int)]
     L.pt_sample_patch_f32.restype = i

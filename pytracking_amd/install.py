@@ -43,6 +43,9 @@ What gets rebound (import path = contract; nothing in the reference tree is edit
   ltr.models.lwl.label_encoder.ResidualDS16SW.forward, ltr.models.rts.label_encoder.ResidualDS16SW.forward
                                                   (mask label encoder; only with install(label_encoder=True))
                                                                                       -> pytracking_amd.label_encoder
+  ltr.models.lwl.decoder.LWTLDecoder.forward, ltr.models.rts.decoder.RTSDecoder.forward
+                                                  (segmentation decoder, decoder.py:130-160; only with install(decoder=True))
+                                                                                      -> pytracking_amd.lwl_decoder
 
 Dispatch rule of the rebound *functions*: device fp32 tensors of a shape the gfx950 kernels cover go to the C ABI;
 everything else (CPU tensors, dilations, grouped filters, K*K > 16, more than 16 filters) is outside the hot path and
@@ -603,6 +606,22 @@ def _install_label_encoder():
                                             name + ": call outside the gfx950 hot path"))
 
 
+def _install_lwl_decoder():
+    """`LWTLDecoder.forward` (ltr/models/lwl/decoder.py:130-160) and `RTSDecoder.forward` (ltr/models/rts/decoder.py, the same code): all
+    levels (TSE, RRB, CAB, RRB) and the Upsampler in one asynchronous call.  CPU tensors, training mode, grad-enabled calls, multi-object
+    calls (`num_objects`), modules of another structure and uncovered shapes keep the reference's code.  Off unless
+    `install(decoder=True)`: the set a default install() rebinds is pinned."""
+    from . import lwl_decoder as _dec
+    for modname, clsname in (("ltr.models.lwl.decoder", "LWTLDecoder"), ("ltr.models.rts.decoder", "RTSDecoder")):
+        try:
+            cls = getattr(importlib.import_module(modname), clsname)
+        except Exception:
+            continue
+        name = clsname + ".forward"
+        _rebind(cls, "forward", _dispatcher(cls.forward, name, _dec.covered, functools.partial(_dec.forward, checked=True),
+                                            name + ": call outside the gfx950 hot path"))
+
+
 def _install_gn_hinge():
     """`GNSteepestDescent` on an exact reference `LinearFilterHinge` with parameter_batch_dim=0, residual_batch_dim=1
     (dimpnet.py:236-242, rts_net.py:325-333) -> the fused solver (pytracking_amd.gn_hinge); the residual object stays the reference's.
@@ -740,7 +759,7 @@ def _install_atom_cg():
 
 
 def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=True, iou_refine=True, preprocessing=True,
-            candidate_matching=True, kys=True, iou_feat=False, label_encoder=False):
+            candidate_matching=True, kys=True, iou_feat=False, label_encoder=False, decoder=False):
     """Rebind the boundary symbols.  Call after the reference is importable (`sys.path`) and before networks or
     trackers are constructed.  Idempotent.  If an installer raises, what was rebound so far is undone before the exception
     propagates (an optional reference module that does not import is not a failure: its family is skipped)."""
@@ -758,7 +777,8 @@ def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=T
         for flag, installer in ((tomp, _install_tomp), (clf_head, _install_clf_head), (localization, _install_localization),
                                 (iou_refine, _install_iou_refine), (preprocessing, _install_preprocessing),
                                 (candidate_matching, _install_candidate_matching), (kys, _install_kys), (atom_cg, _install_atom_cg),
-                                (iou_feat, _install_iou_feat), (label_encoder, _install_label_encoder)):
+                                (iou_feat, _install_iou_feat), (label_encoder, _install_label_encoder),
+                                (decoder, _install_lwl_decoder)):
             if flag:
                 installer()
     except BaseException:

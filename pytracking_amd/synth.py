@@ -607,3 +607,80 @@ def label_enc_masks(seed, n, H, W):
         d = (np.sqrt(((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2) - 1.0) * min(ry, rx)      # signed distance to the ellipse, about px
         out[k] = np.clip(0.5 - d / edge, 0.0, 1.0).astype(np.float32)
     return out
+
+
+# Segmentation decoder (ltr/models/lwl/decoder.py:87-160).  name: dict(n, mdim, ic, use_bn, levels = ((layer, fc, H, W), ...) deepest first,
+# image (H, W), scores (h, w)).  Feature maps are inputs: their sizes need not come from a real backbone.
+LWL_DECODER_CASES = {
+    # every resize ratio is non-integral
+    "tiny": dict(n=1, mdim=32, ic=16, use_bn=True, levels=(("layer4", 32, 2, 2), ("layer3", 32, 3, 4), ("layer2", 16, 5, 7), ("layer1", 16, 9, 13)),
+                 image=(33, 50), scores=(3, 4)),
+    # no layer4: layer3 is the deepest level; no BatchNorm
+    "three": dict(n=2, mdim=32, ic=16, use_bn=False, levels=(("layer3", 32, 4, 6), ("layer2", 16, 7, 11), ("layer1", 16, 14, 22)),
+                  image=(56, 88), scores=(4, 6)),
+    # several bands and channel splits on the banded route
+    "bands": dict(n=2, mdim=32, ic=16, use_bn=True, levels=(("layer4", 64, 5, 9), ("layer3", 32, 10, 18), ("layer2", 32, 20, 36), ("layer1", 16, 40, 72)),
+                  image=(160, 288), scores=(10, 18)),
+    # rows wider than the banded route stages: the GEMM route at layer1 and in the Upsampler
+    "wide": dict(n=1, mdim=32, ic=16, use_bn=True, levels=(("layer4", 32, 1, 23), ("layer3", 32, 2, 45), ("layer2", 16, 3, 90), ("layer1", 16, 6, 180)),
+                 image=(24, 720), scores=(2, 45)),
+    # a score map of another size than every level: a real bilinear down- and up-resize
+    "ratio": dict(n=1, mdim=32, ic=32, use_bn=True, levels=(("layer4", 32, 3, 5), ("layer3", 32, 6, 10), ("layer2", 16, 12, 20), ("layer1", 16, 24, 40)),
+                  image=(96, 160), scores=(8, 13)),
+    # lwl_ytvos.py / lwl_stage2.py: 480 x 832 image, ResNet-50 layers 4..1, decoder_mdim 64, 16 score channels, BatchNorm
+    "deployed": dict(n=1, mdim=64, ic=16, use_bn=True,
+                     levels=(("layer4", 2048, 15, 26), ("layer3", 1024, 30, 52), ("layer2", 512, 60, 104), ("layer1", 256, 120, 208)),
+                     image=(480, 832), scores=(30, 52)),
+}
+_LWL_DECODER_OC = {"layer1": 1, "layer2": 2, "layer3": 2, "layer4": 4}
+
+
+def lwl_decoder_state(seed, mdim, ic, use_bn, levels):
+    """A state dict (numpy, float32) of an LWTLDecoder(ic, mdim, {layer: fc}, use_bn): fan-in scaled weights (the residual branches and the
+    CAB sum scaled down so that activations stay O(1) through all levels), non-zero biases and, with use_bn, BatchNorm gains, shifts and
+    running statistics away from their defaults."""
+    rng = np.random.default_rng(seed)
+    sd = {}
+
+    def conv(name, i, o, k, bias=True, gain=1.0):
+        sd[name + ".weight"] = (rng.standard_normal((o, i, k, k), dtype=np.float32) * np.float32(gain * np.sqrt(1.0 / (k * k * i)))).astype(np.float32)
+        if bias:
+            sd[name + ".bias"] = (rng.standard_normal(o, dtype=np.float32) * np.float32(0.1)).astype(np.float32)
+
+    def rrb(name, oc):
+        conv(name + ".conv1x1", oc, oc, 1, gain=0.8)
+        conv(name + ".bblock.0", oc, oc, 3, gain=1.4)
+        if use_bn:
+            sd[name + ".bblock.1.weight"] = rng.uniform(0.5, 1.5, oc).astype(np.float32)
+            sd[name + ".bblock.1.bias"] = (rng.standard_normal(oc) * 0.1).astype(np.float32)
+            sd[name + ".bblock.1.running_mean"] = (rng.standard_normal(oc) * 0.2).astype(np.float32)
+            sd[name + ".bblock.1.running_var"] = rng.uniform(0.5, 2.0, oc).astype(np.float32)
+            sd[name + ".bblock.1.num_batches_tracked"] = np.array(100, dtype=np.int64)
+        conv(name + ".bblock.%d" % (3 if use_bn else 2), oc, oc, 3, bias=False, gain=0.7)
+
+    prev = None
+    for L, fc, _, _ in levels:
+        oc = _LWL_DECODER_OC[L] * mdim
+        nc = oc + ic
+        if prev is not None:
+            conv("proj.%s.0" % L, prev, oc, 1, gain=0.7)
+        conv("TSE.%s.reduce.0" % L, fc, oc, 1, gain=1.4)
+        conv("TSE.%s.reduce.2" % L, oc, oc, 1, gain=1.4)
+        for k in (0, 2, 4):
+            conv("TSE.%s.transform.%d" % (L, k), nc, oc if k == 4 else nc, 3, gain=1.4)
+        rrb("RRB1.%s" % L, oc)
+        conv("CAB.%s.convreluconv.0" % L, 2 * oc, oc, 1, gain=1.4)
+        conv("CAB.%s.convreluconv.2" % L, oc, oc, 1, gain=2.0)
+        rrb("RRB2.%s" % L, oc)
+        prev = oc
+    conv("project.conv1", mdim, mdim // 2, 3, gain=1.4)
+    conv("project.conv2", mdim // 2, 1, 3, gain=1.4)
+    return sd
+
+
+def lwl_decoder_inputs(seed, n, ic, levels, scores):
+    """(scores (n, 1, ic, h, w), {layer: (n, fc, H, W)}) float32: signed score channels, rectified features."""
+    rng = np.random.default_rng(seed)
+    s = rng.standard_normal((n, 1, ic) + tuple(scores), dtype=np.float32)
+    feats = {L: np.maximum(rng.standard_normal((n, fc, H, W), dtype=np.float32), 0.0).astype(np.float32) for L, fc, H, W in levels}
+    return s, feats
