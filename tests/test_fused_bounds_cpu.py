@@ -1,0 +1,107 @@
+"""The bound of tests/fused_f64.py without a GPU: ref_err of every committed case is the number its golden recorded, and FACTOR x ref_err
+catches what the flat 1e-4 of the golden tests lets through.  Two mutants of the stand-in, evaluated in float64 so that nothing but the
+mutation separates them from `want`: every BatchNorm eps doubled (errors of 2e-6 to 9e-5, all under 1e-4), and the weights of one
+mid-network convolution cut to a 10-bit mantissa.  Each must leave the bound on every committed small case while the unmutated fp32 run
+stays inside it; raising FACTOR until a mutant slips through fails here (the decoder's eps mutant peaks at 6.8 x ref_err on `tiny`, 11 x on
+`ratio`).
+
+Every test prints its figures before it asserts (run with -s)."""
+import copy
+
+import numpy as np
+import pytest
+import torch
+
+import fused_f64 as F64
+import iou_feat_cases as IC
+import label_enc_cases as LC
+import lwl_decoder_cases as DC
+from pytracking_amd import synth
+
+# the mid-network convolution whose weights are truncated ({last}: the decoder's last level; the later stages attenuate a deeper one)
+TRUNCATED = {"iou_feat": "conv3_1t.0", "label_enc": "res2.conv1", "lwl_decoder": "RRB2.{last}.conv1x1"}
+COMMITTED = [(kind, name) for kind in F64.KINDS for name in F64.SMALL[kind] + F64.DEPLOYED[kind]]
+SMALL = [(kind, name) for kind in F64.KINDS for name in F64.SMALL[kind]]
+
+
+def _has_bn(kind, name):
+    return {"iou_feat": lambda: True, "label_enc": lambda: synth.LABEL_ENC_CASES[name][4],
+            "lwl_decoder": lambda: synth.LWL_DECODER_CASES[name]["use_bn"]}[kind]()
+
+
+# a case without BatchNorm has no eps mutant
+MUTANTS = [(kind, name, which) for kind, name in SMALL for which in ("eps", "weights") if which == "weights" or _has_bn(kind, name)]
+
+
+def _mutant(kind, name, which):
+    """The stand-in of a committed case in float64 with one defect."""
+    net = copy.deepcopy(F64.committed_case(kind, name)[0]).double()
+    if which == "eps":
+        bns = [m for m in net.modules() if isinstance(m, torch.nn.BatchNorm2d)]
+        assert bns
+        for m in bns:
+            m.eps *= 2
+    else:
+        conv = net.get_submodule(TRUNCATED[kind].format(last=list(getattr(net, "ft_channels", {"": 0}))[-1]))
+        with torch.no_grad():
+            w32 = conv.weight.float().contiguous()                        # exact: the state is fp32
+            conv.weight.copy_((w32.view(torch.int32) & ~0x1FFF).view(torch.float32))
+    return net
+
+
+def _golden_fp32(kind, name, want):
+    """[(the golden's stored fp32 values of an output, the same elements of the arrays `want`)] and whether every output is stored in full."""
+    g = {"iou_feat": IC, "label_enc": LC, "lwl_decoder": DC}[kind].case(name)[0]
+    pairs, full = [], True
+    for q, w in want.items():
+        if q not in g:
+            full = False                                                  # deployed decoder: layer4_dec and the mask only
+        elif kind == "iou_feat" and "idx" + q[1] in g:
+            pairs.append((g[q], w.reshape(-1)[g["idx" + q[1]]]))          # deployed towers: a fixed sample of each output
+            full = False
+        else:
+            w = DC.golden_view(name, q, w) if kind == "lwl_decoder" else w
+            full = full and w.size == want[q].size
+            pairs.append((g[q], w.reshape(g[q].shape)))
+    return pairs, full
+
+
+@pytest.mark.parametrize("kind,name", COMMITTED)
+def test_ref_err_is_what_the_golden_recorded(kind, name):
+    """ref_err is the goldens' ref_fp32_err.  Two statements, because an fp32 CPU convolution blocks its sums by host (threads, vector
+    width), so its rounding -- and with it ref_err, a maximum over few elements -- moves by tens of per cent between hosts:
+      * on any host, the golden's stored fp32 output is ref_fp32_err away from `want`: the anchor is the float64 arithmetic the goldens were
+        measured against (the decoder's and the label encoder's took it from the reference's own module in float64, the IoU goldens from
+        the numpy restatement of tests/iou_feat_np.py).  Where the golden stores a sample of an output, at most that far.
+      * where this host's fp32 run reproduces the golden's bits, ref_err itself is that number.
+    Equal means to 1e-6 relative: the float64 run's own order of summation moves its values by 2^-53 relative, 1e-9 of an error of 1e-6."""
+    a, recorded = F64.committed(kind, name), F64.committed_case(kind, name)[2]
+    pairs, full = _golden_fp32(kind, name, a.want)
+    dist = max(float(np.abs(g.astype(np.float64) - w).max()) for g, w in pairs)
+    print(f"\n{kind}_{name}: ref_err {a.ref_err:.6e}, golden ref_fp32_err {recorded:.6e}, max |golden fp32 - float64| {dist:.6e}"
+          + ("" if full else " (on the stored sample)"))
+    assert abs(dist / recorded - 1) <= 1e-6 if full else dist <= recorded * (1 + 1e-6)
+    net, args, _ = F64.committed_case(kind, name)
+    f32 = {q: t.numpy() for q, t in F64.standin(kind, net, args).items()}
+    same_bits = all(np.array_equal(g, v) for g, v in _golden_fp32(kind, name, f32)[0])
+    if same_bits:
+        assert abs(a.ref_err / recorded - 1) <= 1e-6
+    assert max(a.ref_errs.values()) == a.ref_err and set(a.want) == set(a.ref_errs) and 0.25 * recorded <= a.ref_err <= 4 * recorded
+
+
+@pytest.mark.parametrize("kind,name", SMALL)
+def test_the_fp32_stand_in_is_inside_the_bound(kind, name):
+    net, args, _ = F64.committed_case(kind, name)
+    a = F64.committed(kind, name)
+    errs = F64.errors(a.want, F64.standin(kind, net, args))
+    print(F64.report(f"{kind}_{name}, fp32 CPU", errs, a.ref_err))
+    assert all(e <= F64.bound(a.ref_err) for e in errs.values()), errs
+
+
+@pytest.mark.parametrize("kind,name,which", MUTANTS)
+def test_the_bound_catches_the_mutant(kind, name, which):
+    a = F64.committed(kind, name)
+    args = F64.convert(F64.committed_case(kind, name)[1], dtype=torch.float64)
+    errs = F64.errors(a.want, F64.standin(kind, _mutant(kind, name, which), args))
+    print(F64.report(f"{kind}_{name}, mutant {which}", errs, a.ref_err) + f"  (under the flat 1e-4: {max(errs.values()) <= 1e-4})")
+    assert max(errs.values()) > F64.bound(a.ref_err), errs
