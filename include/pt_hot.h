@@ -266,6 +266,44 @@ size_t pt_tomp_bbreg_ws_bytes(int n, int d_model, int H, int W);
 int pt_tomp_bbreg_f32(const float* params, const float* feat, const float* filter, float* ltrb, int n, int d_model,
                       int H, int W, void* ws, size_t ws_bytes, void* stream);
 
+/* The kernels the three ToMP entry points above would launch, in launch order, as route ids.  Host only: launches nothing, touches
+ * no device, allocates nothing.  The queries walk the entry points' own host code and dispatchers, so what they report is what a call
+ * with 256-byte aligned buffers (what the Python wrappers allocate) runs; parameter-pack, prepared-buffer and workspace offsets are the
+ * real ones.  A launcher-selected kernel has one id per kernel or operand mode; a kernel that is launched unconditionally has one id.
+ *   PT_TOMP_R_GEMM_*      launch_gemm: 32 x 32 tiles (plain grid / XCD swizzle / swizzle whose last group of 8 row tiles is partly
+ *                         phantom), 64 x 64 tiles, k_gemm_ps 64 x 64 (PS2) and 128 x 64 (PS4, whole K or split-K), each with the
+ *                         16-byte epilogue (_WIDE) or the scalar one, k_gemm_big, the 3x3 gather with and without the GroupNorm loader
+ *   PT_TOMP_R_ATTN*       k_attn<16 | 32 | 64>
+ *   PT_TOMP_R_LN*         k_ln_rows_t<4> plain / with two or four split-K addends + residual / two norms in one, k_ln_rows_t<2>,
+ *                         k_ln_rows_t<1>, the generic k_ln_rows
+ *   PT_TOMP_R_DEC0_*      no launch: decoder layer 0's first two GEMVs come as prepared constants (CONST) or are launched (LIVE)
+ *   PT_TOMP_R_GEMV_*      k_gemv_dec<1 | 2 | 4 | 8>, k_gemv<4>, k_gemv<1>
+ *   PT_TOMP_R_GN_APPLY    the tower's unfused GroupNorm (maps under 32 positions, more than 256 slices per image)
+ * pt_tomp_predict_routes follows pt_tomp_predict_f32 (the routes do not depend on num_gth_frames), pt_tomp_bbreg_routes
+ * pt_tomp_bbreg_f32, pt_tomp_linear_routes pt_tomp_linear_f32.  On PT_OK routes[0 .. *n_routes) are set and the rest of the `cap`
+ * entries zeroed.  Otherwise every entry is zeroed and *n_routes = 0: PT_ERR_SHAPE / PT_ERR_UNSUPPORTED exactly where the entry point
+ * (and pt_tomp_predict_ws_bytes / pt_tomp_bbreg_ws_bytes) refuses, PT_ERR_WORKSPACE when cap is too small (PT_TOMP_MAX_ROUTES always
+ * suffices); PT_ERR_NULL for a null argument. */
+enum pt_tomp_route {
+    PT_TOMP_R_NONE = 0,
+    PT_TOMP_R_TOKENS, PT_TOMP_R_BOX1,
+    PT_TOMP_R_GEMM_T32, PT_TOMP_R_GEMM_T32_SWZ, PT_TOMP_R_GEMM_T32_SWZ_PAD, PT_TOMP_R_GEMM_T64,
+    PT_TOMP_R_GEMM_PS2_WIDE, PT_TOMP_R_GEMM_PS2, PT_TOMP_R_GEMM_PS4_WIDE, PT_TOMP_R_GEMM_PS4,
+    PT_TOMP_R_GEMM_PS4_SPLITK_WIDE, PT_TOMP_R_GEMM_PS4_SPLITK, PT_TOMP_R_GEMM_BIG, PT_TOMP_R_GEMM_CONV, PT_TOMP_R_GEMM_CONV_GN,
+    PT_TOMP_R_ATTN16, PT_TOMP_R_ATTN32, PT_TOMP_R_ATTN64,
+    PT_TOMP_R_LN256, PT_TOMP_R_LN256_SPLIT2, PT_TOMP_R_LN256_SPLIT4, PT_TOMP_R_LN256_DOUBLE, PT_TOMP_R_LN128, PT_TOMP_R_LN64,
+    PT_TOMP_R_LN_GENERIC,
+    PT_TOMP_R_DEC0_CONST, PT_TOMP_R_DEC0_LIVE,
+    PT_TOMP_R_GEMV_DEC1, PT_TOMP_R_GEMV_DEC2, PT_TOMP_R_GEMV_DEC4, PT_TOMP_R_GEMV_DEC8, PT_TOMP_R_GEMV_V4, PT_TOMP_R_GEMV_V1,
+    PT_TOMP_R_DEC_SCORES, PT_TOMP_R_DEC_CTX, PT_TOMP_R_TO_NCHW,
+    PT_TOMP_R_REG_ATTEND, PT_TOMP_R_GN_REDUCE, PT_TOMP_R_GN_APPLY, PT_TOMP_R_REG_FINISH,
+    PT_TOMP_R_COUNT
+};
+#define PT_TOMP_MAX_ROUTES 256
+int pt_tomp_predict_routes(const pt_tomp_dims* dims, int n_train, int n_seq, int parallel, int* routes, int cap, int* n_routes);
+int pt_tomp_bbreg_routes(int n, int d_model, int H, int W, int* routes, int cap, int* n_routes);
+int pt_tomp_linear_routes(int B, int N, int K, int* routes, int cap, int* n_routes);
+
 /* ------------------------------------------------------------------------------------------------
  * Classification-feature head -- `residual_bottleneck(num_blocks=0, final_conv=True, l2norm=True)`
  * (ltr/models/target_classifier/features.py:49-73): Conv2d(Cin, Cout, 3, padding=1, bias=False) followed by

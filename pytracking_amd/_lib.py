@@ -74,6 +74,14 @@ class TompDims(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in ("d_model", "nhead", "dim_ff", "n_enc", "n_dec", "H", "W", "max_res")]
 
 
+# `enum pt_tomp_route` of include/pt_hot.h, by value (what pt_tomp_*_routes report)
+TOMP_ROUTES = (
+    "NONE", "TOKENS", "BOX1", "GEMM_T32", "GEMM_T32_SWZ", "GEMM_T32_SWZ_PAD", "GEMM_T64", "GEMM_PS2_WIDE", "GEMM_PS2", "GEMM_PS4_WIDE",
+    "GEMM_PS4", "GEMM_PS4_SPLITK_WIDE", "GEMM_PS4_SPLITK", "GEMM_BIG", "GEMM_CONV", "GEMM_CONV_GN", "ATTN16", "ATTN32", "ATTN64", "LN256",
+    "LN256_SPLIT2", "LN256_SPLIT4", "LN256_DOUBLE", "LN128", "LN64", "LN_GENERIC", "DEC0_CONST", "DEC0_LIVE", "GEMV_DEC1", "GEMV_DEC2",
+    "GEMV_DEC4", "GEMV_DEC8", "GEMV_V4", "GEMV_V1", "DEC_SCORES", "DEC_CTX", "TO_NCHW", "REG_ATTEND", "GN_REDUCE", "GN_APPLY", "REG_FINISH")
+PT_TOMP_MAX_ROUTES = 256
+
 EXPORTS = [
     "pt_strerror", "pt_abi_version",
     "pt_corr_pass_plan", "pt_apply_filter_ws_bytes", "pt_apply_filter_f32",
@@ -86,6 +94,7 @@ EXPORTS = [
     "pt_lwl_ws_bytes", "pt_lwl_gn_solve_f32",
     "pt_tomp_param_floats", "pt_tomp_prepared_floats", "pt_tomp_prepare_f32", "pt_tomp_posenc_f32", "pt_tomp_predict_ws_bytes", "pt_tomp_predict_f32", "pt_tomp_linear_f32",
     "pt_tomp_bbreg_param_floats", "pt_tomp_bbreg_ws_bytes", "pt_tomp_bbreg_f32",
+    "pt_tomp_predict_routes", "pt_tomp_bbreg_routes", "pt_tomp_linear_routes",
     "pt_clf_head_ws_bytes", "pt_clf_head_f32", "pt_max2d_f32", "pt_localize_f32", "pt_localize_decide_f32",
     "pt_localize_constants_f32", "pt_localize_advanced_f32", "pt_localize_advanced_sync_f32",
     "pt_iou_param_floats", "pt_iou_prepared_floats", "pt_iou_prepare_f32", "pt_iou_refine_ws_bytes", "pt_iou_refine_f32", "pt_iou_refine_sync_f32",
@@ -312,6 +321,13 @@ def lib():
     L.pt_tomp_bbreg_ws_bytes.argtypes = [i, i, i, i]
     L.pt_tomp_bbreg_f32.restype = i
     L.pt_tomp_bbreg_f32.argtypes = [vp, vp, vp, vp, i, i, i, i, vp, sz, vp]
+    ip = ctypes.POINTER(ctypes.c_int)
+    L.pt_tomp_predict_routes.restype = i
+    L.pt_tomp_predict_routes.argtypes = [dp, i, i, i, ip, i, ip]
+    L.pt_tomp_bbreg_routes.restype = i
+    L.pt_tomp_bbreg_routes.argtypes = [i, i, i, i, ip, i, ip]
+    L.pt_tomp_linear_routes.restype = i
+    L.pt_tomp_linear_routes.argtypes = [i, i, i, ip, i, ip]
     L.pt_clf_head_ws_bytes.restype = sz
     L.pt_clf_head_ws_bytes.argtypes = [i] * 5
     L.pt_clf_head_f32.restype = i

@@ -671,7 +671,21 @@ static bool wide_store_ok(const GemmArgs& g) {
            ((uintptr_t)g.C % 16) == 0 && (!g.bias || ((uintptr_t)g.bias % 16) == 0);
 }
 
-int launch_gemm(const GemmArgs& g, hipStream_t st, bool conv = false) {
+// Route log of the host-only queries (pt_tomp_route_query): a launcher that is handed one appends the id of the kernel it picked
+// (PT_TOMP_R_* of include/pt_hot.h) and queues nothing.  n counts every entry, also those past cap.
+struct PtRouteLog { int* out; int cap; int n; };
+static inline void pt_route_note(PtRouteLog* log, int id) {
+    if (log->n < log->cap) log->out[log->n] = id;
+    ++log->n;
+}
+
+// The kernel launch_gemm runs for a problem: decided here, on the host, from the arguments alone (no device call), for the launcher and
+// for the route query alike.  route: PT_TOMP_R_GEMM_*; nz: grid.z (K-slices or batch); gy: row tiles of the 64 x 64 / 32 x 32 kernels
+// before the swizzle rounds them up to a multiple of 8.
+struct GemmPlan { int route, nz, swizzle, gy; };
+
+int gemm_plan(const GemmArgs& g, bool conv, GemmPlan* p) {
+    *p = GemmPlan{};
     // K % 4: a loader thread fetches 4 consecutive k (16 bytes); quads past K are not requested at all (zeros)
     if (g.K % 4 != 0 || (conv && g.K % 32 != 0) || g.M <= 0 || g.N <= 0 || (g.batch && g.ksteps)) return PT_ERR_UNSUPPORTED;
     // the epilogue addresses C (and R) with 32-bit byte offsets through a raw buffer descriptor
@@ -679,6 +693,7 @@ int launch_gemm(const GemmArgs& g, hipStream_t st, bool conv = false) {
     const long rows = g.nchw ? (long)g.M * g.N : (g.c_segstride ? ((long)(g.M / g.c_seg) + 1) * g.c_segstride * g.ldc
                                                                    : (long)g.M * g.ldc);
     if ((rows + (long)(nz - 1) * g.c_zstride) * 4 >= 0xFFFFFFE0L) return PT_ERR_UNSUPPORTED;
+    p->nz = nz;
     // round 6: 128 x 64 tiles, two workgroups per CU (every other shape: the round-5 routes below), for
     //   * wide outputs at short K (FFN first product: N = 2048, K = 256 -> 512 workgroups of 8 stages)
     //   * split-K products the caller asked to be cut in >= 4 (FFN second product: 256 workgroups of 16 stages, M tiles on x)
@@ -686,26 +701,16 @@ int launch_gemm(const GemmArgs& g, hipStream_t st, bool conv = false) {
         g.c_segstride == 0 && g.N >= 512) {
         // the attention's input projection (N = 3 D = 768, K = 256, "+pos" on the q | k column tiles): 64 x 64 tiles of 4 waves, 37 KB LDS,
         // up to four workgroups per CU; the 32 x 32 route took 16.2 us for 0.76 GFLOP (1464 workgroups = 1.45 rounds)
-        constexpr size_t lds = 2 * (64 + 64) * GB_LS * sizeof(float);
-        if (wide_store_ok(g)) hipLaunchKernelGGL((k_gemm_ps<2, 2, 2, 2, false, true>), dim3((g.N + 63) / 64, (g.M + 63) / 64, 1), dim3(256), lds, st, g);
-        else hipLaunchKernelGGL((k_gemm_ps<2, 2, 2, 2, false>), dim3((g.N + 63) / 64, (g.M + 63) / 64, 1), dim3(256), lds, st, g);
-        PT_CHECK_LAUNCH();
+        p->route = wide_store_ok(g) ? PT_TOMP_R_GEMM_PS2_WIDE : PT_TOMP_R_GEMM_PS2;
         return PT_OK;
     }
     if (!conv && g.M >= 1024 && g.K % 32 == 0 && !g.pos && !g.batch && !g.nchw && ((g.N >= 1024 && nz == 1) || (nz >= 4 && g.N % 64 == 0))) {
-        constexpr size_t lds = 2 * (128 + 64) * GB_LS * sizeof(float);
         const bool sw = wide_store_ok(g);
-        if (nz == 1 && sw) hipLaunchKernelGGL((k_gemm_ps<4, 2, 2, 2, false, true>), dim3((g.N + 63) / 64, (g.M + 127) / 128, 1), dim3(512), lds, st, g);
-        else if (nz == 1) hipLaunchKernelGGL((k_gemm_ps<4, 2, 2, 2, false>), dim3((g.N + 63) / 64, (g.M + 127) / 128, 1), dim3(512), lds, st, g);
-        else if (sw) hipLaunchKernelGGL((k_gemm_ps<4, 2, 2, 2, true, true>), dim3((g.M + 127) / 128, (g.N + 63) / 64, nz), dim3(512), lds, st, g);
-        else hipLaunchKernelGGL((k_gemm_ps<4, 2, 2, 2, true>), dim3((g.M + 127) / 128, (g.N + 63) / 64, nz), dim3(512), lds, st, g);
-        PT_CHECK_LAUNCH();
+        p->route = nz == 1 ? (sw ? PT_TOMP_R_GEMM_PS4_WIDE : PT_TOMP_R_GEMM_PS4) : (sw ? PT_TOMP_R_GEMM_PS4_SPLITK_WIDE : PT_TOMP_R_GEMM_PS4_SPLITK);
         return PT_OK;
     }
     if (!conv && g.N >= 1024 && g.M >= 1024 && g.K % 32 == 0 && !g.pos && !g.batch) {
-        hipLaunchKernelGGL(k_gemm_big, dim3((g.N + 127) / 128, (g.M + 127) / 128, nz), dim3(512), 2 * GB_STAGE * sizeof(float),
-                           st, g);
-        PT_CHECK_LAUNCH();
+        p->route = PT_TOMP_R_GEMM_BIG;
         return PT_OK;
     }
     if (conv) {
@@ -715,23 +720,75 @@ int launch_gemm(const GemmArgs& g, hipStream_t st, bool conv = false) {
             if (g.gn_slices > GEMM_GN_MAX_SLICES || g.gn_slices < 1 || !g.gn_gam || !g.gn_bet || g.HW < 32 || g.gn_count <= 0 ||
                 ((uintptr_t)g.gn_gam % 16) != 0 || ((uintptr_t)g.gn_bet % 16) != 0)
                 return PT_ERR_UNSUPPORTED;
-            hipLaunchKernelGGL((k_gemm<32, 32, 2>), dim3((g.N + 31) / 32, (g.M + 31) / 32, nz), dim3(256), 0, st, g);
+            p->route = PT_TOMP_R_GEMM_CONV_GN;
         } else {
-            hipLaunchKernelGGL((k_gemm<32, 32, 1>), dim3((g.N + 31) / 32, (g.M + 31) / 32, nz), dim3(256), 0, st, g);
+            p->route = PT_TOMP_R_GEMM_CONV;
         }
+        p->gy = (g.M + 31) / 32;
     } else if (g.N >= GEMM_TILE64_MIN_N && g.M >= 1024 && nz == 1 && g.K % 32 == 0) {
-        GemmArgs gs = g;
-        const int gy = (g.M + 63) / 64;
-        gs.swizzle = gy >= 16;
-        hipLaunchKernelGGL((k_gemm<64, 64, 0, 32>), dim3((g.N + 63) / 64, gs.swizzle ? (gy + 7) / 8 * 8 : gy, 1), dim3(256), 0,
-                           st, gs);
+        p->route = PT_TOMP_R_GEMM_T64;
+        p->gy = (g.M + 63) / 64;
+        p->swizzle = p->gy >= 16;
     } else {
-        GemmArgs gs = g;
-        const int gy = (g.M + 31) / 32;
-        gs.swizzle = nz == 1 && gy >= 16;                            // worth it once every XCD gets >= 2 row tiles
+        p->gy = (g.M + 31) / 32;
+        p->swizzle = nz == 1 && p->gy >= 16;                         // worth it once every XCD gets >= 2 row tiles
+        // swizzled grids are rounded up to whole groups of 8 row tiles: the phantom tiles of the last group have their own id
+        p->route = !p->swizzle ? PT_TOMP_R_GEMM_T32 : p->gy % 8 == 0 ? PT_TOMP_R_GEMM_T32_SWZ : PT_TOMP_R_GEMM_T32_SWZ_PAD;
+    }
+    return PT_OK;
+}
+
+// log != nullptr: the route is noted and nothing is queued
+int launch_gemm(const GemmArgs& g, hipStream_t st, bool conv = false, PtRouteLog* log = nullptr) {
+    GemmPlan p;
+    const int rc = gemm_plan(g, conv, &p);
+    if (rc) return rc;
+    if (log) {
+        pt_route_note(log, p.route);
+        return PT_OK;
+    }
+    const int nz = p.nz;
+    const unsigned gy = p.swizzle ? (p.gy + 7) / 8 * 8 : p.gy;
+    constexpr size_t lds2 = 2 * (64 + 64) * GB_LS * sizeof(float), lds4 = 2 * (128 + 64) * GB_LS * sizeof(float);
+    GemmArgs gs = g;
+    switch (p.route) {
+    case PT_TOMP_R_GEMM_PS2_WIDE:
+        hipLaunchKernelGGL((k_gemm_ps<2, 2, 2, 2, false, true>), dim3((g.N + 63) / 64, (g.M + 63) / 64, 1), dim3(256), lds2, st, g);
+        break;
+    case PT_TOMP_R_GEMM_PS2:
+        hipLaunchKernelGGL((k_gemm_ps<2, 2, 2, 2, false>), dim3((g.N + 63) / 64, (g.M + 63) / 64, 1), dim3(256), lds2, st, g);
+        break;
+    case PT_TOMP_R_GEMM_PS4_WIDE:
+        hipLaunchKernelGGL((k_gemm_ps<4, 2, 2, 2, false, true>), dim3((g.N + 63) / 64, (g.M + 127) / 128, 1), dim3(512), lds4, st, g);
+        break;
+    case PT_TOMP_R_GEMM_PS4:
+        hipLaunchKernelGGL((k_gemm_ps<4, 2, 2, 2, false>), dim3((g.N + 63) / 64, (g.M + 127) / 128, 1), dim3(512), lds4, st, g);
+        break;
+    case PT_TOMP_R_GEMM_PS4_SPLITK_WIDE:
+        hipLaunchKernelGGL((k_gemm_ps<4, 2, 2, 2, true, true>), dim3((g.M + 127) / 128, (g.N + 63) / 64, nz), dim3(512), lds4, st, g);
+        break;
+    case PT_TOMP_R_GEMM_PS4_SPLITK:
+        hipLaunchKernelGGL((k_gemm_ps<4, 2, 2, 2, true>), dim3((g.M + 127) / 128, (g.N + 63) / 64, nz), dim3(512), lds4, st, g);
+        break;
+    case PT_TOMP_R_GEMM_BIG:
+        hipLaunchKernelGGL(k_gemm_big, dim3((g.N + 127) / 128, (g.M + 127) / 128, nz), dim3(512), 2 * GB_STAGE * sizeof(float),
+                           st, g);
+        break;
+    case PT_TOMP_R_GEMM_CONV_GN:
+        hipLaunchKernelGGL((k_gemm<32, 32, 2>), dim3((g.N + 31) / 32, gy, nz), dim3(256), 0, st, g);
+        break;
+    case PT_TOMP_R_GEMM_CONV:
+        hipLaunchKernelGGL((k_gemm<32, 32, 1>), dim3((g.N + 31) / 32, gy, nz), dim3(256), 0, st, g);
+        break;
+    case PT_TOMP_R_GEMM_T64:
+        gs.swizzle = p.swizzle;
+        hipLaunchKernelGGL((k_gemm<64, 64, 0, 32>), dim3((g.N + 63) / 64, gy, 1), dim3(256), 0, st, gs);
+        break;
+    default:                                                        // PT_TOMP_R_GEMM_T32, _SWZ, _SWZ_PAD
+        gs.swizzle = p.swizzle;
         if (g.batch) gs.ksteps = 0;
-        hipLaunchKernelGGL((k_gemm<32, 32, 0>), dim3((g.N + 31) / 32, gs.swizzle ? (gy + 7) / 8 * 8 : gy, nz), dim3(256), 0,
-                           st, gs);
+        hipLaunchKernelGGL((k_gemm<32, 32, 0>), dim3((g.N + 31) / 32, gy, nz), dim3(256), 0, st, gs);
+        break;
     }
     PT_CHECK_LAUNCH();
     return PT_OK;

@@ -30,6 +30,18 @@
 
 namespace {
 
+// A launch of this file that no dispatcher stands in front of: with a route log (the host-only query) its id is noted and nothing is
+// queued; without one the kernel is launched and the launch status checked.  `log` is the enclosing function's PtRouteLog*.
+#define PT_TOMP_LAUNCH(ID, ...)                   \
+    do {                                          \
+        if (log) {                                \
+            pt_route_note(log, ID);               \
+        } else {                                  \
+            hipLaunchKernelGGL(__VA_ARGS__);      \
+            PT_CHECK_LAUNCH();                    \
+        }                                         \
+    } while (0)
+
 // ------------------------------------------------------------------------------------------------------------------
 // fp32 flash attention over the packed (rows, 3D) q|k|v projections
 // ------------------------------------------------------------------------------------------------------------------
@@ -230,6 +242,23 @@ __global__ __launch_bounds__(512) void k_attn(AttnArgs a) {
     }
 }
 
+// head width -> instantiation (dims_check admits 16 / 32 / 64 only)
+int attn_route(int HD) { return HD == 32 ? PT_TOMP_R_ATTN32 : HD == 16 ? PT_TOMP_R_ATTN16 : PT_TOMP_R_ATTN64; }
+
+int launch_attn(const AttnArgs& at, int B, hipStream_t st, PtRouteLog* log) {
+    const int route = attn_route(at.D / at.nhead);
+    if (log) {
+        pt_route_note(log, route);
+        return PT_OK;
+    }
+    const dim3 ag((at.L + 63) / 64, at.nhead, B);
+    if (route == PT_TOMP_R_ATTN32) hipLaunchKernelGGL((k_attn<32>), ag, dim3(512), 0, st, at);
+    else if (route == PT_TOMP_R_ATTN16) hipLaunchKernelGGL((k_attn<16>), ag, dim3(512), 0, st, at);
+    else hipLaunchKernelGGL((k_attn<64>), ag, dim3(512), 0, st, at);
+    PT_CHECK_LAUNCH();
+    return PT_OK;
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // row LayerNorm, one wavefront per row (D % 64 == 0, D <= 512); in-place safe
 // ------------------------------------------------------------------------------------------------------------------
@@ -326,21 +355,42 @@ static bool ln_rows_wide_ok(const float* in, const float* out, const float* gam,
     return D == 256 && ((uintptr_t)in % 16 == 0) && ((uintptr_t)out % 16 == 0) && ((uintptr_t)gam % 16 == 0) && ((uintptr_t)bet % 16 == 0);
 }
 
-// Returns PT_ERR_UNSUPPORTED (nothing queued) when extra operands are given that only the 256-wide vector kernel serves and that
-// kernel cannot be used: dropping in2 / in3 / the second norm silently would lose the split-K half, the residual or a LayerNorm.
-static int launch_ln_rows(const float* in, float* out, const float* gam, const float* bet, int rows, int D, hipStream_t st,
-                          const float* in2 = nullptr, const float* in3 = nullptr, const float* gam2 = nullptr,
-                          const float* bet2 = nullptr, const float* in4 = nullptr, const float* in5 = nullptr) {
-    const dim3 grid((rows + 3) / 4), block(256);
+// The kernel launch_ln_rows runs (PT_TOMP_R_LN*), from the operands alone.  PT_ERR_UNSUPPORTED when extra operands are given that only
+// the 256-wide vector kernel serves and that kernel cannot be used: dropping in2 / in3 / the second norm silently would lose the split-K
+// half, the residual or a LayerNorm.
+static int ln_rows_route(const float* in, const float* out, const float* gam, const float* bet, int D, const float* in2, const float* in3,
+                         const float* gam2, const float* bet2, const float* in4, const float* in5, int* route) {
     const bool al = ((uintptr_t)in % 16 == 0) && ((uintptr_t)out % 16 == 0) && ((uintptr_t)gam % 16 == 0) && ((uintptr_t)bet % 16 == 0) &&
                     ((uintptr_t)in2 % 16 == 0) && ((uintptr_t)in3 % 16 == 0) && ((uintptr_t)gam2 % 16 == 0) && ((uintptr_t)bet2 % 16 == 0) &&
                     ((uintptr_t)in4 % 16 == 0) && ((uintptr_t)in5 % 16 == 0);
     if (!(D == 256 && al) && (in2 || in3 || gam2 || bet2 || in4 || in5)) return PT_ERR_UNSUPPORTED;
     if ((in4 == nullptr) != (in5 == nullptr) || (in4 && !in2)) return PT_ERR_UNSUPPORTED;
-    if (D == 256 && al) hipLaunchKernelGGL(k_ln_rows_t<4>, grid, block, 0, st, in, out, gam, bet, rows, in2, in3, gam2, bet2, in4, in5);
-    else if (D == 128) hipLaunchKernelGGL(k_ln_rows_t<2>, grid, block, 0, st, in, out, gam, bet, rows);
-    else if (D == 64) hipLaunchKernelGGL(k_ln_rows_t<1>, grid, block, 0, st, in, out, gam, bet, rows);
-    else hipLaunchKernelGGL(k_ln_rows, grid, block, 0, st, in, out, gam, bet, rows, D);
+    if (D == 256 && al) *route = gam2 ? PT_TOMP_R_LN256_DOUBLE : in4 ? PT_TOMP_R_LN256_SPLIT4 : (in2 || in3) ? PT_TOMP_R_LN256_SPLIT2 : PT_TOMP_R_LN256;
+    else if (D == 128) *route = PT_TOMP_R_LN128;
+    else if (D == 64) *route = PT_TOMP_R_LN64;
+    else *route = PT_TOMP_R_LN_GENERIC;
+    return PT_OK;
+}
+
+// Nothing is queued when the status is not PT_OK, or when a route log is given (the route is noted instead).
+static int launch_ln_rows(const float* in, float* out, const float* gam, const float* bet, int rows, int D, hipStream_t st, PtRouteLog* log,
+                          const float* in2 = nullptr, const float* in3 = nullptr, const float* gam2 = nullptr,
+                          const float* bet2 = nullptr, const float* in4 = nullptr, const float* in5 = nullptr) {
+    int route = 0;
+    const int rc = ln_rows_route(in, out, gam, bet, D, in2, in3, gam2, bet2, in4, in5, &route);
+    if (rc) return rc;
+    if (log) {
+        pt_route_note(log, route);
+        return PT_OK;
+    }
+    const dim3 grid((rows + 3) / 4), block(256);
+    switch (route) {
+    case PT_TOMP_R_LN128: hipLaunchKernelGGL(k_ln_rows_t<2>, grid, block, 0, st, in, out, gam, bet, rows); break;
+    case PT_TOMP_R_LN64: hipLaunchKernelGGL(k_ln_rows_t<1>, grid, block, 0, st, in, out, gam, bet, rows); break;
+    case PT_TOMP_R_LN_GENERIC: hipLaunchKernelGGL(k_ln_rows, grid, block, 0, st, in, out, gam, bet, rows, D); break;
+    default: hipLaunchKernelGGL(k_ln_rows_t<4>, grid, block, 0, st, in, out, gam, bet, rows, in2, in3, gam2, bet2, in4, in5); break;
+    }
+    PT_CHECK_LAUNCH();
     return PT_OK;
 }
 
@@ -763,28 +813,43 @@ __global__ __launch_bounds__(256) void k_gemv_dec(const float* __restrict__ Wt, 
     }
 }
 
-int launch_gemv(const GemvArgs& a, hipStream_t st) {
+// The kernel launch_gemv runs (PT_TOMP_R_GEMV_*), from the arguments alone
+int gemv_route(const GemvArgs& a, int* route) {
     if (a.B > 8 || a.K % 64 != 0 || (a.rg && a.N % 64 != 0)) return PT_ERR_UNSUPPORTED;
     const bool v4 = a.K % 256 == 0 && (!a.rg || a.N % 256 == 0);
     const int nch = a.K / 256;
     auto al16 = [](const void* p) { return ((uintptr_t)p % 16) == 0; };
     const bool dec = v4 && a.B <= 2 && (nch == 1 || nch == 2 || nch == 4 || nch == 8) && a.N < 65536 && (!a.rg || (a.res && a.N <= 2048)) &&
                      al16(a.Wt) && al16(a.x) && al16(a.xg) && al16(a.xb) && al16(a.xadd) && al16(a.res);
-    if (dec) {
+    if (dec) *route = nch == 1 ? PT_TOMP_R_GEMV_DEC1 : nch == 2 ? PT_TOMP_R_GEMV_DEC2 : nch == 4 ? PT_TOMP_R_GEMV_DEC4 : PT_TOMP_R_GEMV_DEC8;
+    else *route = v4 ? PT_TOMP_R_GEMV_V4 : PT_TOMP_R_GEMV_V1;
+    return PT_OK;
+}
+
+int launch_gemv(const GemvArgs& a, hipStream_t st, PtRouteLog* log = nullptr) {
+    int route = 0;
+    const int rc = gemv_route(a, &route);
+    if (rc) return rc;
+    if (log) {
+        pt_route_note(log, route);
+        return PT_OK;
+    }
+    const dim3 grid((a.N + 3) / 4), block(256);
+    if (route == PT_TOMP_R_GEMV_V4) {
+        hipLaunchKernelGGL((k_gemv<4>), grid, block, 0, st, a);
+    } else if (route == PT_TOMP_R_GEMV_V1) {
+        hipLaunchKernelGGL((k_gemv<1>), grid, block, 0, st, a);
+    } else {
         const unsigned nk = (unsigned)a.N | ((unsigned)a.K << 16);
         const unsigned flags = (unsigned)a.B | ((a.relu ? 1u : 0u) << 4) | ((a.rg ? 1u : 0u) << 5) | ((unsigned)(a.rg ? a.N / 256 : 0) << 8);
         const GemvLate l{(pt_gcf)a.bias, (pt_gcf)a.rg, (pt_gcf)a.rb, (pt_gf)a.out};
-        const dim3 grid((a.N + 3) / 4), block(256);
 #define PT_GEMV_DEC(NC) hipLaunchKernelGGL((k_gemv_dec<NC>), grid, block, 0, st, a.Wt, a.x, a.xg, a.xb, a.xadd, a.res, nk, flags, l)
-        if (nch == 1) PT_GEMV_DEC(1);
-        else if (nch == 2) PT_GEMV_DEC(2);
-        else if (nch == 4) PT_GEMV_DEC(4);
+        if (route == PT_TOMP_R_GEMV_DEC1) PT_GEMV_DEC(1);
+        else if (route == PT_TOMP_R_GEMV_DEC2) PT_GEMV_DEC(2);
+        else if (route == PT_TOMP_R_GEMV_DEC4) PT_GEMV_DEC(4);
         else PT_GEMV_DEC(8);
 #undef PT_GEMV_DEC
-    } else if (v4)
-        hipLaunchKernelGGL((k_gemv<4>), dim3((a.N + 3) / 4), dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL((k_gemv<1>), dim3((a.N + 3) / 4), dim3(256), 0, st, a);
+    }
     PT_CHECK_LAUNCH();
     return PT_OK;
 }
@@ -1215,13 +1280,20 @@ extern "C" size_t pt_tomp_predict_ws_bytes(const pt_tomp_dims* d, int n_train, i
     return ws_carve(d, B, n_train).total * sizeof(float);
 }
 
-extern "C" int pt_tomp_linear_f32(const float* weight, const float* bias, const float* x, float* y, int B, int N, int K,
-                                  int relu, void* stream) {
+namespace {
+int tomp_linear_impl(const float* weight, const float* bias, const float* x, float* y, int B, int N, int K, int relu, void* stream,
+                     PtRouteLog* log) {
     if (!weight || !x || !y) return PT_ERR_NULL;
     if (B <= 0 || N <= 0 || K <= 0) return PT_ERR_SHAPE;
     GemvArgs a{};
     a.Wt = weight; a.bias = bias; a.N = N; a.K = K; a.x = x; a.relu = relu; a.B = B; a.out = y;
-    return launch_gemv(a, (hipStream_t)stream);
+    return launch_gemv(a, (hipStream_t)stream, log);
+}
+}  // namespace
+
+extern "C" int pt_tomp_linear_f32(const float* weight, const float* bias, const float* x, float* y, int B, int N, int K,
+                                  int relu, void* stream) {
+    return tomp_linear_impl(weight, bias, x, y, B, N, K, relu, stream, nullptr);
 }
 
 extern "C" size_t pt_tomp_prepared_floats(const pt_tomp_dims* d) {
@@ -1269,11 +1341,12 @@ extern "C" int pt_tomp_prepare_f32(const pt_tomp_dims* d, const float* params, f
     return PT_OK;
 }
 
-extern "C" int pt_tomp_predict_f32(const pt_tomp_dims* d, const float* params, const float* prepared, const float* pos,
-                                   const float* train_feat,
-                                   const float* test_feat, const float* train_label, const float* train_ltrb,
-                                   int n_train, int n_seq, int parallel, int num_gth_frames, float* filters,
-                                   float* enc_feat, void* ws, size_t ws_bytes, void* stream) {
+namespace {
+// log == nullptr: the predictor.  Otherwise the same walk through the same dispatchers with nothing queued: every launch site notes its
+// route instead (pt_tomp_predict_routes).  Host code only derives addresses from the pointers, it never reads through them.
+int tomp_predict_impl(const pt_tomp_dims* d, const float* params, const float* prepared, const float* pos, const float* train_feat,
+                      const float* test_feat, const float* train_label, const float* train_ltrb, int n_train, int n_seq, int parallel,
+                      int num_gth_frames, float* filters, float* enc_feat, void* ws, size_t ws_bytes, void* stream, PtRouteLog* log) {
     if (!params || !prepared || !pos || !train_feat || !test_feat || !train_label || !train_ltrb || !filters || !enc_feat || !ws)
         return PT_ERR_NULL;
     int rc = dims_check(d);
@@ -1303,19 +1376,17 @@ extern "C" int pt_tomp_predict_f32(const pt_tomp_dims* d, const float* params, c
             t.cp_src[1] = prepared + pl0.qk0; t.cp_dst[1] = base + cv.qk; t.cp_n[1] = NH * D;
         }
         dec0_const = t.cp_src[0] != nullptr;
-        hipLaunchKernelGGL(k_tomp_tokens, dim3((HW + 31) / 32, (D + 31) / 32, (n_train + 1) * B), dim3(256), 0, st, t);
-        PT_CHECK_LAUNCH();
+        PT_TOMP_LAUNCH(PT_TOMP_R_TOKENS, k_tomp_tokens, dim3((HW + 31) / 32, (D + 31) / 32, (n_train + 1) * B), dim3(256), 0, st, t);
         BoxArgs bx{train_ltrb, P + po.bw1, P + po.bb1, P + po.bn1, P + po.bn2, base + cv.E1, base + cv.bnsc,
                    base + cv.bnsh, n_train, n_seq, parallel ? 1 : 0, D, D4, HW};
         const long tot = (long)B * Ltr * D4;
-        hipLaunchKernelGGL(k_tomp_box1, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, bx);
-        PT_CHECK_LAUNCH();
+        PT_TOMP_LAUNCH(PT_TOMP_R_BOX1, k_tomp_box1, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, bx);
         GemmArgs g = gemm_args(base + cv.E1, D4, (long)B * Ltr, P + po.bw2, B * Ltr, D, D4, P + po.bb2, base + cv.E2, D);
         g.scale = base + cv.bnsc; g.shift = base + cv.bnsh; g.relu = 1;
-        if ((rc = launch_gemm(g, st))) return rc;
+        if ((rc = launch_gemm(g, st, false, log))) return rc;
         g = gemm_args(base + cv.E2, D, (long)B * Ltr, P + po.bw3, B * Ltr, D, D, P + po.bb3, X, D);
         g.R = X; g.c_seg = Ltr; g.c_segstride = L;
-        if ((rc = launch_gemm(g, st))) return rc;
+        if ((rc = launch_gemm(g, st, false, log))) return rc;
     }
     AttnArgs at{};
     at.qkv = QKV; at.qkv_bytes = (unsigned)((long)rows * 3 * D * 4); at.out = AO; at.L = L; at.D = D; at.nhead = NH;
@@ -1330,22 +1401,17 @@ extern "C" int pt_tomp_predict_f32(const pt_tomp_dims* d, const float* params, c
         const EncOff& e = po.enc[i];
         GemmArgs g = gemm_args(X, D, rows, P + e.sa.w_in, rows, 3 * D, D, P + e.sa.b_in, QKV, 3 * D);
         g.pos = pos; g.pos_bytes = (unsigned)((long)HW * D * 4); g.pos_cols = 2 * D; g.L = L; g.HW = HW;
-        if ((rc = launch_gemm(g, st))) return rc;
-        const dim3 ag((L + 63) / 64, NH, B);
-        if (HD == 32) hipLaunchKernelGGL((k_attn<32>), ag, dim3(512), 0, st, at);
-        else if (HD == 16) hipLaunchKernelGGL((k_attn<16>), ag, dim3(512), 0, st, at);
-        else hipLaunchKernelGGL((k_attn<64>), ag, dim3(512), 0, st, at);
-        PT_CHECK_LAUNCH();
+        if ((rc = launch_gemm(g, st, false, log))) return rc;
+        if ((rc = launch_attn(at, B, st, log))) return rc;
         g = gemm_args(AO, D, rows, P + e.sa.w_out, rows, D, D, P + e.sa.b_out, Y, D);
         g.R = X;
-        if ((rc = launch_gemm(g, st))) return rc;
+        if ((rc = launch_gemm(g, st, false, log))) return rc;
         // (norm1 folded into the FFN's first product saved a launch per layer and lost: frame 0.885 -> 0.894 ms,
         // profiles/r06p_tomp_ln1_fold.txt)
-        if ((rc = launch_ln_rows(Y, X, P + e.n1g, P + e.n1b, rows, D, st))) return rc;
-        PT_CHECK_LAUNCH();
+        if ((rc = launch_ln_rows(Y, X, P + e.n1g, P + e.n1b, rows, D, st, log))) return rc;
         g = gemm_args(X, D, rows, P + e.w1, rows, ff, D, P + e.b1, Hd, ff);
         g.relu = 1;
-        if ((rc = launch_gemm(g, st))) return rc;
+        if ((rc = launch_gemm(g, st, false, log))) return rc;
         const long rD = (long)rows * D;
         if ((ff / 64) % 4 == 0 && rows >= 1024 && D % 64 == 0 && cv.AO == cv.QKV + 3 * (size_t)rD &&
             ln_rows_wide_ok(QKV, X, P + e.n2g, P + e.n2b, D)) {
@@ -1355,16 +1421,14 @@ extern "C" int pt_tomp_predict_f32(const pt_tomp_dims* d, const float* params, c
             // QKV[0..2], AO -- all free here -- that meet, with the residual, in the LayerNorm
             g = gemm_args(Hd, ff, rows, P + e.w2, rows, D, ff, P + e.b2, QKV, D);
             g.ksteps = ff / 64 / 4; g.c_zstride = rD;
-            if ((rc = launch_gemm(g, st))) return rc;
-            if ((rc = launch_ln_rows(QKV, X, P + e.n2g, P + e.n2b, rows, D, st, QKV + rD, X, nullptr, nullptr, QKV + 2 * rD, AO))) return rc;
-            PT_CHECK_LAUNCH();
+            if ((rc = launch_gemm(g, st, false, log))) return rc;
+            if ((rc = launch_ln_rows(QKV, X, P + e.n2g, P + e.n2b, rows, D, st, log, QKV + rD, X, nullptr, nullptr, QKV + 2 * rD, AO))) return rc;
             continue;
         }
         g = gemm_args(Hd, ff, rows, P + e.w2, rows, D, ff, P + e.b2, Y, D);
         g.R = X;
-        if ((rc = launch_gemm(g, st))) return rc;
-        if ((rc = launch_ln_rows(Y, X, P + e.n2g, P + e.n2b, rows, D, st))) return rc;
-        PT_CHECK_LAUNCH();
+        if ((rc = launch_gemm(g, st, false, log))) return rc;
+        if ((rc = launch_ln_rows(Y, X, P + e.n2g, P + e.n2b, rows, D, st, log))) return rc;
     }
     // ---- decoder (transformer.py:224-238), one query per batch row; T = LayerNorm(pre) is applied by the consumers
     // (base + cv.zero was cleared by k_tomp_tokens)
@@ -1376,6 +1440,8 @@ extern "C" int pt_tomp_predict_f32(const pt_tomp_dims* d, const float* params, c
     const float* tpre = base + cv.zero;                            // pre-LayerNorm state entering the layer
     const float *tg = nullptr, *tb = nullptr;                      // its LayerNorm (none for the initial zeros)
     const PrepLayout pl = prep_layout(D, NH, d->n_dec);
+    // layer 0's state after self-attention and its folded query: copied by k_tomp_tokens (no launch of their own) or two GEMVs
+    if (log && d->n_dec > 0) pt_route_note(log, dec0_const ? PT_TOMP_R_DEC0_CONST : PT_TOMP_R_DEC0_LIVE);
     for (int i = 0; i < d->n_dec; ++i) {
         const DecOff& dc = po.dec[i];
         const PrepOff& pp = pl.dec[i];
@@ -1384,50 +1450,54 @@ extern "C" int pt_tomp_predict_f32(const pt_tomp_dims* d, const float* params, c
         // self-attention over one token (softmax of a single key is 1), folded: Pa = t + (Wo Wv) t + (Wo bv + bo)
         v.Wt = prepared + pp.wsa; v.bias = prepared + pp.bsa; v.N = D; v.K = D; v.x = tpre; v.xg = tg; v.xb = tb;
         v.res = tpre; v.rg = tg; v.rb = tb; v.B = B; v.out = Pa;
-        if (!(i == 0 && dec0_const) && (rc = launch_gemv(v, st))) return rc;        // layer 0: written by k_tomp_tokens
+        if (!(i == 0 && dec0_const) && (rc = launch_gemv(v, st, log))) return rc;        // layer 0: written by k_tomp_tokens
         // cross-attention query folded onto the keys: qk[b][h] = Wk_h^T (Wq_h (LN1(Pa) + query_pos) + bq_h) / sqrt(HD)
         v = GemvArgs{};
         v.Wt = prepared + pp.mq; v.bias = prepared + pp.cq; v.N = NH * D; v.K = D; v.x = Pa; v.xg = P + dc.n1g;
         v.xb = P + dc.n1b; v.xadd = qpos; v.B = B; v.out = base + cv.qk;     // one query_pos row for all batch rows
-        if (!(i == 0 && dec0_const) && (rc = launch_gemv(v, st))) return rc;
-        hipLaunchKernelGGL(k_dec_scores, dim3((L + 15) / 16, B), dim3(64), 0, st, da);
-        PT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_dec_ctx, dim3(D / 16, B), dim3(1024),
-                           ((size_t)NH * ((L + 3) & ~3) + 16 + 16 * 256) * sizeof(float), st, da);
-        PT_CHECK_LAUNCH();
+        if (!(i == 0 && dec0_const) && (rc = launch_gemv(v, st, log))) return rc;
+        PT_TOMP_LAUNCH(PT_TOMP_R_DEC_SCORES, k_dec_scores, dim3((L + 15) / 16, B), dim3(64), 0, st, da);
+        PT_TOMP_LAUNCH(PT_TOMP_R_DEC_CTX, k_dec_ctx, dim3(D / 16, B), dim3(1024),
+                       ((size_t)NH * ((L + 3) & ~3) + 16 + 16 * 256) * sizeof(float), st, da);
         // value projection + out_proj folded over the heads' attention-weighted memories, residual LN1(Pa)
         v = GemvArgs{};
         v.Wt = prepared + pp.wov; v.bias = prepared + pp.bov; v.N = D; v.K = NH * D; v.x = base + cv.ctx;
         v.res = Pa; v.rg = P + dc.n1g; v.rb = P + dc.n1b; v.B = B; v.out = Pb;
-        if ((rc = launch_gemv(v, st))) return rc;
+        if ((rc = launch_gemv(v, st, log))) return rc;
         // feed-forward on LN2(Pb)
         v = GemvArgs{};
         v.Wt = P + dc.w1; v.bias = P + dc.b1; v.N = ff; v.K = D; v.x = Pb; v.xg = P + dc.n2g;
         v.xb = P + dc.n2b; v.relu = 1; v.B = B; v.out = base + cv.hdn;
-        if ((rc = launch_gemv(v, st))) return rc;
+        if ((rc = launch_gemv(v, st, log))) return rc;
         v = GemvArgs{};
         v.Wt = P + dc.w2; v.bias = P + dc.b2; v.N = D; v.K = ff; v.x = base + cv.hdn;
         v.res = Pb; v.rg = P + dc.n2g; v.rb = P + dc.n2b; v.B = B; v.out = Pc;
-        if ((rc = launch_gemv(v, st))) return rc;
+        if ((rc = launch_gemv(v, st, log))) return rc;
         tpre = Pc; tg = P + dc.n3g; tb = P + dc.n3b;
     }
     // norm3 of the last layer, then the decoder's final norm (transformer.py:141-142)
     if (d->n_dec > 0 && ln_rows_wide_ok(tpre, filters, tg, tb, D)) {
-        if ((rc = launch_ln_rows(tpre, filters, tg, tb, B, D, st, nullptr, nullptr, P + po.dng, P + po.dnb))) return rc;   // both norms, one launch
-        PT_CHECK_LAUNCH();
+        if ((rc = launch_ln_rows(tpre, filters, tg, tb, B, D, st, log, nullptr, nullptr, P + po.dng, P + po.dnb))) return rc;   // both norms, one launch
     } else {
         if (d->n_dec > 0) {
-            if ((rc = launch_ln_rows(tpre, base + cv.a, tg, tb, B, D, st))) return rc;
-            PT_CHECK_LAUNCH();
+            if ((rc = launch_ln_rows(tpre, base + cv.a, tg, tb, B, D, st, log))) return rc;
             tpre = base + cv.a;
         }
-        if ((rc = launch_ln_rows(tpre, filters, P + po.dng, P + po.dnb, B, D, st))) return rc;
-        PT_CHECK_LAUNCH();
+        if ((rc = launch_ln_rows(tpre, filters, P + po.dng, P + po.dnb, B, D, st, log))) return rc;
     }
-    hipLaunchKernelGGL(k_tokens_to_nchw, dim3((HW + 31) / 32, (D + 31) / 32, B), dim3(256), 0, st, X, enc_feat, B, L, D,
-                       HW, Ltr);
-    PT_CHECK_LAUNCH();
+    PT_TOMP_LAUNCH(PT_TOMP_R_TO_NCHW, k_tokens_to_nchw, dim3((HW + 31) / 32, (D + 31) / 32, B), dim3(256), 0, st, X, enc_feat, B, L, D,
+                   HW, Ltr);
     return PT_OK;
+}
+}  // namespace
+
+extern "C" int pt_tomp_predict_f32(const pt_tomp_dims* d, const float* params, const float* prepared, const float* pos,
+                                   const float* train_feat,
+                                   const float* test_feat, const float* train_label, const float* train_ltrb,
+                                   int n_train, int n_seq, int parallel, int num_gth_frames, float* filters,
+                                   float* enc_feat, void* ws, size_t ws_bytes, void* stream) {
+    return tomp_predict_impl(d, params, prepared, pos, train_feat, test_feat, train_label, train_ltrb, n_train, n_seq, parallel,
+                             num_gth_frames, filters, enc_feat, ws, ws_bytes, stream, nullptr);
 }
 
 // ---- DenseBoxRegressor (heads.py:119-141) ------------------------------------------------------------------------
@@ -1471,8 +1541,15 @@ extern "C" size_t pt_tomp_bbreg_ws_bytes(int n, int d_model, int H, int W) {
     return reg_carve(n, d_model, H, W).total * sizeof(float);
 }
 
-extern "C" int pt_tomp_bbreg_f32(const float* params, const float* feat, const float* filter, float* ltrb, int n,
-                                 int d_model, int H, int W, void* ws, size_t ws_bytes, void* stream) {
+namespace {
+// GroupNorm + ReLU of tower layer i applied by layer i + 1's loader (mfma_gemm.h: gn_*) instead of k_gn_apply: the fused loader takes
+// at most GEMM_GN_MAX_SLICES slices per image, maps of at least one 32-row tile and 16-byte aligned affine parameters
+bool reg_fuse_gn(int slices, int HW, int D, const float* gg, const float* gb) {
+    return slices <= GEMM_GN_MAX_SLICES && HW >= 32 && ((uintptr_t)gg % 16) == 0 && ((uintptr_t)gb % 16) == 0 && (D % 4) == 0;
+}
+
+int tomp_bbreg_impl(const float* params, const float* feat, const float* filter, float* ltrb, int n, int d_model, int H, int W, void* ws,
+                    size_t ws_bytes, void* stream, PtRouteLog* log) {
     if (!params || !feat || !filter || !ltrb || !ws) return PT_ERR_NULL;
     if (n <= 0 || d_model <= 0 || H <= 0 || W <= 0) return PT_ERR_SHAPE;
     if (d_model % 64 != 0 || d_model > 512) return PT_ERR_UNSUPPORTED;
@@ -1485,19 +1562,17 @@ extern "C" int pt_tomp_bbreg_f32(const float* params, const float* feat, const f
     float *fproj = base + cv.fproj, *part = base + cv.part, *stats = base + cv.stats;
     GemvArgs v{};
     v.Wt = params + ro.lw; v.bias = params + ro.lb; v.N = D; v.K = D; v.x = filter; v.B = 1; v.out = fproj;
-    int rc = launch_gemv(v, st);
+    int rc = launch_gemv(v, st, log);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_reg_attend, dim3((HW + 31) / 32, n), dim3(256), ((size_t)D * 33 + 32) * sizeof(float), st, feat,
-                       fproj, base + cv.T0, D, HW);
-    PT_CHECK_LAUNCH();
+    PT_TOMP_LAUNCH(PT_TOMP_R_REG_ATTEND, k_reg_attend, dim3((HW + 31) / 32, n), dim3(256), ((size_t)D * 33 + 32) * sizeof(float), st, feat,
+                   fproj, base + cv.T0, D, HW);
     // each 3x3 convolution = 9 per-tap partial GEMMs (one K-slice of Cin per tap) reduced by the GroupNorm statistics pass
     float *src = base + cv.T0, *dst = base + cv.T1;
     const long zs = (long)M * D;
     // Round 4: GroupNorm + ReLU of layer i are applied by layer i + 1's loader (mfma_gemm.h: gn_*): the tower is conv -> reduce per
     // layer, the activations between two layers exist only as raw sums + slice statistics (k_gn_apply stays for shapes the fused
     // loader does not take: more than GEMM_GN_MAX_SLICES slices per image, maps smaller than a 32-row tile)
-    const bool fuse_gn = cv.slices <= GEMM_GN_MAX_SLICES && HW >= 32 && ((uintptr_t)(params + ro.gg[0]) % 16) == 0 &&
-                         ((uintptr_t)(params + ro.gb[0]) % 16) == 0 && (D % 4) == 0;
+    const bool fuse_gn = reg_fuse_gn(cv.slices, HW, D, params + ro.gg[0], params + ro.gb[0]);
     auto with_gn = [&](GemmArgs& g, int prev) {
         if (!fuse_gn || prev < 0) return;
         g.gn_stats = stats; g.gn_slices = cv.slices; g.gn_count = HW * D;
@@ -1507,23 +1582,73 @@ extern "C" int pt_tomp_bbreg_f32(const float* params, const float* feat, const f
         GemmArgs g = gemm_args(src, D, M, params + ro.cw[i], M, D, 9 * D, params + ro.cb[i], part, D);
         g.H = H; g.Wd = W; g.Cin = D; g.HW = HW; g.ksteps = D / 64; g.c_zstride = zs;
         with_gn(g, i - 1);
-        if ((rc = launch_gemm(g, st, true))) return rc;
-        hipLaunchKernelGGL(k_gn_reduce, dim3(cv.slices, n), dim3(256), 0, st, part, 9, zs, dst, stats, HW * D);
-        PT_CHECK_LAUNCH();
+        if ((rc = launch_gemm(g, st, true, log))) return rc;
+        PT_TOMP_LAUNCH(PT_TOMP_R_GN_REDUCE, k_gn_reduce, dim3(cv.slices, n), dim3(256), 0, st, part, 9, zs, dst, stats, HW * D);
         if (!fuse_gn) {
-            hipLaunchKernelGGL(k_gn_apply, dim3(cv.slices, n), dim3(256), 0, st, dst, stats, params + ro.gg[i],
-                               params + ro.gb[i], D, HW * D);
-            PT_CHECK_LAUNCH();
+            PT_TOMP_LAUNCH(PT_TOMP_R_GN_APPLY, k_gn_apply, dim3(cv.slices, n), dim3(256), 0, st, dst, stats, params + ro.gg[i],
+                           params + ro.gb[i], D, HW * D);
         }
         std::swap(src, dst);
     }
     GemmArgs g = gemm_args(src, D, M, params + ro.fw, M, 4, 9 * D, params + ro.fb, part, 4);
     g.H = H; g.Wd = W; g.Cin = D; g.HW = HW; g.ksteps = D / 64; g.c_zstride = (long)M * 4;
     with_gn(g, 3);
-    if ((rc = launch_gemm(g, st, true))) return rc;
-    hipLaunchKernelGGL(k_reg_finish, dim3((M * 4 + 255) / 256), dim3(256), 0, st, part, 9, (long)M * 4, ltrb, M, HW);
-    PT_CHECK_LAUNCH();
+    if ((rc = launch_gemm(g, st, true, log))) return rc;
+    PT_TOMP_LAUNCH(PT_TOMP_R_REG_FINISH, k_reg_finish, dim3((M * 4 + 255) / 256), dim3(256), 0, st, part, 9, (long)M * 4, ltrb, M, HW);
     return PT_OK;
+}
+}  // namespace
+
+extern "C" int pt_tomp_bbreg_f32(const float* params, const float* feat, const float* filter, float* ltrb, int n,
+                                 int d_model, int H, int W, void* ws, size_t ws_bytes, void* stream) {
+    return tomp_bbreg_impl(params, feat, filter, ltrb, n, d_model, H, W, ws, ws_bytes, stream, nullptr);
+}
+
+// ---- host-only route queries (include/pt_hot.h: pt_tomp_*_routes) -----------------------------------------------------------------
+// Each walks the entry point's own code with a route log and stand-in addresses: 256-byte aligned, as the Python wrappers allocate, and
+// far enough apart that no two buffers overlap; the pack / prepared / workspace offsets added to them are the real ones, so every
+// alignment predicate sees what a call sees.  Nothing is launched and no device is touched.
+namespace {
+float* route_fake(int k) { return reinterpret_cast<float*>((uintptr_t)(k + 1) << 40); }
+
+int route_finish(int rc, const PtRouteLog& log, int* routes, int cap, int* n_routes) {
+    if (rc == PT_OK && log.n > cap) rc = PT_ERR_WORKSPACE;
+    if (rc != PT_OK) {
+        for (int i = 0; i < cap; ++i) routes[i] = 0;
+        *n_routes = 0;
+        return rc;
+    }
+    for (int i = log.n; i < cap; ++i) routes[i] = 0;
+    *n_routes = log.n;
+    return PT_OK;
+}
+}  // namespace
+
+extern "C" int pt_tomp_predict_routes(const pt_tomp_dims* d, int n_train, int n_seq, int parallel, int* routes, int cap, int* n_routes) {
+    if (!routes || !n_routes || !d) return PT_ERR_NULL;
+    if (cap < 0) return PT_ERR_SHAPE;
+    PtRouteLog log{routes, cap, 0};
+    const int rc = tomp_predict_impl(d, route_fake(0), route_fake(1), route_fake(2), route_fake(3), route_fake(4), route_fake(5),
+                                     route_fake(6), n_train, n_seq, parallel, 0, route_fake(7), route_fake(8), route_fake(9), ~(size_t)0,
+                                     nullptr, &log);
+    return route_finish(rc, log, routes, cap, n_routes);
+}
+
+extern "C" int pt_tomp_bbreg_routes(int n, int d_model, int H, int W, int* routes, int cap, int* n_routes) {
+    if (!routes || !n_routes) return PT_ERR_NULL;
+    if (cap < 0) return PT_ERR_SHAPE;
+    PtRouteLog log{routes, cap, 0};
+    const int rc = tomp_bbreg_impl(route_fake(0), route_fake(1), route_fake(2), route_fake(3), n, d_model, H, W, route_fake(4), ~(size_t)0,
+                                   nullptr, &log);
+    return route_finish(rc, log, routes, cap, n_routes);
+}
+
+extern "C" int pt_tomp_linear_routes(int B, int N, int K, int* routes, int cap, int* n_routes) {
+    if (!routes || !n_routes) return PT_ERR_NULL;
+    if (cap < 0) return PT_ERR_SHAPE;
+    PtRouteLog log{routes, cap, 0};
+    const int rc = tomp_linear_impl(route_fake(0), route_fake(1), route_fake(2), route_fake(3), B, N, K, 0, nullptr, &log);
+    return route_finish(rc, log, routes, cap, n_routes);
 }
 
 // ==================================================================================================================

@@ -12,6 +12,7 @@ import torch
 from conftest import load_golden
 from oracle import np_oracle as O
 from pytracking_amd import synth
+from tomp_cases import build_tomp_modules               # shared with tests/test_gpu_tomp_routes.py
 
 pytestmark = pytest.mark.gpu
 
@@ -936,27 +937,6 @@ def test_bench_trajectory_prdimp_closed_loop_40_frames():
 # ------------------------------------------------------------------------------------------------------
 # ToMP transformer model predictor
 # ------------------------------------------------------------------------------------------------------
-def build_tomp_modules(cfg, params, device):
-    """The mirrored FilterPredictor / LinearFilterClassifier / DenseBoxRegressor carrying the seeded parameters,
-    loaded through `load_state_dict(strict=True)` with the reference's key names."""
-    from pytracking_amd import transformer as TM
-    D = cfg["D"]
-    tr = TM.Transformer(d_model=D, nhead=cfg["nhead"], num_encoder_layers=cfg["n_enc"],
-                        num_decoder_layers=cfg["n_dec"], dim_feedforward=cfg["ff"])
-    pred = TM.FilterPredictor(tr, feature_sz=cfg["feature_sz"], use_test_frame_encoding=True)
-    cls = TM.LinearFilterClassifier(num_channels=D)
-    reg = TM.DenseBoxRegressor(num_channels=D)
-    for mod, pre in ((pred, "fp."), (cls, "cls."), (reg, "reg.")):
-        sd = {k[len(pre):]: torch.from_numpy(v.copy()) for k, v in params.items() if k.startswith(pre)}
-        if pre == "fp.":
-            sd["query_embed_fg_decoder.weight"] = sd["query_embed_fg.weight"]
-            for idx in (1, 4):
-                sd[f"box_encoding.{idx}.num_batches_tracked"] = torch.tensor(0)
-        mod.load_state_dict(sd, strict=True)
-        mod.to(device).eval()
-    return pred, cls, reg
-
-
 @pytest.mark.parametrize("name,cfg", [("tomp_small", "TOMP_SMALL"), ("tomp_full", "TOMP")])
 def test_tomp_predictor_golden(name, cfg):
     """predict_cls_bbreg_filters_parallel + classifier + box regressor vs the reference run (tomp.py:282-303)."""
