@@ -318,6 +318,24 @@ int pt_clf_head_f32(const float* feat, const float* weight_tap_major, float* out
                     float norm_scale, float eps, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Feature head at stride 1 or 2 -- the heads in front of the LWL / RTS learners:
+ *   `residual_basic_block(num_blocks=0, final_conv=True, l2norm=True)` (features.py:9-28), the target-model head of LWL and RTS
+ *     (lwl_net.py:173-177, rts_net.py:294-298): Conv2d(1024, 512, 3, padding=1, bias=False) + InstanceL2Norm on a 30 x 52 map, stride 1;
+ *   `residual_bottleneck(num_blocks=0, final_conv=True, l2norm=True, final_stride=2)` (features.py:49-73), the RTS classifier head
+ *     (rts_net.py:339-344): the same convolution at stride 2, 1024 x 30 x 52 -> 512 x 15 x 26.
+ *   feat (n, Cin, H, W); weight_tap_major (Cout, ky, kx, Cin) as for pt_clf_head_f32; out (n, Cout, Ho, Wo) with Ho = (H-1)/stride + 1,
+ *   Wo = (W-1)/stride + 1, = y * norm_scale * sqrt(Cout*Ho*Wo / (sum over the image of y^2 + eps)), y the zero-padded 3x3 convolution
+ *   at that stride (padding 1: output (oy, ox), tap (ky, kx) reads input (stride*oy + ky - 1, stride*ox + kx - 1)).
+ * stride == 1 IS pt_clf_head_f32 (same kernels, same workspace size, same bits).  stride == 2: one partial product per tap on the exact
+ * fp32 MFMA, the nine summed in fixed order.  Any other stride: PT_ERR_UNSUPPORTED, ws_bytes 0.
+ * Covered: Cin % 64 == 0, Cout % 4 == 0.  Every check precedes the first launch; asynchronous on `stream`, the caller owns the
+ * workspace; no atomics, fixed summation order: repeated calls give the same bits and the call can be captured in a graph.
+ * ---------------------------------------------------------------------------------------------- */
+size_t pt_feat_head_ws_bytes(int n, int Cin, int Cout, int H, int W, int stride);
+int pt_feat_head_f32(const float* feat, const float* weight_tap_major, float* out, int n, int Cin, int Cout, int H, int W, int stride,
+                     float norm_scale, float eps, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Target localisation on the device -- the score-map arithmetic of DiMP/ToMP `localize_advanced`
  * (pytracking/tracker/dimp/dimp.py:238-303, pytracking/tracker/tomp/tomp.py) and `dcf.max2d`
  * (pytracking/libs/dcf.py:156-164), one launch, results left on the device for a single copy.

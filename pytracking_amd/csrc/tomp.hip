@@ -1812,3 +1812,153 @@ int pt_clf_head_impl(const float* feat, const float* weight_tap_major, float* ou
     PT_CHECK_LAUNCH();
     return PT_OK;
 }
+
+// ==================================================================================================================
+// Feature head at stride 1 or 2 (pt_feat_head_f32): Conv2d(Cin, Cout, 3, stride, padding 1, no bias) -> InstanceL2Norm.
+//   stride 1 IS the classification-feature head above (pt_clf_head_impl, same bits).
+//   stride 2 (the RTS classifier head, 1024 x 30 x 52 -> 512 x 15 x 26): the token route of that head with a strided gather --
+//   NCHW -> tokens (k_nchw_to_tokens), one partial product per tap (k_gemm_s2, grid.z = 9), the partials summed in fixed order with the
+//   per-image sum of squares (k_gn_reduce), normalise + transpose back to NCHW (k_head_finish).  No atomics.
+// ==================================================================================================================
+namespace {
+
+// k_gemm<32, 32, 1> (mfma_gemm.h: gemm_tile, MODE 1) with input and output maps of different size: row r of the product is output token
+// (img, oy, ox) = (r / g.HW, (r % g.HW) / Wo, r % Wo) and tap (ky, kx) gathers input token (2 oy + ky - 1, 2 ox + kx - 1) of the
+// g.H x g.Wd map of the SAME image (rows of A: img * g.H * g.Wd + y * g.Wd + x); a tap outside that map is an out-of-range buffer
+// offset, which the hardware answers with zeros.  g.HW = Ho * Wo, g.M = n * Ho * Wo.  Same LDS layout, fragment permutation, register
+// ring and epilogue as gemm_tile; blockIdx.z owns g.ksteps = Cin / 64 K-steps, i.e. one tap.
+__global__ __launch_bounds__(256) void k_gemm_s2(GemmArgs g, int Wo) {
+    constexpr int BM = 32, BN = 32, BK = 64, LS = BK + 4, RP = 1024 / BK, AL = BM / RP, BL = BN / RP, PD = 2;
+    __shared__ __attribute__((aligned(16))) float As[2][BM * LS];
+    __shared__ __attribute__((aligned(16))) float Bs[2][BN * LS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN, bz = blockIdx.z;
+    const int lrow = tid / (BK / 4), lc4 = (tid % (BK / 4)) * 4;
+    const __amdgpu_buffer_rsrc_t rsA = pt_rsrc(g.A, g.a_bytes), rsW = pt_rsrc(g.Wt, g.w_bytes);
+    unsigned aoff[AL], woff[BL];
+    int py[AL], px[AL];
+#pragma unroll
+    for (int i = 0; i < AL; ++i) {
+        const int row = m0 + lrow + RP * i;
+        const bool ok = row < g.M;
+        const int img = row / g.HW, p = row - img * g.HW, oy = p / Wo;
+        py[i] = ok ? 2 * oy : -4;                                        // -4: every tap falls outside the map
+        px[i] = 2 * (p - oy * Wo);
+        aoff[i] = (unsigned)(((long)img * g.H * g.Wd * g.lda + lc4) * 4);
+    }
+#pragma unroll
+    for (int i = 0; i < BL; ++i) {
+        const int n = n0 + lrow + RP * i;
+        woff[i] = n < g.N ? (unsigned)(((long)n * g.K + lc4) * 4) : OOB;
+    }
+    const int nkt = g.K / BK;                                            // K = 9 Cin, Cin % 64 == 0
+    f32x4 ra[PD][AL], rb[PD][BL];
+    auto fetch = [&](int kb, int sl) {                                   // a step past the end re-fetches the last one (never consumed)
+        const int kc = min(kb, nkt - 1);
+        const int k0 = kc * BK, tap = k0 / g.Cin, c0 = k0 - tap * g.Cin;
+        const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
+#pragma unroll
+        for (int i = 0; i < AL; ++i) {
+            const int y = py[i] + dy, x = px[i] + dx;
+            const bool in = y >= 0 && y < g.H && x >= 0 && x < g.Wd;
+            ra[sl][i] = pt_bload4(rsA, in ? aoff[i] + (unsigned)(((long)(y * g.Wd + x) * g.lda + c0) * 4) : OOB);
+        }
+#pragma unroll
+        for (int i = 0; i < BL; ++i)
+            rb[sl][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsW, woff[i], (unsigned)kc * (BK * 4u), 0));
+    };
+    auto stash = [&](int sl, int buf) {
+#pragma unroll
+        for (int i = 0; i < AL; ++i) *reinterpret_cast<f32x4*>(&As[buf][(lrow + RP * i) * LS + lc4]) = ra[sl][i];
+#pragma unroll
+        for (int i = 0; i < BL; ++i) *reinterpret_cast<f32x4*>(&Bs[buf][(lrow + RP * i) * LS + lc4]) = rb[sl][i];
+    };
+    f32x4 acc[1][1] = {{f32x4{0.f, 0.f, 0.f, 0.f}}};
+    const int qoff = ((lane >> 4) & 1) * 2 + (lane >> 5);                // conflict-free fragment maps of gemm_tile
+    const int aso = (wm * 16 + gemm_prow(lane & 15)) * LS + qoff * 4, bso = (wn * 16 + gemm_prow(lane & 15)) * LS + qoff * 4;
+    const int kb0 = bz * g.ksteps, nk = min(nkt, kb0 + g.ksteps);
+#pragma unroll
+    for (int sl = 0; sl < PD; ++sl) fetch(kb0 + sl, sl);
+    stash(0, 0);
+    __syncthreads();
+    for (int t0 = kb0; t0 < nk; t0 += PD) {
+#pragma unroll
+        for (int u = 0; u < PD; ++u) {
+            const int kb = t0 + u, buf = u & 1;
+            fetch(kb + PD, u);                                           // slot u (step kb) already sits in LDS[buf]
+            if (kb < nk) {                                               // workgroup-uniform
+                f32x4 fa[BK / 16], fb[BK / 16];
+#pragma unroll
+                for (int hh = 0; hh < BK / 16; ++hh) {
+                    fa[hh] = *reinterpret_cast<const f32x4*>(&As[buf][aso + hh * 16]);
+                    fb[hh] = *reinterpret_cast<const f32x4*>(&Bs[buf][bso + hh * 16]);
+                }
+#pragma unroll
+                for (int hh = 0; hh < BK / 16; ++hh)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[0][0] = mfma16(fa[hh][j], fb[hh][j], acc[0][0]);
+            }
+            stash((u + 1) % PD, buf ^ 1);                                // step kb+1 (past the end: never read)
+            __syncthreads();
+        }
+    }
+    gemm_store<1, 1>(g, acc, m0 + wm * 16, n0 + wn * 16, lane, bz);
+}
+
+struct FeatHeadCarve { size_t X, part, Y, stats, total; int slices, Ho, Wo; };
+FeatHeadCarve feat_head_carve(int n, int Cin, int Cout, int H, int W) {
+    FeatHeadCarve c{};
+    c.Ho = (H - 1) / 2 + 1; c.Wo = (W - 1) / 2 + 1;
+    const size_t Mo = (size_t)n * c.Ho * c.Wo;
+    size_t o = 0;
+    auto take = [&](size_t k) { size_t r = o; o += pt_align_floats(k); return r; };
+    c.slices = (int)(((size_t)c.Ho * c.Wo * Cout + GN_SLICE - 1) / GN_SLICE);
+    c.X = take((size_t)n * H * W * Cin); c.part = take(9 * Mo * Cout); c.Y = take(Mo * Cout); c.stats = take((size_t)2 * n * c.slices);
+    c.total = o;
+    return c;
+}
+
+// head_check's shapes and limits; stride 2 also keeps the nine partial products inside the epilogue's 32-bit byte offsets
+int feat_head_check(int n, int Cin, int Cout, int H, int W, int stride) {
+    const int rc = head_check(n, Cin, Cout, H, W);
+    if (rc) return rc;
+    if (stride == 1) return PT_OK;
+    if (stride != 2) return PT_ERR_UNSUPPORTED;
+    const size_t Mo = (size_t)n * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1);
+    return 9 * Mo * Cout * 4 >= 0xFFFFFFE0ull ? PT_ERR_UNSUPPORTED : PT_OK;
+}
+
+}  // namespace
+
+extern "C" size_t pt_feat_head_ws_bytes(int n, int Cin, int Cout, int H, int W, int stride) {
+    if (feat_head_check(n, Cin, Cout, H, W, stride)) return 0;
+    if (stride == 1) return pt_clf_head_ws_bytes(n, Cin, Cout, H, W);
+    return feat_head_carve(n, Cin, Cout, H, W).total * sizeof(float);
+}
+
+extern "C" int pt_feat_head_f32(const float* feat, const float* weight_tap_major, float* out, int n, int Cin, int Cout, int H, int W,
+                                int stride, float norm_scale, float eps, void* ws, size_t ws_bytes, void* stream) {
+    if (!feat || !weight_tap_major || !out || !ws) return PT_ERR_NULL;
+    const int rc = feat_head_check(n, Cin, Cout, H, W, stride);
+    if (rc) return rc;
+    if (stride == 1)
+        return pt_clf_head_impl(feat, weight_tap_major, out, n, Cin, Cout, H, W, norm_scale, eps, ws, ws_bytes, stream, nullptr, 0);
+    const FeatHeadCarve cv = feat_head_carve(n, Cin, Cout, H, W);
+    if (ws_bytes < cv.total * sizeof(float) || ((uintptr_t)ws % 256) != 0) return PT_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    float* base = (float*)ws;
+    const int HW = H * W, HWo = cv.Ho * cv.Wo, Mo = n * HWo;
+    hipLaunchKernelGGL(k_nchw_to_tokens, dim3((HW + 31) / 32, (Cin + 31) / 32, n), dim3(256), 0, st, feat, base + cv.X, Cin, HW);
+    PT_CHECK_LAUNCH();
+    const long zs = (long)Mo * Cout;
+    GemmArgs g = gemm_args(base + cv.X, Cin, (long)n * HW, weight_tap_major, Mo, Cout, 9 * Cin, nullptr, base + cv.part, Cout);
+    g.H = H; g.Wd = W; g.Cin = Cin; g.HW = HWo; g.ksteps = Cin / 64; g.c_zstride = zs;
+    hipLaunchKernelGGL(k_gemm_s2, dim3((Cout + 31) / 32, (Mo + 31) / 32, 9), dim3(256), 0, st, g, cv.Wo);
+    PT_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_gn_reduce, dim3(cv.slices, n), dim3(256), 0, st, base + cv.part, 9, zs, base + cv.Y, base + cv.stats, HWo * Cout);
+    PT_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_head_finish, dim3((HWo + 31) / 32, (Cout + 31) / 32, n), dim3(256), 0, st, base + cv.Y, base + cv.stats, cv.slices,
+                       out, Cout, HWo, norm_scale, eps);
+    PT_CHECK_LAUNCH();
+    return PT_OK;
+}

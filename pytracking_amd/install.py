@@ -38,6 +38,9 @@ What gets rebound (import path = contract; nothing in the reference tree is edit
   pytracking.tracker.dimp.dimp.DiMP.optimize_boxes_default / optimize_boxes_relative (and DiMPSimple's, KeepTrack's),
   pytracking.tracker.atom.atom.ATOM.optimize_boxes                                    (IoU-guided box refinement)
                                                                                       -> pytracking_amd.iou_refine
+  ltr.models.target_classifier.features.residual_basic_block, and residual_bottleneck with final_stride=2
+                                                  (LWL / RTS target-model head, RTS classifier head; only with
+                                                  install(feature_heads=True))        -> pytracking_amd.features
   ltr.models.bbreg.atom_iou_net.AtomIoUNet.get_iou_feat  (both IoU feature towers; only with install(iou_feat=True))
                                                                                       -> pytracking_amd.iou_feat
   ltr.models.lwl.label_encoder.ResidualDS16SW.forward, ltr.models.rts.label_encoder.ResidualDS16SW.forward
@@ -310,10 +313,13 @@ def _install_tomp():
         _tm.DenseBoxRegressor, "DenseBoxRegressor: channel count outside the gfx950 hot path"))
 
 
-def _install_clf_head():
+def _install_clf_head(feature_heads=False):
     """Classification-feature head: `clf_features.residual_bottleneck(...)` is reached through the module attribute by
     every network constructor (dimpnet.py:169, tompnet.py:99).  Covered argument sets build the fused module around the
-    reference's own layer objects; on a CPU tensor / in training it runs those layers as `nn.Sequential` would."""
+    reference's own layer objects; on a CPU tensor / in training it runs those layers as `nn.Sequential` would.
+    `feature_heads` (off unless `install(feature_heads=True)`: the set a default install() rebinds is pinned): the rebound
+    `residual_bottleneck` also takes `final_stride=2` (RTS classifier head, rts_net.py:339-344) and `residual_basic_block`
+    (LWL / RTS target-model head, lwl_net.py:173-177, rts_net.py:294-298) is rebound the same way."""
     from . import features as _fm
     try:
         fmod = importlib.import_module("ltr.models.target_classifier.features")
@@ -329,9 +335,11 @@ def _install_clf_head():
         forward = _dispatcher(torch.nn.Sequential.forward, "residual_bottleneck", fused, _fm.ClfHead.forward,
                               "clf feature head: call outside the gfx950 hot path")
 
+    covered = _fm.covered_strided if feature_heads else _fm.covered
+
     def residual_bottleneck(*args, **kw):
         seq = ref_fn(*args, **kw)
-        if _fm.covered(*args, **kw) and len(seq) == 2:
+        if covered(*args, **kw) and len(seq) == 2:
             return ClfHead(seq[0], seq[1])                # the reference's Conv2d and InstanceL2Norm objects
         _outside("residual_bottleneck: configuration outside the gfx950 hot path")
         return seq
@@ -339,6 +347,24 @@ def _install_clf_head():
     residual_bottleneck.__doc__ = ref_fn.__doc__
     residual_bottleneck.__wrapped__ = ref_fn
     _rebind(fmod, "residual_bottleneck", residual_bottleneck)
+    if not feature_heads:
+        return
+    ref_bb = fmod.residual_basic_block
+
+    class FeatHead(_fm.ClfHead):
+        forward = _dispatcher(torch.nn.Sequential.forward, "residual_basic_block", fused, _fm.ClfHead.forward,
+                              "feature head: call outside the gfx950 hot path")
+
+    def residual_basic_block(*args, **kw):
+        seq = ref_bb(*args, **kw)
+        if _fm.covered_basic_block(*args, **kw) and len(seq) == 2:
+            return FeatHead(seq[0], seq[1])               # the reference's Conv2d and InstanceL2Norm objects
+        _outside("residual_basic_block: configuration outside the gfx950 hot path")
+        return seq
+
+    residual_basic_block.__doc__ = ref_bb.__doc__
+    residual_basic_block.__wrapped__ = ref_bb
+    _rebind(fmod, "residual_basic_block", residual_basic_block)
 
 
 def _install_localization():
@@ -759,7 +785,7 @@ def _install_atom_cg():
 
 
 def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=True, iou_refine=True, preprocessing=True,
-            candidate_matching=True, kys=True, iou_feat=False, label_encoder=False, decoder=False):
+            candidate_matching=True, kys=True, iou_feat=False, label_encoder=False, decoder=False, feature_heads=False):
     """Rebind the boundary symbols.  Call after the reference is importable (`sys.path`) and before networks or
     trackers are constructed.  Idempotent.  If an installer raises, what was rebound so far is undone before the exception
     propagates (an optional reference module that does not import is not a failure: its family is skipped)."""
@@ -774,7 +800,9 @@ def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=T
         _install_gn_hinge()
         _install_lwl()                                        # chains to the hinge class: after _install_gn_hinge
         # in this order: iou_refine imports `atom.atom` before _install_atom_cg re-points the names it imported
-        for flag, installer in ((tomp, _install_tomp), (clf_head, _install_clf_head), (localization, _install_localization),
+        for flag, installer in ((tomp, _install_tomp),
+                                (clf_head or feature_heads, functools.partial(_install_clf_head, feature_heads)),
+                                (localization, _install_localization),
                                 (iou_refine, _install_iou_refine), (preprocessing, _install_preprocessing),
                                 (candidate_matching, _install_candidate_matching), (kys, _install_kys), (atom_cg, _install_atom_cg),
                                 (iou_feat, _install_iou_feat), (label_encoder, _install_label_encoder),

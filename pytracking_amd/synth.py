@@ -684,3 +684,29 @@ def lwl_decoder_inputs(seed, n, ic, levels, scores):
     s = rng.standard_normal((n, 1, ic) + tuple(scores), dtype=np.float32)
     feats = {L: np.maximum(rng.standard_normal((n, fc, H, W), dtype=np.float32), 0.0).astype(np.float32) for L, fc, H, W in levels}
     return s, feats
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Feature heads of LWL / RTS: Conv2d(Cin, Cout, 3, stride 1 or 2, padding 1, no bias) + InstanceL2Norm
+# (ltr/models/target_classifier/features.py:9-28, 49-73)
+FEAT_HEAD_CASES = {   # name: (n, Cin, Cout, H, W); every case runs at stride 2 and at stride 1
+    "one": (1, 64, 16, 1, 1),            # one output: only the centre tap is inside the map
+    "two_three": (1, 64, 16, 2, 3),      # smallest map with an even and an odd side
+    "cout36": (1, 64, 36, 6, 7),         # Cout no multiple of 16; even H: last row fully inside, odd W: last column padded
+    "odd_h": (2, 128, 32, 5, 8),         # odd H, two images
+    "straddle": (3, 192, 16, 5, 22),     # 33 output tokens per image: a 32-token tile straddles images; three K-steps per tap
+    "map": (3, 64, 16, 30, 52),          # the deployed map at a small width, 390 output tokens per image
+}
+FEAT_HEAD_DEPLOYED = (1, 1024, 512, 30, 52)   # lwl_net.py:173-177, rts_net.py:294-298 (stride 1); rts_net.py:339-344 (stride 2)
+FEAT_HEAD_SCALE = 0.1                         # norm_scale of the cases: the RMS of every output
+
+
+def feat_head_problem(seed, n, Cin, Cout, H, W, integers=False):
+    """(x (n, Cin, H, W), weight (Cout, Cin, 3, 3)) float32: non-negative maps, as the outputs of ResNet blocks are, and kaiming (fan-in)
+    weights; `integers`: both drawn from -2 ... 2, so that every convolution sum is exact in fp32 in any order."""
+    rng = np.random.default_rng(seed)
+    if integers:
+        return (rng.integers(-2, 3, (n, Cin, H, W)).astype(np.float32), rng.integers(-2, 3, (Cout, Cin, 3, 3)).astype(np.float32))
+    x = np.maximum(rng.standard_normal((n, Cin, H, W), dtype=np.float32), 0.0).astype(np.float32)
+    w = (rng.standard_normal((Cout, Cin, 3, 3), dtype=np.float32) * np.float32(np.sqrt(2.0 / (9 * Cin)))).astype(np.float32)
+    return x, w
