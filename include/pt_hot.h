@@ -868,6 +868,48 @@ int pt_lwl_decoder_f32(const float* scores, const float* const* feats, const flo
                        int levels, const int* fc, const int* hw, const int* score_hw, const int* image_hw, int ic, int mdim, void* ws,
                        size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * RTS instance-score encoder and learners fusion, rts_fusion.hip: what RTS.track() (pytracking/tracker/rts/rts.py:253-260) runs
+ * between the classifier and the decoder.
+ *
+ * pt_score_enc_f32 -- ResidualDS16SW_Clf.forward (ltr/models/rts/label_encoder.py:57-103), the stride-1 sibling of the mask label
+ * encoder above:
+ *   s (n,1,H,W) -> conv3x3 s1 p1 (1->c0) [BN] ReLU -> maxpool3x3 s1 p1 -> BasicBlock(c0->c1, s1) -> BasicBlock(c1->c2, s1)
+ *               -> label_enc (n,f,H,W) = relu([BN](conv3x3(c2->f)))  and  sample_w (n,f,H,W) = conv3x3(c2->f);
+ *   every stride is 1, every map H x W.  scores (n, H, W) fp32 contiguous.  `sample_w` may be NULL (the tracker discards it): that half
+ *   of the heads is then neither computed nor stored, and label_enc has the bits of the full call.  `pack` has the layout and the
+ *   per-layer arithmetic of the mask label encoder's (six layers, tap-major weight | scale | shift each, conv_without_bias(x) * scale +
+ *   shift).  Pooling padding is ignored, convolution padding is zero.  fp32 throughout: the stem on the vector ALU with the
+ *   convolution output kept on chip, every other convolution on the exact fp32 MFMA; no atomics and no split sums, so repeated calls
+ *   are bit-identical.  Six asynchronous launches, no allocation, no host synchronisation.
+ *   Covered: c0, c1, c2, f multiples of 16 up to 64; H, W <= 1024; n <= 1024; pack 16-byte aligned.
+ *
+ * pt_learners_fuse_f32 -- the resize and LearnersFusion of RTSNet.segment_target (ltr/models/rts/rts_net.py:227-230,
+ * ltr/models/rts/learners_fusion.py:24-38) in one launch:
+ *   out (n,f,Ht,Wt) = fusion(seg_enc (n,f,Ht,Wt), resize(clf_enc (n,f,Hs,Ws) -> Ht x Wt)).
+ *   resize = F.interpolate(mode='bilinear', align_corners=False) to an explicit size: src = (dst + 0.5) * (in / out) - 0.5 clamped
+ *   below at 0, i0 = floor(src), i1 = min(i0 + 1, in - 1), weight src - i0, no antialiasing; skipped when the sizes are equal.
+ *   mode PT_FUSE_ADD:    seg_enc + resized; `pack` is not read and may be NULL.  Covered: f <= 64.
+ *   mode PT_FUSE_CONCAT: Conv2d(2f -> f, 3, padding 1, bias) over cat(seg_enc, resized) along the channels, on the fp32 MFMA; the resized
+ *                        map and the concatenation never exist in memory.  `pack` (pt_learners_fuse_pack_floats floats, 16-byte
+ *                        aligned) = weight (f, 3, 3, 2f) tap-major = Conv2d.weight.permute(0, 2, 3, 1), then bias (f).
+ *                        Covered: f a multiple of 16 up to 64.
+ *   Both: Hs, Ws, Ht, Wt <= 1024; n <= 1024.  No workspace.
+ *
+ * Status: NULL pointer PT_ERR_NULL, non-positive size PT_ERR_SHAPE, uncovered size / mode / misaligned pack PT_ERR_UNSUPPORTED,
+ * workspace too small or not 256-byte aligned PT_ERR_WORKSPACE -- all before anything is queued.  pt_score_enc_ws_bytes,
+ * pt_score_enc_pack_floats and pt_learners_fuse_pack_floats are host-only and return 0 for sizes that are not covered.
+ * ---------------------------------------------------------------------------------------------- */
+#define PT_FUSE_ADD 0
+#define PT_FUSE_CONCAT 1
+size_t pt_score_enc_pack_floats(int c0, int c1, int c2, int f);
+size_t pt_score_enc_ws_bytes(int n, int H, int W, int c0, int c1, int c2, int f);
+int pt_score_enc_f32(const float* scores, const float* pack, float* label_enc, float* sample_w, int n, int H, int W, int c0, int c1,
+                     int c2, int f, void* ws, size_t ws_bytes, void* stream);
+size_t pt_learners_fuse_pack_floats(int f);
+int pt_learners_fuse_f32(const float* seg_enc, const float* clf_enc, const float* pack, float* out, int n, int f, int Hs, int Ws, int Ht,
+                         int Wt, int mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -416,3 +416,22 @@ extern "C" int pt_label_enc_f32(const float* masks, const float* pack, float* la
                                 int c1, int c2, int f, void* ws, size_t ws_bytes, void* stream) {
     return pt_label_enc_impl(masks, pack, label_enc, sample_w, n, H, W, c0, c1, c2, f, ws, ws_bytes, (hipStream_t)stream);
 }
+
+// RTS instance-score encoder (ResidualDS16SW_Clf.forward) and learners fusion (rts_fusion.hip)
+extern "C" size_t pt_score_enc_pack_floats(int c0, int c1, int c2, int f) { return pt_score_enc_pack_floats_impl(c0, c1, c2, f); }
+
+extern "C" size_t pt_score_enc_ws_bytes(int n, int H, int W, int c0, int c1, int c2, int f) {
+    return pt_score_enc_ws_bytes_impl(n, H, W, c0, c1, c2, f);
+}
+
+extern "C" int pt_score_enc_f32(const float* scores, const float* pack, float* label_enc, float* sample_w, int n, int H, int W, int c0,
+                                int c1, int c2, int f, void* ws, size_t ws_bytes, void* stream) {
+    return pt_score_enc_impl(scores, pack, label_enc, sample_w, n, H, W, c0, c1, c2, f, ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" size_t pt_learners_fuse_pack_floats(int f) { return pt_learners_fuse_pack_floats_impl(f); }
+
+extern "C" int pt_learners_fuse_f32(const float* seg_enc, const float* clf_enc, const float* pack, float* out, int n, int f, int Hs,
+                                    int Ws, int Ht, int Wt, int mode, void* stream) {
+    return pt_learners_fuse_impl(seg_enc, clf_enc, pack, out, n, f, Hs, Ws, Ht, Wt, mode, (hipStream_t)stream);
+}

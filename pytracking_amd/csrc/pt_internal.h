@@ -241,6 +241,15 @@ size_t pt_label_enc_ws_bytes_impl(int n, int H, int W, int c0, int c1, int c2, i
 int pt_label_enc_impl(const float* masks, const float* pack, float* label_enc, float* sample_w, int n, int H, int W, int c0, int c1,
                       int c2, int f, void* ws, size_t ws_bytes, hipStream_t stream);
 
+// RTS instance-score encoder and learners fusion (rts_fusion.hip); exported as pt_score_enc_* / pt_learners_fuse_* by api.hip
+size_t pt_score_enc_pack_floats_impl(int c0, int c1, int c2, int f);
+size_t pt_score_enc_ws_bytes_impl(int n, int H, int W, int c0, int c1, int c2, int f);
+int pt_score_enc_impl(const float* scores, const float* pack, float* label_enc, float* sample_w, int n, int H, int W, int c0, int c1,
+                      int c2, int f, void* ws, size_t ws_bytes, hipStream_t stream);
+size_t pt_learners_fuse_pack_floats_impl(int f);
+int pt_learners_fuse_impl(const float* seg_enc, const float* clf_enc, const float* pack, float* out, int n, int f, int Hs, int Ws, int Ht,
+                          int Wt, int mode, hipStream_t stream);
+
 // the argument / shape / route checks of a refinement call, nothing queued (iou_refine.hip)
 int pt_iou_refine_validate(const pt_iou_dims* d, const float* params, const float* prepared, const float* c3, const float* c4,
                            const float* mod3, const float* mod4, bool have_init_boxes, const float* boxes_out, const float* iou_out, int P,

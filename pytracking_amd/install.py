@@ -49,6 +49,10 @@ What gets rebound (import path = contract; nothing in the reference tree is edit
   ltr.models.lwl.decoder.LWTLDecoder.forward, ltr.models.rts.decoder.RTSDecoder.forward
                                                   (segmentation decoder, decoder.py:130-160; only with install(decoder=True))
                                                                                       -> pytracking_amd.lwl_decoder
+  ltr.models.rts.label_encoder.ResidualDS16SW_Clf.forward, ltr.models.rts.rts_net.RTSNet.segment_target
+                                                  (RTS instance-score encoder; resize + LearnersFusion between the target model and
+                                                  the decoder; only with install(rts_fusion=True))
+                                                                                      -> pytracking_amd.rts_fusion
 
 Dispatch rule of the rebound *functions*: device fp32 tensors of a shape the gfx950 kernels cover go to the C ABI;
 everything else (CPU tensors, dilations, grouped filters, K*K > 16, more than 16 filters) is outside the hot path and
@@ -648,6 +652,24 @@ def _install_lwl_decoder():
                                             name + ": call outside the gfx950 hot path"))
 
 
+def _install_rts_fusion():
+    """`ResidualDS16SW_Clf.forward` (ltr/models/rts/label_encoder.py:86-103): the stride-1 score encoder in six launches; and
+    `RTSNet.segment_target` (ltr/models/rts/rts_net.py:219-236): the bilinear resize of the encoded scores and the LearnersFusion in one
+    launch between `target_model.apply_target_model` and `decoder`, which are called as they are bound.  CPU tensors, training mode,
+    grad-enabled calls, calls without encoded scores, more than one sequence, modules of another structure and uncovered sizes keep the
+    reference's code.  Off unless `install(rts_fusion=True)`: the set a default install() rebinds is pinned."""
+    from . import rts_fusion as _rf
+    try:
+        enc_cls = importlib.import_module("ltr.models.rts.label_encoder").ResidualDS16SW_Clf
+        net_cls = importlib.import_module("ltr.models.rts.rts_net").RTSNet
+    except Exception:
+        return
+    for cls, attr, covered, fast in ((enc_cls, "forward", _rf.encoder_covered, functools.partial(_rf.encode, checked=True)),
+                                     (net_cls, "segment_target", _rf.segment_covered, functools.partial(_rf.segment_target, checked=True))):
+        name = cls.__name__ + "." + attr
+        _rebind(cls, attr, _dispatcher(getattr(cls, attr), name, covered, fast, name + ": call outside the gfx950 hot path"))
+
+
 def _install_gn_hinge():
     """`GNSteepestDescent` on an exact reference `LinearFilterHinge` with parameter_batch_dim=0, residual_batch_dim=1
     (dimpnet.py:236-242, rts_net.py:325-333) -> the fused solver (pytracking_amd.gn_hinge); the residual object stays the reference's.
@@ -785,7 +807,8 @@ def _install_atom_cg():
 
 
 def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=True, iou_refine=True, preprocessing=True,
-            candidate_matching=True, kys=True, iou_feat=False, label_encoder=False, decoder=False, feature_heads=False):
+            candidate_matching=True, kys=True, iou_feat=False, label_encoder=False, decoder=False, feature_heads=False,
+            rts_fusion=False):
     """Rebind the boundary symbols.  Call after the reference is importable (`sys.path`) and before networks or
     trackers are constructed.  Idempotent.  If an installer raises, what was rebound so far is undone before the exception
     propagates (an optional reference module that does not import is not a failure: its family is skipped)."""
@@ -806,7 +829,7 @@ def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=T
                                 (iou_refine, _install_iou_refine), (preprocessing, _install_preprocessing),
                                 (candidate_matching, _install_candidate_matching), (kys, _install_kys), (atom_cg, _install_atom_cg),
                                 (iou_feat, _install_iou_feat), (label_encoder, _install_label_encoder),
-                                (decoder, _install_lwl_decoder)):
+                                (decoder, _install_lwl_decoder), (rts_fusion, _install_rts_fusion)):
             if flag:
                 installer()
     except BaseException:

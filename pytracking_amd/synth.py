@@ -710,3 +710,63 @@ def feat_head_problem(seed, n, Cin, Cout, H, W, integers=False):
     x = np.maximum(rng.standard_normal((n, Cin, H, W), dtype=np.float32), 0.0).astype(np.float32)
     w = (rng.standard_normal((Cout, Cin, 3, 3), dtype=np.float32) * np.float32(np.sqrt(2.0 / (9 * Cin)))).astype(np.float32)
     return x, w
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# RTS instance-score encoder (ltr/models/rts/label_encoder.py:57-103) and learners fusion (rts_net.py:219-236, learners_fusion.py).
+# The encoder has the parameter names and shapes of the mask label encoder (every stride is 1 instead of 2): its states are
+# `label_enc_state`.  The classifier score map of the deployed tracker is 16 x 27 (15 x 26 features, 4 x 4 filter; rts50.py) and is fused
+# with the 30 x 52 mask encoding.
+SCORE_ENC_CASES = {   # name: (n, H, W, layer_dims, use_bn)
+    "one": (1, 1, 1, LABEL_ENC_DIMS, False),                 # every tap but the centre is padding; the pool window has one member
+    "row": (1, 1, 19, LABEL_ENC_DIMS, False),                # a single row wider than a 16-pixel tile
+    "odd": (3, 5, 7, LABEL_ENC_DIMS, False),                 # per-map indexing
+    "edge": (1, 17, 33, LABEL_ENC_DIMS, False),              # one past a tile boundary in both directions
+    "deployed": (2, 16, 27, LABEL_ENC_DIMS, False),          # the tracker's size; n = 2 so that the batch stride is exercised
+    "bn": (2, 9, 20, LABEL_ENC_DIMS, True),                  # BatchNorm folding
+    "dims": (2, 11, 13, (16, 16, 32, 32), False),            # channel counts other than the deployed ones
+}
+LEARNERS_FUSE_CASES = {   # name: (n, F, (Hs, Ws), (Ht, Wt)); every case runs as 'add' and as 'concat'
+    "same": (1, 16, (6, 9), (6, 9)),                         # the no-resize branch
+    "up1": (1, 16, (1, 1), (3, 4)),                          # every neighbour clamped
+    "deployed": (1, 16, (16, 27), (30, 52)),                 # the tracker's size
+    "down": (2, 16, (9, 11), (4, 5)),                        # shrinking without antialiasing
+    "edge": (1, 16, (8, 14), (17, 33)),                      # one past a tile boundary
+    "f32": (1, 32, (5, 7), (9, 13)),                         # F other than 16
+}
+FUSION_TYPES = ("add", "concat")
+RTS_CHAIN_CASE = dict(H=16, W=27, dims=LABEL_ENC_DIMS, target=(30, 52))     # chain_deployed: the encoder, then the fuse
+
+
+def score_maps(seed, n, H, W):
+    """(n, H, W) float32 classifier score maps, roughly in [-0.2, 1]: one peaked target response, two weaker distractors and noise."""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    out = np.empty((n, H, W), dtype=np.float32)
+    for k in range(n):
+        s = rng.standard_normal((H, W)) * 0.04 - 0.02
+        for amp in (rng.uniform(0.8, 1.0), rng.uniform(0.2, 0.45), rng.uniform(0.1, 0.3)):
+            cy, cx = rng.uniform(0.0, 1.0) * (H - 1), rng.uniform(0.0, 1.0) * (W - 1)
+            sig = rng.uniform(0.8, 1.6)
+            s = s + amp * np.exp(-0.5 * ((yy - cy) ** 2 + (xx - cx) ** 2) / sig ** 2)
+        out[k] = np.clip(s, -0.2, 1.0).astype(np.float32)
+    return out
+
+
+def learners_fusion_state(seed, f, fusion_type):
+    """A state dict (numpy, float32) of a LearnersFusion: empty for 'add'; for 'concat' the Conv2d(2F, F, 3, padding=1) with fan-in scaled
+    weights and a non-zero bias."""
+    if fusion_type == "add":
+        return {}
+    rng = np.random.default_rng(seed)
+    return {"fusion_conv1.weight": (rng.standard_normal((f, 2 * f, 3, 3), dtype=np.float32) * np.float32(np.sqrt(2.0 / (9 * 2 * f)))).astype(np.float32),
+            "fusion_conv1.bias": (rng.standard_normal(f, dtype=np.float32) * np.float32(0.1)).astype(np.float32)}
+
+
+def learners_fuse_inputs(seed, n, f, source, target):
+    """(seg_enc (1, n, F, Ht, Wt) signed, as a target model's mask encoding; clf_enc (1, n, F, Hs, Ws) non-negative, as the encoder's
+    rectified output) float32."""
+    rng = np.random.default_rng(seed)
+    seg = rng.standard_normal((1, n, f) + tuple(target), dtype=np.float32)
+    clf = np.maximum(rng.standard_normal((1, n, f) + tuple(source), dtype=np.float32), 0.0).astype(np.float32)
+    return seg, clf
