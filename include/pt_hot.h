@@ -910,6 +910,59 @@ size_t pt_learners_fuse_pack_floats(int f);
 int pt_learners_fuse_f32(const float* seg_enc, const float* clf_enc, const float* pack, float* out, int n, int f, int Hs, int Ws, int Ht,
                          int Wt, int mode, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Segmentation read-out of LWL / RTS, seg_readout.hip: the host-side stages the trackers run between the decoder's raw score map and the
+ * next frame's label encoder.  fp32, asynchronous on `stream`, no allocation, no host synchronisation, no atomics (two runs on the same
+ * input are bit-identical), graph-capturable.  Workspaces are caller-owned, 256-byte aligned and sized by the *_ws_bytes queries.
+ *
+ * Statistics block: PT_SEG_STATS_FLOATS = 16 floats
+ *    [0] prob_sum   [1] e_y   [2] e_x   [3] var_y   [4] var_x            of p       (get_target_state of lwl.py:276-298; var = the
+ *    [5] prob_sum_c [6] e_y_c [7] e_x_c [8] var_y_c [9] var_x_c          of max(p,0) reference's e_h, e_w before the square root)
+ *    [10] mask_count  [11] x_min [12] y_min [13] x_max [14] y_max         of the mask (masks_to_bboxes; an empty mask gives 0, 0, 0, 0)
+ *    [15] 0
+ *   Rows and columns are summed first (per-tile partial sums, added in tile order), the moments are centred on e_y / e_x afterwards, as
+ *   the reference does; the one-pass sum p y^2 - e_y^2 sum p is not used.  prob_sum == 0 gives NaN moments, as the reference.  Counts
+ *   are exact up to 2^24 pixels.
+ *
+ * pt_seg_readout_f32 -- convert_scores_crop_to_image (lwl.py:330-359, rts.py:460-493, sta_helper.py:88-117) with `> 0`, sigmoid and the
+ *   sums of get_target_state / masks_to_bboxes in one pass plus the finishing kernel:
+ *     resized(ry, rx) = bilinear(scores (Hc, Wc)) as F.interpolate(scale_factor=scale, mode='bilinear', align_corners=False) without a
+ *                       recomputed scale factor: src = max((dst + 0.5) / scale - 0.5, 0), i0 = min(floor(src), in - 1),
+ *                       i1 = min(i0 + 1, in - 1); Hr = floor(Hc * scale), Wr = floor(Wc * scale) are the CALLER's;
+ *     scores_im(y, x) = resized(y - r1, x - c1) inside the window [r1, r1 + Hr) x [c1, c1 + Wr), -100 outside; (r1, c1) is the window's
+ *                       unclipped corner, r1 = int(pos_r - 0.5 Hr) with truncation towards zero, the caller's as well;
+ *     prob_im = sigmoid(scores_im) (0 outside the window: exp(100) overflows), mask_im = scores_im > 0 as 0 / 1 floats.
+ *   The resized map is never stored.  scores_im, prob_im, mask_im (Hi, Wi) may each be NULL; `stats` is the block of prob_im with the
+ *   mask scores_im > 0.  A window that misses the image gives the all-background image (-100, 0, 0) and mask_count 0.
+ * pt_seg_state_f32 -- the statistics block of a probability image (H, W) on the device; the mask is `mask` > 0 when a mask image is
+ *   given and prob > 0.5 when `mask` is NULL.  On the read-out's prob_im and mask_im it repeats the read-out's block bit for bit.
+ * pt_seg_merge_f32 -- merge_results (lwl.py:217-248): scores (N, H, W) -> prob (N + 1, H, W), background first:
+ *     p = sigmoid(s), bg = clamp(prod(1 - p), 1e-7, 1 - 1e-7), s_0 = log(bg / (1 - bg)), prob_i = 1 / sum_j exp(s_j - s_i) with j in
+ *     the order 0 .. N; labels (H, W) uint8 = arg-max over i, the first maximum wins (0 = background); stats (N, 16): object i's block
+ *     of prob_{i+1} with the mask labels == i + 1.  One pass over the pixels, the N + 1 scores of a pixel in registers.  1 <= N <=
+ *     PT_SEG_MAX_OBJECTS.
+ * pt_sample_mask_patch_f32 -- sample_patch(is_mask=True) (pytracking/features/preprocessing.py:95-146) for the integer geometry of
+ *   pt_sample_patch_f32: the strided view im[os0::df, os1::df], the crop of crop_h x crop_w at (tl0, tl1) with ZERO padding, then
+ *   torch's legacy 'nearest' resize to OH x OW in fp32: index = min((int)floorf(dst * ((float)in / (float)out)), in - 1).  im (C, H, W),
+ *   out (C, OH, OW).
+ * Covered: every image side <= PT_SEG_MAX_DIM; |r1|, |c1| <= PT_SEG_MAX_DIM; C <= 1024.
+ * Status: NULL pointer PT_ERR_NULL, non-positive size or scale (N = 0, a bad geometry) PT_ERR_SHAPE, a size beyond the bounds above
+ * PT_ERR_UNSUPPORTED, workspace too small or not 256-byte aligned PT_ERR_WORKSPACE -- all before anything is queued.  The *_ws_bytes
+ * queries are host-only and return 0 for what is not covered.
+ * ---------------------------------------------------------------------------------------------- */
+#define PT_SEG_STATS_FLOATS 16
+#define PT_SEG_MAX_OBJECTS 16
+#define PT_SEG_MAX_DIM 8192
+size_t pt_seg_readout_ws_bytes(int Hi, int Wi);
+int pt_seg_readout_f32(const float* scores, int Hc, int Wc, double scale, int Hr, int Wr, int r1, int c1, int Hi, int Wi,
+                       float* scores_im, float* prob_im, float* mask_im, float* stats, void* ws, size_t ws_bytes, void* stream);
+size_t pt_seg_state_ws_bytes(int H, int W);
+int pt_seg_state_f32(const float* prob, const float* mask, int H, int W, float* stats, void* ws, size_t ws_bytes, void* stream);
+size_t pt_seg_merge_ws_bytes(int N, int H, int W);
+int pt_seg_merge_f32(const float* scores, int N, int H, int W, float* prob, unsigned char* labels, float* stats, void* ws,
+                     size_t ws_bytes, void* stream);
+int pt_sample_mask_patch_f32(const float* im, int C, int H, int W, const pt_patch_geom* geom, float* out, int OH, int OW, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -435,3 +435,30 @@ extern "C" int pt_learners_fuse_f32(const float* seg_enc, const float* clf_enc, 
                                     int Ws, int Ht, int Wt, int mode, void* stream) {
     return pt_learners_fuse_impl(seg_enc, clf_enc, pack, out, n, f, Hs, Ws, Ht, Wt, mode, (hipStream_t)stream);
 }
+
+// segmentation read-out, object merge and mask patch of LWL / RTS (seg_readout.hip)
+extern "C" size_t pt_seg_readout_ws_bytes(int Hi, int Wi) { return pt_seg_stats_ws_bytes_impl(1, Hi, Wi); }
+
+extern "C" int pt_seg_readout_f32(const float* scores, int Hc, int Wc, double scale, int Hr, int Wr, int r1, int c1, int Hi, int Wi,
+                                  float* scores_im, float* prob_im, float* mask_im, float* stats, void* ws, size_t ws_bytes, void* stream) {
+    return pt_seg_readout_impl(scores, Hc, Wc, scale, Hr, Wr, r1, c1, Hi, Wi, scores_im, prob_im, mask_im, stats, ws, ws_bytes,
+                               (hipStream_t)stream);
+}
+
+extern "C" size_t pt_seg_state_ws_bytes(int H, int W) { return pt_seg_stats_ws_bytes_impl(1, H, W); }
+
+extern "C" int pt_seg_state_f32(const float* prob, const float* mask, int H, int W, float* stats, void* ws, size_t ws_bytes, void* stream) {
+    return pt_seg_state_impl(prob, mask, H, W, stats, ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" size_t pt_seg_merge_ws_bytes(int N, int H, int W) { return pt_seg_stats_ws_bytes_impl(N, H, W); }
+
+extern "C" int pt_seg_merge_f32(const float* scores, int N, int H, int W, float* prob, unsigned char* labels, float* stats, void* ws,
+                                size_t ws_bytes, void* stream) {
+    return pt_seg_merge_impl(scores, N, H, W, prob, labels, stats, ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" int pt_sample_mask_patch_f32(const float* im, int C, int H, int W, const pt_patch_geom* geom, float* out, int OH, int OW,
+                                        void* stream) {
+    return pt_sample_mask_patch_impl(im, C, H, W, geom, out, OH, OW, (hipStream_t)stream);
+}

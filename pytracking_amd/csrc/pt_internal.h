@@ -250,6 +250,15 @@ size_t pt_learners_fuse_pack_floats_impl(int f);
 int pt_learners_fuse_impl(const float* seg_enc, const float* clf_enc, const float* pack, float* out, int n, int f, int Hs, int Ws, int Ht,
                           int Wt, int mode, hipStream_t stream);
 
+// segmentation read-out, object merge and mask patch (seg_readout.hip); exported as pt_seg_* / pt_sample_mask_patch_f32 by api.hip
+size_t pt_seg_stats_ws_bytes_impl(int blocks, int H, int W);
+int pt_seg_readout_impl(const float* scores, int Hc, int Wc, double scale, int Hr, int Wr, int r1, int c1, int Hi, int Wi, float* scores_im,
+                        float* prob_im, float* mask_im, float* stats, void* ws, size_t ws_bytes, hipStream_t stream);
+int pt_seg_state_impl(const float* prob, const float* mask, int H, int W, float* stats, void* ws, size_t ws_bytes, hipStream_t stream);
+int pt_seg_merge_impl(const float* scores, int N, int H, int W, float* prob, unsigned char* labels, float* stats, void* ws, size_t ws_bytes,
+                      hipStream_t stream);
+int pt_sample_mask_patch_impl(const float* im, int C, int H, int W, const pt_patch_geom* geom, float* out, int OH, int OW, hipStream_t stream);
+
 // the argument / shape / route checks of a refinement call, nothing queued (iou_refine.hip)
 int pt_iou_refine_validate(const pt_iou_dims* d, const float* params, const float* prepared, const float* c3, const float* c4,
                            const float* mod3, const float* mod4, bool have_init_boxes, const float* boxes_out, const float* iou_out, int P,

@@ -53,6 +53,11 @@ What gets rebound (import path = contract; nothing in the reference tree is edit
                                                   (RTS instance-score encoder; resize + LearnersFusion between the target model and
                                                   the decoder; only with install(rts_fusion=True))
                                                                                       -> pytracking_amd.rts_fusion
+  pytracking.tracker.lwl.lwl.LWL.convert_scores_crop_to_image / merge_results,
+  pytracking.tracker.rts.sta_helper.STAHelper.convert_scores_crop_to_image,
+  pytracking.tracker.rts.rts.RTS.convert_seg_scores_crop_to_image / merge_results
+                                                  (crop-to-image paste and multi-object merge; only with install(seg_readout=True))
+                                                                                      -> pytracking_amd.seg_readout
 
 Dispatch rule of the rebound *functions*: device fp32 tensors of a shape the gfx950 kernels cover go to the C ABI;
 everything else (CPU tensors, dilations, grouped filters, K*K > 16, more than 16 filters) is outside the hot path and
@@ -670,6 +675,36 @@ def _install_rts_fusion():
         _rebind(cls, attr, _dispatcher(getattr(cls, attr), name, covered, fast, name + ": call outside the gfx950 hot path"))
 
 
+def _install_seg_readout():
+    """The segmentation trackers' read-out: `convert_scores_crop_to_image` of LWL and of RTS's STAHelper, RTS's
+    `convert_seg_scores_crop_to_image` (resize + paste on the device, the score image comes back as the CPU tensor the trackers expect) and
+    both `merge_results` (one upload, the soft aggregation with its arg-max and per-object statistics on the device, one download; the
+    same numpy dictionaries).  CPU score tensors, a window that misses the image (the reference raises there), uncovered sizes, more than
+    16 objects and a tracker without a GPU keep the reference's code.  `get_target_state` is not rebound: the unmodified trackers only
+    hand it CPU tensors.  Off unless `install(seg_readout=True)`: the set a default install() rebinds is pinned."""
+    from . import seg_readout as _sr
+
+    def covered_rts(self, segmentation_scores, im, sample_coords):
+        pos, scale = _sr.sample_location(self, sample_coords)
+        return _sr.convert_covered(segmentation_scores, im, scale.item(), (pos[0].item(), pos[1].item()))
+
+    def covered(self, segmentation_scores, im, sample_scale, sample_pos):
+        return _sr.convert_covered(segmentation_scores, im, float(sample_scale), (float(sample_pos[0]), float(sample_pos[1])))
+
+    for modname, clsname, attr, cov, fast in (
+            ("pytracking.tracker.lwl.lwl", "LWL", "convert_scores_crop_to_image", covered, _sr.convert_scores_crop_to_image),
+            ("pytracking.tracker.rts.sta_helper", "STAHelper", "convert_scores_crop_to_image", covered, _sr.convert_scores_crop_to_image),
+            ("pytracking.tracker.rts.rts", "RTS", "convert_seg_scores_crop_to_image", covered_rts, _sr.convert_seg_scores_crop_to_image),
+            ("pytracking.tracker.lwl.lwl", "LWL", "merge_results", _sr.merge_covered, _sr.merge_results_lwl),
+            ("pytracking.tracker.rts.rts", "RTS", "merge_results", _sr.merge_covered, _sr.merge_results_rts)):
+        try:
+            cls = getattr(importlib.import_module(modname), clsname)
+        except Exception:               # tracker module not importable here: nothing to patch
+            continue
+        name = clsname + "." + attr
+        _rebind(cls, attr, _dispatcher(getattr(cls, attr), name, cov, fast, name + ": call outside the gfx950 hot path"))
+
+
 def _install_gn_hinge():
     """`GNSteepestDescent` on an exact reference `LinearFilterHinge` with parameter_batch_dim=0, residual_batch_dim=1
     (dimpnet.py:236-242, rts_net.py:325-333) -> the fused solver (pytracking_amd.gn_hinge); the residual object stays the reference's.
@@ -808,7 +843,7 @@ def _install_atom_cg():
 
 def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=True, iou_refine=True, preprocessing=True,
             candidate_matching=True, kys=True, iou_feat=False, label_encoder=False, decoder=False, feature_heads=False,
-            rts_fusion=False):
+            rts_fusion=False, seg_readout=False):
     """Rebind the boundary symbols.  Call after the reference is importable (`sys.path`) and before networks or
     trackers are constructed.  Idempotent.  If an installer raises, what was rebound so far is undone before the exception
     propagates (an optional reference module that does not import is not a failure: its family is skipped)."""
@@ -829,7 +864,8 @@ def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=T
                                 (iou_refine, _install_iou_refine), (preprocessing, _install_preprocessing),
                                 (candidate_matching, _install_candidate_matching), (kys, _install_kys), (atom_cg, _install_atom_cg),
                                 (iou_feat, _install_iou_feat), (label_encoder, _install_label_encoder),
-                                (decoder, _install_lwl_decoder), (rts_fusion, _install_rts_fusion)):
+                                (decoder, _install_lwl_decoder), (rts_fusion, _install_rts_fusion),
+                                (seg_readout, _install_seg_readout)):
             if flag:
                 installer()
     except BaseException:
