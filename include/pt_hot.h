@@ -963,6 +963,83 @@ int pt_seg_merge_f32(const float* scores, int N, int H, int W, float* prob, unsi
                      size_t ws_bytes, void* stream);
 int pt_sample_mask_patch_f32(const float* im, int C, int H, int W, const pt_patch_geom* geom, float* out, int OH, int OW, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * ECO's Fourier-domain per-frame path, eco.hip (pytracking/tracker/eco/eco.py:181-245, 293-309, 339-343; pytracking/libs/fourier.py,
+ * dcf.py:97-103, 156-164).  fp32, complex numbers as a trailing dimension of 2 in the reference's layouts, asynchronous on `stream`, no
+ * allocation, no host synchronisation, no atomics (two runs on the same input are bit-identical), graph-capturable.  Workspaces are
+ * caller-owned and 256-byte aligned.
+ *
+ * Sample transform: x (S, Cin, H, W), proj (Cin, c) or NULL (then c == Cin), window (H, W), interp_y (Hf, 2), interp_x (Wh, 2) ->
+ *   xf (S, c, Hf, Wh, 2), Hf = H + (H + 1) % 2, Wh = W / 2 + 1:
+ *     y = (sum_ci x[., ci] proj[ci, k]) * window;  F[ky, kx] = sum_h sum_w y[h, w] exp(-2 pi i (ky h / H + kx w / W)), kx < Wh;
+ *     row r of xf carries the frequency f = r - (Hf - 1) / 2, i.e. F[f mod H] -- for even H the Nyquist row appears at both ends, as
+ *     rfftshift2 (fourier.py:8-10) leaves it;  xf = (F * interp_y[r]) * interp_x[kx];  with has_shift the two factors of shift_fs
+ *     (fourier.py:78-92) follow: * exp(i shift_y f) * exp(i shift_x kx).
+ *   window may be NULL (no window); interp_y and interp_x may be NULL together (no interpolation factors: the plain centred transform).
+ *   A dense two-pass transform (rows, then columns); twiddle phases are reduced in integers, (k n) mod N, and the N cosine / sine values
+ *   are evaluated in double precision.  In all these entry points the sums over channels, map rows / columns and series terms are
+ *   accumulated in double-precision registers and rounded to fp32 once; everything in memory is fp32.
+ * Shift: the two factors of shift_fs alone on xf (S, c, Hf, Wh, 2), odd Hf; out may not alias xf partially (out == xf is fine).
+ * Filter response (eco.py:244-245): hf (1, c, Hf, Wh, 2), xf (S, c, Hf, Wh, 2) -> sf (S, 1, Hf, Wh, 2) = sum over k = 0 .. c - 1, in that
+ *   order, of the complex products hf[k] * xf[s, k].
+ * Localisation (eco.py:247-252, 272; fourier.py:34-61, 95-114): `sf`, `Hf`, `Wh`, `weight` are HOST arrays of nb <= PT_ECO_MAX_BLOCKS
+ *   entries, the block with the largest series FIRST: device pointers to (S, 1, Hf[b], Wh[b], 2), odd Hf[b] <= Hf[0], Wh[b] <= Wh[0],
+ *   and the translation weights (NULL: all 1, fusion 'sum').  A = weight[0] sf[0], and weight[b] sf[b] added at sum_fs's offsets (rows
+ *   centred on the zero frequency, columns from 0).  The series is evaluated on the (Oh, Ow) grid, Oh >= Hf[0], Ow >= 2 Wh[0] - 1, even
+ *   or odd, as the REAL PART OF THE HALF-SPECTRUM SERIES:
+ *     scores[s, y, x] = Re sum_kx m_kx exp(2 pi i kx x / Ow) sum_r A[s, r, kx] exp(2 pi i (r - (Hf[0] - 1) / 2) y / Oh),  m_0 = 1, m_kx = 2:
+ *   the kx = 0 column counts once, every kx > 0 column twice.  For Hermitian-consistent input this is what the inverse real transform of
+ *   sample_fs returns after its zero padding (pad_top = (Oh - Hf) / 2 rounded down, the rest below; columns to Ow / 2 + 1) and its
+ *   Oh Ow rescale; the imaginary part of the kx = 0 column is ignored here as it is there.  For a grid EQUAL to the series sample_fs
+ *   passes no size to the inverse transform, which then returns 2 Wh - 2 columns: that case is defined here with Ow = 2 Wh - 1 and is
+ *   not what the reference computes.  scores (S, 1, Oh, Ow); max_val (S) and argmax (S, 2) int64 [row, col] as the max2d entry above.
+ * Memory insert (eco.py:223-230, 339-343): xf (1, c, Hf, Wh, 2), shifted when has_shift, stored transposed into slot `ind` of
+ *   samples (Hf, Wh, n, c, 2); nothing outside the slot is written.
+ * Covered: H, W <= PT_ECO_MAX_FEAT; Oh, Ow <= PT_ECO_MAX_GRID; Wh[0] <= 64.
+ * Status: NULL pointer PT_ERR_NULL, a non-positive or inconsistent size PT_ERR_SHAPE, a size beyond the bounds above PT_ERR_UNSUPPORTED,
+ * workspace too small or misaligned PT_ERR_WORKSPACE -- all before anything is queued.  The ws_bytes query is host-only and returns 0 for
+ * what is not covered.
+ * ---------------------------------------------------------------------------------------------- */
+#define PT_ECO_MAX_FEAT 64
+#define PT_ECO_MAX_GRID 1024
+#define PT_ECO_MAX_BLOCKS 4
+#define PT_ECO_MAX_SAMPLES 1024
+/* Filter update, FilterOptim.run (pytracking/tracker/eco/optim.py:142-208) on run_CG (pytracking/libs/optimization.py:72-163): one call,
+ * all feature blocks.  Per block: samples (Hf, Wh, n, c, 2), weights (n) ON THE DEVICE, yf (Hf, Wh), reg_filter (Rh, Rw), sample_energy
+ * (c, Hf, Wh) in/out, new_xf (c, Hf, Wh, 2) or NULL, x (c, Hf, Wh, 2) updated IN PLACE, and the carried CG state the caller owns: p and
+ * r_prev (c, Hf, Wh, 2) and state[2] = {rho, 1 if p is valid else 0} (zero-initialise state[1] before the first call).  Steps: the sample-energy
+ * moving average (1 - lr) e + lr |new_xf|^2 when new_xf is given; b = yf conj(sum_n w_n S_n); diag_M = (1 - reg_param) (data_param e +
+ * (1 - data_param) mean_c e) + reg_param reg_energy; r = b - A(x); num_iter iterations with M1 = 1 / diag_M, Polak-Ribiere or
+ * Fletcher-Reeves beta clamped at 0, alpha = rho / ip(p, q) (standard_alpha) or ip(p, r) / ip(p, q), the residual update skipped on the
+ * last iteration.  direction_forget_factor 0 resets the state, otherwise rho /= factor when p is valid.  ip is inner_prod_fs.  CG scalars
+ * are per block; if any block's rho is exactly 0 at the top of an iteration the run ends for every block with x as it stands (a flag in
+ * the workspace turns the remaining launches into no-ops; rho of that iteration is kept, as in the reference).  num_iter == 0 returns at
+ * once.  A(v) = S^H diag(w) S v per bin plus the regulariser: v extended to the left by conj(flip(v[.., 1 : pad2 + 1, :])), convolved with
+ * reg_filter at padding (pad1, pad2), min(pad2, Wh - 1) columns dropped, convolved again without padding; pad1 = min(Rh - 1, Hf - 1),
+ * pad2 = min(Rw - 1, 2 Wh - 2).  A filter whose clipped padding does not give (Hf, Wh) back (the reference's conv2d raises there) is
+ * PT_ERR_UNSUPPORTED.  Covered: c <= 64, n <= PT_ECO_MAX_SAMPLES, Rh, Rw <= 15, <= PT_ECO_MAX_BLOCKS blocks. */
+typedef struct pt_eco_fu_block {
+    const float *samples, *weights, *yf, *reg_filter;
+    float* sample_energy;
+    const float* new_xf;
+    float *x, *p, *r_prev, *state;
+    int Hf, Wh, c, n, Rh, Rw;
+    float learning_rate, reg_energy;
+} pt_eco_fu_block;
+size_t pt_eco_filter_update_ws_bytes(const pt_eco_fu_block* blk, int nb);
+int pt_eco_filter_update_f32(const pt_eco_fu_block* blk, int nb, int num_iter, int fletcher_reeves, int standard_alpha,
+                             float direction_forget_factor, float precond_data_param, float precond_reg_param, void* ws, size_t ws_bytes,
+                             void* stream);
+int pt_eco_sample_f32(const float* x, const float* proj, const float* window, const float* interp_y, const float* interp_x, int has_shift,
+                      float shift_y, float shift_x, float* xf, int S, int Cin, int c, int H, int W, void* stream);
+int pt_eco_shift_f32(const float* xf, float shift_y, float shift_x, float* out, int S, int c, int Hf, int Wh, void* stream);
+int pt_eco_apply_filter_f32(const float* hf, const float* xf, float* sf, int S, int c, int Hf, int Wh, void* stream);
+size_t pt_eco_localize_ws_bytes(int S, int Wh, int Oh, int Ow);
+int pt_eco_localize_f32(const float* const* sf, const int* Hf, const int* Wh, const float* weight, int nb, int S, int Oh, int Ow, float* scores,
+                        float* max_val, long long* argmax, void* ws, size_t ws_bytes, void* stream);
+int pt_eco_insert_f32(const float* xf, int has_shift, float shift_y, float shift_x, float* samples, int c, int Hf, int Wh, int n, int ind,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PT_HOT_LIB", os.path.join(_HERE, "libpt_hot.so"))   # override: experiments only
-SOURCES = ["filter_kernels.hip", "fast_passes.hip", "sd_solver.hip", "mf_kernels.hip", "lwl_solver.hip", "atom_cg.hip", "atom_gn.hip", "tomp.hip", "localize.hip", "iou_refine.hip", "prroi.hip", "patch.hip", "frame_full.hip", "api.hip", "gn_hinge.hip", "tcm.hip", "kys.hip", "iou_feat.hip", "label_enc.hip", "lwl_decoder.hip", "rts_fusion.hip", "seg_readout.hip"]
+SOURCES = ["filter_kernels.hip", "fast_passes.hip", "sd_solver.hip", "mf_kernels.hip", "lwl_solver.hip", "atom_cg.hip", "atom_gn.hip", "tomp.hip", "localize.hip", "iou_refine.hip", "prroi.hip", "patch.hip", "frame_full.hip", "api.hip", "gn_hinge.hip", "tcm.hip", "kys.hip", "iou_feat.hip", "label_enc.hip", "lwl_decoder.hip", "rts_fusion.hip", "seg_readout.hip", "eco.hip"]
 HEADERS = ["common.h", "pt_internal.h", "rbuild.h", "sd_common.h", "mfma_gemm.h", "conv_tokens.h", "prroi_dev.h", "localize_dev.h", "frame_mid.h", os.path.join("..", "..", "include", "pt_hot.h")]
 # kernarg preload: leading scalar kernel parameters arrive in SGPRs at wave launch (kernels that take them that way only)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-pass-failed", "-mllvm", "-amdgpu-kernarg-preload-count=14"]
@@ -20,6 +20,13 @@ PT_ACT_RELU, PT_ACT_BENTPAR = 0, 1
 PT_MASK_SIGMOID, PT_MASK_LINEAR = 0, 1
 PT_FUSE_ADD, PT_FUSE_CONCAT = 0, 1
 PT_SEG_STATS_FLOATS, PT_SEG_MAX_OBJECTS, PT_SEG_MAX_DIM = 16, 16, 8192
+PT_ECO_MAX_FEAT, PT_ECO_MAX_GRID, PT_ECO_MAX_BLOCKS, PT_ECO_MAX_SAMPLES = 64, 1024, 4, 1024
+
+
+class EcoFuBlock(ctypes.Structure):
+    """`pt_eco_fu_block` of include/pt_hot.h."""
+    _fields_ = ([(n, ctypes.c_void_p) for n in ("samples", "weights", "yf", "reg_filter", "sample_energy", "new_xf", "x", "p", "r_prev", "state")]
+                + [(n, ctypes.c_int) for n in ("Hf", "Wh", "c", "n", "Rh", "Rw")] + [("learning_rate", ctypes.c_float), ("reg_energy", ctypes.c_float)])
 
 class IouDims(ctypes.Structure):
     """`pt_iou_dims` of include/pt_hot.h."""
@@ -114,6 +121,8 @@ EXPORTS = [
     "pt_score_enc_pack_floats", "pt_score_enc_ws_bytes", "pt_score_enc_f32", "pt_learners_fuse_pack_floats", "pt_learners_fuse_f32",
     "pt_seg_readout_ws_bytes", "pt_seg_readout_f32", "pt_seg_state_ws_bytes", "pt_seg_state_f32", "pt_seg_merge_ws_bytes", "pt_seg_merge_f32",
     "pt_sample_mask_patch_f32",
+    "pt_eco_sample_f32", "pt_eco_shift_f32", "pt_eco_apply_filter_f32", "pt_eco_localize_ws_bytes", "pt_eco_localize_f32", "pt_eco_insert_f32",
+    "pt_eco_filter_update_ws_bytes", "pt_eco_filter_update_f32",
 ]
 
 PT_TCM_MAX_POINTS, PT_TCM_MAX_LAYERS = 64, 32       # include/pt_hot.h
@@ -461,6 +470,22 @@ def lib():
     L.pt_seg_merge_f32.argtypes = [vp, i, i, i, vp, vp, vp, vp, sz, vp]
     L.pt_sample_mask_patch_f32.restype = i
     L.pt_sample_mask_patch_f32.argtypes = [vp, i, i, i, ctypes.POINTER(PatchGeom), vp, i, i, vp]
+    L.pt_eco_sample_f32.restype = i
+    L.pt_eco_sample_f32.argtypes = [vp] * 5 + [i, f, f, vp] + [i] * 5 + [vp]
+    L.pt_eco_shift_f32.restype = i
+    L.pt_eco_shift_f32.argtypes = [vp, f, f, vp] + [i] * 4 + [vp]
+    L.pt_eco_apply_filter_f32.restype = i
+    L.pt_eco_apply_filter_f32.argtypes = [vp] * 3 + [i] * 4 + [vp]
+    L.pt_eco_localize_ws_bytes.restype = sz
+    L.pt_eco_localize_ws_bytes.argtypes = [i] * 4
+    L.pt_eco_localize_f32.restype = i
+    L.pt_eco_localize_f32.argtypes = [ctypes.POINTER(vp), ip, ip, fp] + [i] * 4 + [vp, vp, vp, vp, sz, vp]
+    L.pt_eco_insert_f32.restype = i
+    L.pt_eco_insert_f32.argtypes = [vp, i, f, f, vp] + [i] * 5 + [vp]
+    L.pt_eco_filter_update_ws_bytes.restype = sz
+    L.pt_eco_filter_update_ws_bytes.argtypes = [ctypes.POINTER(EcoFuBlock), i]
+    L.pt_eco_filter_update_f32.restype = i
+    L.pt_eco_filter_update_f32.argtypes = [ctypes.POINTER(EcoFuBlock), i, i, i, i, f, f, f, vp, sz, vp]
     L.pt_mf_corr_tm_plan.restype = i
     L.pt_mf_corr_tm_plan.argtypes = [i] * 5 + [ctypes.POINTER(ctypes.c_int)]
     L.pt_sample_patch_f32.restype = i

@@ -59,6 +59,12 @@ What gets rebound (import path = contract; nothing in the reference tree is edit
                                                   (crop-to-image paste and multi-object merge; only with install(seg_readout=True))
                                                                                       -> pytracking_amd.seg_readout
 
+  pytracking.libs.fourier.cfft2 / cifft2 / shift_fs, pytracking.libs.dcf.get_reg_filter (the Fourier tools on torch.fft: the reference's
+  call the removed torch.rfft / torch.irfft), pytracking.tracker.eco.eco.ECO.preprocess_sample / extract_fourier_sample / apply_filter /
+  localize_target / update_memory, pytracking.tracker.eco.optim.FilterOptim.run
+                                             (ECO's per-frame Fourier-domain path and filter update; only with install(eco=True))
+                                                                                      -> pytracking_amd.eco
+
 Dispatch rule of the rebound *functions*: device fp32 tensors of a shape the gfx950 kernels cover go to the C ABI;
 everything else (CPU tensors, dilations, grouped filters, K*K > 16, more than 16 filters) is outside the hot path and
 is handed to the reference's ORIGINAL function object -- its own stock-PyTorch code, not a re-implementation --
@@ -705,6 +711,49 @@ def _install_seg_readout():
         _rebind(cls, attr, _dispatcher(getattr(cls, attr), name, cov, fast, name + ": call outside the gfx950 hot path"))
 
 
+def _install_eco():
+    """ECO (pytracking/tracker/eco/eco.py).  `fourier.cfft2`, `fourier.cifft2` and `dcf.get_reg_filter` call torch.rfft / torch.irfft, which
+    the installed torch does not have: they are REPLACED by pytracking_amd.eco's forms on torch.fft (any device; there is no reference code
+    to hand a call to), `cfft2` of a covered device tensor by the sample-transform kernel.  `fourier.shift_fs` and the ECO methods
+    `preprocess_sample`, `extract_fourier_sample`, `apply_filter`, `localize_target`, `update_memory` are dispatchers: CPU tensors,
+    grad-enabled calls, other dtypes, debug >= 3, the 'transcale' fusion, a score grid equal to or smaller than the series and uncovered
+    shapes keep the reference's code; so does `FilterOptim.run` (the filter update: all blocks, the CG state carried on the device).  The first-frame joint Gauss-Newton (whose problem class `_install_atom_cg`'s
+    dispatcher declines) and `symmetrize_filter` stay the reference's.  Off unless `install(eco=True)`: the set a default install() rebinds
+    is pinned."""
+    from . import eco as _eco
+    try:
+        fmod = importlib.import_module("pytracking.libs.fourier")
+        dmod = importlib.import_module("pytracking.libs.dcf")
+        lift = importlib.import_module("pytracking.libs.tensorlist").tensor_operation
+    except Exception:
+        return
+
+    def cfft2(a):
+        if _hit("cfft2", _eco.covered_cfft2(a)):
+            return _eco.cfft2_device(a)
+        return _eco.cfft2(a)
+
+    for owner, name, fn in ((fmod, "cfft2", lift(cfft2)), (fmod, "cifft2", lift(_eco.cifft2)), (dmod, "get_reg_filter", _eco.get_reg_filter)):
+        _rebind(owner, name, fn)
+    ref_shift = fmod.shift_fs
+    _rebind(fmod, "shift_fs", lift(_dispatcher(getattr(ref_shift, "__wrapped__", ref_shift), "shift_fs", _eco.covered_shift_fs, _eco.shift_fs,
+                                               "shift_fs: call outside the gfx950 hot path")))
+    try:
+        cls = importlib.import_module("pytracking.tracker.eco.eco").ECO
+    except Exception:               # tracker module not importable here: the Fourier tools are still provided
+        return
+    for attr, covered, fast in (("preprocess_sample", _eco.covered_preprocess_sample, _eco.tracker_preprocess_sample),
+                                ("extract_fourier_sample", _eco.covered_extract_fourier_sample, _eco.tracker_extract_fourier_sample),
+                                ("apply_filter", _eco.covered_tracker_apply_filter, _eco.tracker_apply_filter),
+                                ("localize_target", _eco.covered_localize_target, _eco.tracker_localize_target),
+                                ("update_memory", _eco.covered_update_memory, _eco.tracker_update_memory)):
+        name = "ECO." + attr
+        _rebind(cls, attr, _dispatcher(getattr(cls, attr), name, covered, fast, name + ": call outside the gfx950 hot path"))
+    ocls = importlib.import_module("pytracking.tracker.eco.optim").FilterOptim
+    _rebind(ocls, "run", _dispatcher(ocls.run, "FilterOptim.run", _eco.covered_filter_run, _eco.tracker_filter_run,
+                                     "FilterOptim.run: call outside the gfx950 hot path"))
+
+
 def _install_gn_hinge():
     """`GNSteepestDescent` on an exact reference `LinearFilterHinge` with parameter_batch_dim=0, residual_batch_dim=1
     (dimpnet.py:236-242, rts_net.py:325-333) -> the fused solver (pytracking_amd.gn_hinge); the residual object stays the reference's.
@@ -843,7 +892,7 @@ def _install_atom_cg():
 
 def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=True, iou_refine=True, preprocessing=True,
             candidate_matching=True, kys=True, iou_feat=False, label_encoder=False, decoder=False, feature_heads=False,
-            rts_fusion=False, seg_readout=False):
+            rts_fusion=False, seg_readout=False, eco=False):
     """Rebind the boundary symbols.  Call after the reference is importable (`sys.path`) and before networks or
     trackers are constructed.  Idempotent.  If an installer raises, what was rebound so far is undone before the exception
     propagates (an optional reference module that does not import is not a failure: its family is skipped)."""
@@ -865,7 +914,7 @@ def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=T
                                 (candidate_matching, _install_candidate_matching), (kys, _install_kys), (atom_cg, _install_atom_cg),
                                 (iou_feat, _install_iou_feat), (label_encoder, _install_label_encoder),
                                 (decoder, _install_lwl_decoder), (rts_fusion, _install_rts_fusion),
-                                (seg_readout, _install_seg_readout)):
+                                (seg_readout, _install_seg_readout), (eco, _install_eco)):
             if flag:
                 installer()
     except BaseException:

@@ -770,3 +770,55 @@ def learners_fuse_inputs(seed, n, f, source, target):
     seg = rng.standard_normal((1, n, f) + tuple(target), dtype=np.float32)
     clf = np.maximum(rng.standard_normal((1, n, f) + tuple(source), dtype=np.float32), 0.0).astype(np.float32)
     return seg, clf
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# ECO (pytracking/tracker/eco): inputs of the Fourier-domain per-frame path
+
+def eco_features(seed, S, C, H, W, smooth=2):
+    """Spatially correlated feature maps (S, C, H, W), float32: white noise box-filtered `smooth` times along both axes (periodic) and
+    rescaled to unit variance, so that their spectrum decays with the frequency as a real backbone's does."""
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((S, C, H, W))
+    for _ in range(smooth):
+        x = (np.roll(x, 1, 2) + x + np.roll(x, -1, 2)) / 3.0 if H > 2 else x
+        x = (np.roll(x, 1, 3) + x + np.roll(x, -1, 3)) / 3.0 if W > 2 else x
+    return (x / max(x.std(), 1e-6)).astype(np.float32)
+
+
+def eco_projection(seed, Cin, c):
+    """A projection matrix (Cin, c) with orthonormal columns, as the PCA initialisation of eco.py:110-113 gives."""
+    q, _ = np.linalg.qr(np.random.default_rng(seed).standard_normal((Cin, c)))
+    return np.ascontiguousarray(q[:, :c]).astype(np.float32)
+
+
+def eco_window(H, W):
+    """dcf.hann2d (dcf.py:8-18), centred: (1, 1, H, W) float32."""
+    def hann(n):
+        return 0.5 * (1.0 - np.cos((2.0 * math.pi / (n + 1)) * np.arange(1, n + 1)))
+    return (hann(H)[:, None] * hann(W)[None, :]).astype(np.float32).reshape(1, 1, H, W)
+
+
+def eco_interp(seed, H, W):
+    """Complex interpolation factors in get_interp_fourier's shapes and magnitudes (dcf.py:74-94): interp_y (1, 1, Hf, 1, 2) of modulus about
+    1 / H with the centring phase -pi ky / Hf, interp_x (1, 1, 1, Wh, 2) likewise; the moduli are seeded instead of the cubic spline's."""
+    rng = np.random.default_rng(seed)
+    Hf, Wh = H + (H + 1) % 2, W // 2 + 1
+    ky, kx = np.arange(Hf) - (Hf - 1) // 2, np.arange(Wh)
+    my, mx = rng.uniform(0.5, 1.0, Hf) / Hf, rng.uniform(0.5, 1.0, Wh) / (2 * Wh - 1)
+    iy = np.stack((my * np.cos(-math.pi * ky / Hf), my * np.sin(-math.pi * ky / Hf)), -1)
+    ix = np.stack((mx * np.cos(-math.pi * kx / (2 * Wh - 1)), mx * np.sin(-math.pi * kx / (2 * Wh - 1))), -1)
+    return iy.astype(np.float32).reshape(1, 1, Hf, 1, 2), ix.astype(np.float32).reshape(1, 1, 1, Wh, 2)
+
+
+def eco_series(seed, S, c, Hf, Wh, decay=0.35):
+    """Half-spectrum coefficients (S, c, Hf, Wh, 2), float32, Hermitian-consistent in the kx = 0 column (row r is the conjugate of row
+    Hf - 1 - r there, the centre real) with moduli that decay with the frequency: what the sample transform produces, without running it."""
+    rng = np.random.default_rng(seed)
+    a = rng.standard_normal((S, c, Hf, Wh, 2))
+    ky, kx = np.abs(np.arange(Hf) - (Hf - 1) // 2)[:, None], np.arange(Wh)[None, :]
+    a *= (1.0 / (1.0 + decay * np.hypot(ky, kx)) ** 2)[None, None, :, :, None]
+    col = a[:, :, :, 0, :]
+    flip = col[:, :, ::-1, :] * np.array([1.0, -1.0])
+    a[:, :, :, 0, :] = 0.5 * (col + flip)
+    return a.astype(np.float32)
