@@ -305,6 +305,61 @@ int pt_tomp_bbreg_routes(int n, int d_model, int H, int W, int* routes, int cap,
 int pt_tomp_linear_routes(int B, int N, int K, int* routes, int cap, int* n_routes);
 
 /* ------------------------------------------------------------------------------------------------
+ * TaMOs multi-object filter predictor -- replaces, for inference,
+ *   GOTFilterPredictor.predict_filter                       (ltr/models/transformer/filter_predictor.py:180-233)
+ *   GOTFilterPredictor._predict_cls_bbreg_filters_parallel  (ltr/models/transformer/filter_predictor.py:245-315)
+ *   Transformer.forward with T = num_tokens object queries  (ltr/models/transformer/transformer.py:90-96,172-180,224-238)
+ * for label_enc = 'gaussian' and box_enc = 'ltrb_token' (ltr/train_settings/tamos/*.py), as the tracker calls it every frame
+ * (pytracking/tracker/tamos/tamos.py:289-306).  The classifier's scores come from the multi-filter correlation that exists already.
+ * Out of scope: heads.FPN, the multi-object DenseBoxRegressor on the FPN map, TaMOs.track end to end, training.  pt_tomp_* is unchanged.
+ *
+ * Pack: pt_tomp's transformer tensors in pt_tomp's order, then the 14 box_encoding tensors in pt_tomp's order, then
+ * query_embed_fg.weight (T, D).  There is no test-frame token.  pt_tamos_param_floats() is the length (0: not covered).
+ *
+ * Shapes, with B = n_seq, or 2 when `parallel`: train_feat (n_train, n_seq, D, H, W); test_feat (1, n_seq, D, H, W);
+ * train_label (n_train, n_seq, T, H, W); train_ltrb (n_train, n_seq, T, 4, H, W); pos (H*W, D) from pt_tomp_posenc_f32;
+ * filters (B, T, D); enc_feat (B, D, H, W).
+ *   parallel = 0: predict_filter.   parallel = 1 (n_seq must be 1): row 0 classification, row 1 box regression with the keys
+ *   [num_gth_frames H W, L - H W) masked in encoder and decoder (filter_predictor.py:298-299).
+ *
+ * The call computes
+ *   memory tokens  feat + sum_o label[o] E[o] + sum_o E[o] (.) MLP(ltrb[o])   (filter_predictor.py:204-220); E = query_embed_fg.weight,
+ *                  MLP = 4 -> D/4 -> D -> D with eval-mode BatchNorm1d and ReLU (:6-17).  An absent object (zero label, zero box) still
+ *                  contributes E[o] (.) MLP(0).  The object sum in front of the last Linear is one product with K = T D against
+ *                  diag(E[o]) W3, a weight-only matrix that pt_tamos_prepare_f32 folds; test tokens are the features as they are (:222)
+ *   encoder        pt_tomp's stack and launchers (transformer.py:172-180)
+ *   decoder        T queries per batch row, post-norm (transformer.py:224-238): self-attention among the T queries, cross-attention of
+ *                  the T nhead query rows over all L keys with pt_tomp's fold (W_k,h^T W_q,h / sqrt(d_h) and W_o[:,h] W_v,h, folded by
+ *                  pt_tamos_prepare_f32) -- the keys stream in 64-key chunks whose (max, sum, context) are merged in chunk order, so
+ *                  nothing of size L is held on chip and L has no limit of its own --, FFN, three LayerNorms, then decoder.norm (:140-141)
+ * fp32 products and accumulation, no atomics (the same inputs give the same bits), no host synchronisation (graph-capturable).
+ *
+ * Covered: pt_tomp's dims (d_model in {128,256,384,512}, head width in {16,32,64}, dim_ff % 64 == 0, <= 16 layers each), B <= 8,
+ * 1 <= T <= 16, any L whose buffers stay under 4 GiB (32-bit byte offsets).  Otherwise pt_tamos_param_floats / _ws_bytes return 0 and
+ * the entry points PT_ERR_UNSUPPORTED / PT_ERR_SHAPE before any launch.
+ *
+ * pt_tamos_predict_routes: host only, like pt_tomp_predict_routes; the shared launchers report their PT_TOMP_R_* ids, the launches that
+ * are new here -- k_tamos_tokens, k_tamos_box1, k_tamos_self_attn, k_tamos_xattn<D / 16>, k_tamos_xmerge -- ids of enum pt_tamos_route.
+ * It refuses exactly where pt_tamos_predict_f32 does; PT_TAMOS_MAX_ROUTES entries always suffice.
+ * ---------------------------------------------------------------------------------------------- */
+enum pt_tamos_route {
+    PT_TAMOS_R_TOKENS = 1000, PT_TAMOS_R_BOX1, PT_TAMOS_R_SELF_ATTN,
+    PT_TAMOS_R_XATTN128, PT_TAMOS_R_XATTN256, PT_TAMOS_R_XATTN384, PT_TAMOS_R_XATTN512, PT_TAMOS_R_XMERGE,
+    PT_TAMOS_R_END
+};
+#define PT_TAMOS_MAX_ROUTES 512
+size_t pt_tamos_param_floats(const pt_tomp_dims* dims, int num_tokens);
+size_t pt_tamos_prepared_floats(const pt_tomp_dims* dims, int num_tokens);
+int pt_tamos_prepare_f32(const pt_tomp_dims* dims, int num_tokens, const float* params, float* prepared, void* stream);
+size_t pt_tamos_predict_ws_bytes(const pt_tomp_dims* dims, int num_tokens, int n_train, int n_seq, int parallel);
+int pt_tamos_predict_f32(const pt_tomp_dims* dims, int num_tokens, const float* params, const float* prepared, const float* pos,
+                         const float* train_feat, const float* test_feat, const float* train_label, const float* train_ltrb,
+                         int n_train, int n_seq, int parallel, int num_gth_frames, float* filters, float* enc_feat,
+                         void* ws, size_t ws_bytes, void* stream);
+int pt_tamos_predict_routes(const pt_tomp_dims* dims, int num_tokens, int n_train, int n_seq, int parallel, int* routes, int cap,
+                            int* n_routes);
+
+/* ------------------------------------------------------------------------------------------------
  * Classification-feature head -- `residual_bottleneck(num_blocks=0, final_conv=True, l2norm=True)`
  * (ltr/models/target_classifier/features.py:49-73): Conv2d(Cin, Cout, 3, padding=1, bias=False) followed by
  * InstanceL2Norm(size_average=True, eps, scale) (ltr/models/layers/normalization.py:15-20), as DiMP-50 (1024 -> 512,

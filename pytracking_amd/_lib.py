@@ -90,6 +90,11 @@ TOMP_ROUTES = (
     "LN256_SPLIT2", "LN256_SPLIT4", "LN256_DOUBLE", "LN128", "LN64", "LN_GENERIC", "DEC0_CONST", "DEC0_LIVE", "GEMV_DEC1", "GEMV_DEC2",
     "GEMV_DEC4", "GEMV_DEC8", "GEMV_V4", "GEMV_V1", "DEC_SCORES", "DEC_CTX", "TO_NCHW", "REG_ATTEND", "GN_REDUCE", "GN_APPLY", "REG_FINISH")
 PT_TOMP_MAX_ROUTES = 256
+# `enum pt_tamos_route` of include/pt_hot.h (what pt_tamos_predict_routes reports next to the shared launchers' TOMP_ROUTES): from 1000
+TAMOS_ROUTE_BASE = 1000
+TAMOS_ROUTES = ("TAMOS_TOKENS", "TAMOS_BOX1", "TAMOS_SELF_ATTN", "TAMOS_XATTN128", "TAMOS_XATTN256", "TAMOS_XATTN384", "TAMOS_XATTN512",
+                "TAMOS_XMERGE")
+PT_TAMOS_MAX_ROUTES = 512
 
 EXPORTS = [
     "pt_strerror", "pt_abi_version",
@@ -104,6 +109,8 @@ EXPORTS = [
     "pt_tomp_param_floats", "pt_tomp_prepared_floats", "pt_tomp_prepare_f32", "pt_tomp_posenc_f32", "pt_tomp_predict_ws_bytes", "pt_tomp_predict_f32", "pt_tomp_linear_f32",
     "pt_tomp_bbreg_param_floats", "pt_tomp_bbreg_ws_bytes", "pt_tomp_bbreg_f32",
     "pt_tomp_predict_routes", "pt_tomp_bbreg_routes", "pt_tomp_linear_routes",
+    "pt_tamos_param_floats", "pt_tamos_prepared_floats", "pt_tamos_prepare_f32", "pt_tamos_predict_ws_bytes", "pt_tamos_predict_f32",
+    "pt_tamos_predict_routes",
     "pt_clf_head_ws_bytes", "pt_clf_head_f32", "pt_feat_head_ws_bytes", "pt_feat_head_f32", "pt_max2d_f32", "pt_localize_f32", "pt_localize_decide_f32",
     "pt_localize_constants_f32", "pt_localize_advanced_f32", "pt_localize_advanced_sync_f32",
     "pt_iou_param_floats", "pt_iou_prepared_floats", "pt_iou_prepare_f32", "pt_iou_refine_ws_bytes", "pt_iou_refine_f32", "pt_iou_refine_sync_f32",
@@ -342,6 +349,18 @@ def lib():
     L.pt_tomp_bbreg_routes.argtypes = [i, i, i, i, ip, i, ip]
     L.pt_tomp_linear_routes.restype = i
     L.pt_tomp_linear_routes.argtypes = [i, i, i, ip, i, ip]
+    L.pt_tamos_param_floats.restype = sz
+    L.pt_tamos_param_floats.argtypes = [dp, i]
+    L.pt_tamos_prepared_floats.restype = sz
+    L.pt_tamos_prepared_floats.argtypes = [dp, i]
+    L.pt_tamos_prepare_f32.restype = i
+    L.pt_tamos_prepare_f32.argtypes = [dp, i, vp, vp, vp]
+    L.pt_tamos_predict_ws_bytes.restype = sz
+    L.pt_tamos_predict_ws_bytes.argtypes = [dp, i, i, i, i]
+    L.pt_tamos_predict_f32.restype = i
+    L.pt_tamos_predict_f32.argtypes = [dp, i, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, vp, vp, vp, sz, vp]
+    L.pt_tamos_predict_routes.restype = i
+    L.pt_tamos_predict_routes.argtypes = [dp, i, i, i, i, ip, i, ip]
     L.pt_clf_head_ws_bytes.restype = sz
     L.pt_clf_head_ws_bytes.argtypes = [i] * 5
     L.pt_clf_head_f32.restype = i

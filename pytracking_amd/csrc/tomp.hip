@@ -1342,6 +1342,48 @@ extern "C" int pt_tomp_prepare_f32(const pt_tomp_dims* d, const float* params, f
 }
 
 namespace {
+// The encoder stack (transformer.py:172-180, post-norm) over `rows` = B * L token rows in X, shared by the ToMP and the TaMOs predictor:
+// X is updated in place; QKV (rows, 3D), AO, Y (rows, D) and Hd (rows, ff) are scratch.
+int run_encoder(const pt_tomp_dims* d, const PackOff& po, const float* P, const float* pos, const AttnArgs& at, int B, int L, int HW,
+                float* X, float* QKV, float* AO, float* Y, float* Hd, hipStream_t st, PtRouteLog* log) {
+    const int D = d->d_model, ff = d->dim_ff, rows = B * L;
+    int rc;
+    for (int i = 0; i < d->n_enc; ++i) {
+        const EncOff& e = po.enc[i];
+        GemmArgs g = gemm_args(X, D, rows, P + e.sa.w_in, rows, 3 * D, D, P + e.sa.b_in, QKV, 3 * D);
+        g.pos = pos; g.pos_bytes = (unsigned)((long)HW * D * 4); g.pos_cols = 2 * D; g.L = L; g.HW = HW;
+        if ((rc = launch_gemm(g, st, false, log))) return rc;
+        if ((rc = launch_attn(at, B, st, log))) return rc;
+        g = gemm_args(AO, D, rows, P + e.sa.w_out, rows, D, D, P + e.sa.b_out, Y, D);
+        g.R = X;
+        if ((rc = launch_gemm(g, st, false, log))) return rc;
+        // (norm1 folded into the FFN's first product saved a launch per layer and lost: frame 0.885 -> 0.894 ms,
+        // profiles/r06p_tomp_ln1_fold.txt)
+        if ((rc = launch_ln_rows(Y, X, P + e.n1g, P + e.n1b, rows, D, st, log))) return rc;
+        g = gemm_args(X, D, rows, P + e.w1, rows, ff, D, P + e.b1, Hd, ff);
+        g.relu = 1;
+        if ((rc = launch_gemm(g, st, false, log))) return rc;
+        const long rD = (long)rows * D;
+        if ((ff / 64) % 4 == 0 && rows >= 1024 && D % 64 == 0 && AO == QKV + 3 * (size_t)rD &&
+            ln_rows_wide_ok(QKV, X, P + e.n2g, P + e.n2b, D)) {
+            // The FFN's second product (K = dim_ff) runs as K-slices whose partial sums, bias included, meet in the LayerNorm that
+            // follows (which then also adds the residual); two halves: ToMP frame 1.006 -> 0.996 ms (round 4, profiles/r04e_*).
+            // round 6: four K-quarters on 128 x 64 tiles (k_gemm_ps: 256 workgroups x 16 stages, M tiles on x) into the four row blocks
+            // QKV[0..2], AO -- all free here -- that meet, with the residual, in the LayerNorm
+            g = gemm_args(Hd, ff, rows, P + e.w2, rows, D, ff, P + e.b2, QKV, D);
+            g.ksteps = ff / 64 / 4; g.c_zstride = rD;
+            if ((rc = launch_gemm(g, st, false, log))) return rc;
+            if ((rc = launch_ln_rows(QKV, X, P + e.n2g, P + e.n2b, rows, D, st, log, QKV + rD, X, nullptr, nullptr, QKV + 2 * rD, AO))) return rc;
+            continue;
+        }
+        g = gemm_args(Hd, ff, rows, P + e.w2, rows, D, ff, P + e.b2, Y, D);
+        g.R = X;
+        if ((rc = launch_gemm(g, st, false, log))) return rc;
+        if ((rc = launch_ln_rows(Y, X, P + e.n2g, P + e.n2b, rows, D, st, log))) return rc;
+    }
+    return PT_OK;
+}
+
 // log == nullptr: the predictor.  Otherwise the same walk through the same dispatchers with nothing queued: every launch site notes its
 // route instead (pt_tomp_predict_routes).  Host code only derives addresses from the pointers, it never reads through them.
 int tomp_predict_impl(const pt_tomp_dims* d, const float* params, const float* prepared, const float* pos, const float* train_feat,
@@ -1397,39 +1439,7 @@ int tomp_predict_impl(const pt_tomp_dims* d, const float* params, const float* p
         at.mhi[1] = L - HW;
     }
     // ---- encoder (transformer.py:172-180), post-norm
-    for (int i = 0; i < d->n_enc; ++i) {
-        const EncOff& e = po.enc[i];
-        GemmArgs g = gemm_args(X, D, rows, P + e.sa.w_in, rows, 3 * D, D, P + e.sa.b_in, QKV, 3 * D);
-        g.pos = pos; g.pos_bytes = (unsigned)((long)HW * D * 4); g.pos_cols = 2 * D; g.L = L; g.HW = HW;
-        if ((rc = launch_gemm(g, st, false, log))) return rc;
-        if ((rc = launch_attn(at, B, st, log))) return rc;
-        g = gemm_args(AO, D, rows, P + e.sa.w_out, rows, D, D, P + e.sa.b_out, Y, D);
-        g.R = X;
-        if ((rc = launch_gemm(g, st, false, log))) return rc;
-        // (norm1 folded into the FFN's first product saved a launch per layer and lost: frame 0.885 -> 0.894 ms,
-        // profiles/r06p_tomp_ln1_fold.txt)
-        if ((rc = launch_ln_rows(Y, X, P + e.n1g, P + e.n1b, rows, D, st, log))) return rc;
-        g = gemm_args(X, D, rows, P + e.w1, rows, ff, D, P + e.b1, Hd, ff);
-        g.relu = 1;
-        if ((rc = launch_gemm(g, st, false, log))) return rc;
-        const long rD = (long)rows * D;
-        if ((ff / 64) % 4 == 0 && rows >= 1024 && D % 64 == 0 && cv.AO == cv.QKV + 3 * (size_t)rD &&
-            ln_rows_wide_ok(QKV, X, P + e.n2g, P + e.n2b, D)) {
-            // The FFN's second product (K = dim_ff) runs as K-slices whose partial sums, bias included, meet in the LayerNorm that
-            // follows (which then also adds the residual); two halves: ToMP frame 1.006 -> 0.996 ms (round 4, profiles/r04e_*).
-            // round 6: four K-quarters on 128 x 64 tiles (k_gemm_ps: 256 workgroups x 16 stages, M tiles on x) into the four row blocks
-            // QKV[0..2], AO -- all free here -- that meet, with the residual, in the LayerNorm
-            g = gemm_args(Hd, ff, rows, P + e.w2, rows, D, ff, P + e.b2, QKV, D);
-            g.ksteps = ff / 64 / 4; g.c_zstride = rD;
-            if ((rc = launch_gemm(g, st, false, log))) return rc;
-            if ((rc = launch_ln_rows(QKV, X, P + e.n2g, P + e.n2b, rows, D, st, log, QKV + rD, X, nullptr, nullptr, QKV + 2 * rD, AO))) return rc;
-            continue;
-        }
-        g = gemm_args(Hd, ff, rows, P + e.w2, rows, D, ff, P + e.b2, Y, D);
-        g.R = X;
-        if ((rc = launch_gemm(g, st, false, log))) return rc;
-        if ((rc = launch_ln_rows(Y, X, P + e.n2g, P + e.n2b, rows, D, st, log))) return rc;
-    }
+    if ((rc = run_encoder(d, po, P, pos, at, B, L, HW, X, QKV, AO, Y, Hd, st, log))) return rc;
     // ---- decoder (transformer.py:224-238), one query per batch row; T = LayerNorm(pre) is applied by the consumers
     // (base + cv.zero was cleared by k_tomp_tokens)
     DecAttnArgs da{};
@@ -1648,6 +1658,493 @@ extern "C" int pt_tomp_linear_routes(int B, int N, int K, int* routes, int cap, 
     if (cap < 0) return PT_ERR_SHAPE;
     PtRouteLog log{routes, cap, 0};
     const int rc = tomp_linear_impl(route_fake(0), route_fake(1), route_fake(2), route_fake(3), B, N, K, 0, nullptr, &log);
+    return route_finish(rc, log, routes, cap, n_routes);
+}
+
+// ==================================================================================================================
+// TaMOs multi-object filter predictor (pt_tamos_*, include/pt_hot.h): GOTFilterPredictor.predict_filter /
+// _predict_cls_bbreg_filters_parallel with label_enc 'gaussian' and box_enc 'ltrb_token' (filter_predictor.py:180-233,245-315) around
+// Transformer.forward (transformer.py:90-96).  T object queries per batch row instead of ToMP's one:
+//   tokens    k_tamos_tokens (features + sum_o label[o] E[o]), k_tamos_box1 + two products on launch_gemm for sum_o E[o] (.) MLP(ltrb[o]):
+//             the object sum in front of the last Linear is ONE product with K = T D against diag(E[o]) W3 (folded by prepare)
+//   encoder   run_encoder, as ToMP runs it
+//   decoder   per layer: q|k|v projection of the T queries (launch_gemm, +query_pos on the q|k column tiles), k_tamos_self_attn,
+//             out_proj + residual, LayerNorm; folded query (ToMP's Wk_h^T Wq_h / sqrt(d_h)) for all T nhead query rows in one product,
+//             k_tamos_xattn over 64-key chunks of the memory -- scores and context on v_mfma_f32_16x16x4_f32, 16 query rows per
+//             wavefront, nothing of size L on chip -- whose (max, sum, context) partials k_tamos_xmerge merges in chunk order, the
+//             folded value + out_proj product (K = nhead D), LayerNorm, FFN, LayerNorm
+// No atomics, every reduction in a fixed order: the same inputs give the same bits.  No host synchronisation.
+// ==================================================================================================================
+namespace {
+
+struct TamosTokArgs {
+    const float *train, *test, *label, *E;                       // label (nf, ns, T, HW), E (T, D)
+    float* X;
+    int nf, ns, dup, D, HW, L, T;
+    float* zero; int nzero;                                      // the decoder's initial state, cleared on the side by the blocks of z = 0
+};
+
+// NCHW feature maps -> token-major rows; memory frames + sum_o label[o] * E[o] (filter_predictor.py:205-208), test frame as it is
+__global__ __launch_bounds__(256) void k_tamos_tokens(TamosTokArgs a) {
+    __shared__ float tile[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int p0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+    if (blockIdx.z == 0) {
+        const int nb = gridDim.x * gridDim.y * 256;
+        for (int i = (blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x; i < a.nzero; i += nb) a.zero[i] = 0.f;
+    }
+    const int B = a.dup ? 2 : a.ns;
+    const int fr = blockIdx.z / B, b = blockIdx.z - fr * B, s = a.dup ? 0 : b;
+    const bool train = fr < a.nf;
+    const float* src = train ? a.train + ((long)(fr * a.ns + s) * a.D) * a.HW : a.test + ((long)s * a.D) * a.HW;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = c0 + ty + 8 * i, p = p0 + tx;
+        tile[ty + 8 * i][tx] = (c < a.D && p < a.HW) ? src[(long)c * a.HW + p] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int p = p0 + ty + 8 * i, c = c0 + tx;
+        if (p >= a.HW || c >= a.D) continue;
+        float v = tile[tx][ty + 8 * i];
+        if (train) {
+            const float* lab = a.label + ((long)(fr * a.ns + s) * a.T) * a.HW + p;
+            float e = 0.f;
+            for (int o = 0; o < a.T; ++o) e += a.E[o * a.D + c] * lab[(long)o * a.HW];
+            v += e;
+        }
+        a.X[((long)b * a.L + (long)fr * a.HW + p) * a.D + c] = v;
+    }
+}
+
+struct TamosBoxArgs {
+    const float *ltrb, *w1, *b1, *bn1;           // ltrb (nf, ns, T, 4, HW); bn1: [weight, bias, running_mean, running_var] of D4 floats
+    float* E1;                                   // ((b, l, o), D4)
+    int nf, ns, dup, D4, HW, T;
+};
+
+// first layer of the ltrb MLP for every object (Conv1d 4 -> D/4, eval-mode BatchNorm1d, ReLU; filter_predictor.py:6-17,214-217)
+__global__ __launch_bounds__(256) void k_tamos_box1(TamosBoxArgs a) {
+    const int B = a.dup ? 2 : a.ns, Ltr = a.nf * a.HW;
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)B * Ltr * a.T * a.D4) return;
+    const int j = (int)(idx % a.D4);
+    const long row = idx / a.D4;
+    const int o = (int)(row % a.T);
+    const long bl = row / a.T;
+    const int b = (int)(bl / Ltr), l = (int)(bl - (long)b * Ltr), fr = l / a.HW, p = l - fr * a.HW;
+    const int s = a.dup ? 0 : b;
+    const float* t = a.ltrb + (((long)(fr * a.ns + s) * a.T + o) * 4) * a.HW + p;
+    float e = a.b1[j];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) e += a.w1[j * 4 + i] * t[(long)i * a.HW];
+    e = (e - a.bn1[2 * a.D4 + j]) / sqrtf(a.bn1[3 * a.D4 + j] + 1e-5f) * a.bn1[j] + a.bn1[a.D4 + j];
+    a.E1[idx] = fmaxf(e, 0.f);
+}
+
+// Weight-only part of the token build (pt_tamos_prepare_f32): W3E[n][o D + k] = E[o][n] W3[n][k], b3E[n] = b3[n] sum_o E[o][n], and the
+// second BatchNorm as the scale / shift of the GEMM epilogue.  Plain loops: runs once per weight update.
+__global__ void k_tamos_prep_box(const float* W3, const float* b3, const float* E, const float* bn2, float* W3E, float* b3E, float* sc2,
+                                 float* sh2, int D, int T) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)D * T * D) return;
+    const int n = (int)(idx / ((long)T * D)), o = (int)((idx / D) % T), k = (int)(idx % D);
+    W3E[idx] = E[o * D + n] * W3[(long)n * D + k];
+    if (o == 0 && k == 0) {
+        float t = 0.f;
+        for (int q = 0; q < T; ++q) t += E[q * D + n];
+        b3E[n] = b3[n] * t;
+        const float sc = bn2[n] / sqrtf(bn2[3 * D + n] + 1e-5f);
+        sc2[n] = sc;
+        sh2[n] = bn2[D + n] - bn2[2 * D + n] * sc;
+    }
+}
+
+// Self-attention among the T <= 16 queries of one (head, batch row) (transformer.py:226-228): grid (nhead, B), thread (i, j) of 16 x 16
+__global__ __launch_bounds__(256) void k_tamos_self_attn(const float* __restrict__ qkv, float* __restrict__ out, int T, int D, int HD,
+                                                         float scale) {
+    __shared__ float S[16][17], Pm[16][17];
+    const int i = threadIdx.x >> 4, j = threadIdx.x & 15, h = blockIdx.x, b = blockIdx.y;
+    const long ld = 3L * D;
+    const bool in = i < T && j < T;
+    float s = -INFINITY;
+    if (in) {
+        const float* q = qkv + ((long)b * T + i) * ld + h * HD;
+        const float* k = qkv + ((long)b * T + j) * ld + D + h * HD;
+        float acc = 0.f;
+        for (int c = 0; c < HD; ++c) acc += (q[c] * scale) * k[c];
+        s = acc;
+    }
+    S[i][j] = s;
+    __syncthreads();
+    float p = 0.f;
+    if (in) {
+        float m = -INFINITY, sum = 0.f;
+        for (int jj = 0; jj < T; ++jj) m = fmaxf(m, S[i][jj]);
+        for (int jj = 0; jj < T; ++jj) sum += expf(S[i][jj] - m);
+        p = expf(s - m) / sum;
+    }
+    Pm[i][j] = p;
+    __syncthreads();
+    if (i < T) {
+        for (int c = j; c < HD; c += 16) {
+            float acc = 0.f;
+            for (int jj = 0; jj < T; ++jj) acc += Pm[i][jj] * qkv[((long)b * T + jj) * ld + 2 * D + h * HD + c];
+            out[((long)b * T + i) * D + h * HD + c] = acc;
+        }
+    }
+}
+
+struct XAttnArgs {
+    const float *mem, *pos, *qk;                 // mem (B, L, D); pos (HW, D); qk (B, R, D), row r = t nhead + h: the folded queries
+    float *part, *pm, *ps;                       // (B, nch, R16, D) context partials, (B, nch, R16) chunk maxima and sums
+    int B, L, D, R, R16, HW, nch;
+    int mlo[8], mhi[8];                          // keys [mlo[b], mhi[b]) of batch row b are padding
+};
+
+// Cross-attention of 16 query rows over one 64-key chunk of the memory (transformer.py:231-232 with pt_tomp's fold): one wavefront.
+//   S^T[key][row] = (mem[key] + pos[key]) . qk[row]      4 tiles of 16 keys, D / 4 MFMAs each (A = memory rows, B = folded queries)
+//   P^T = exp(S^T - chunk maximum of the row)            masked keys and keys past L: exp(-inf) = 0
+//   O^T[c][row] += mem[key][c] P^T[key][row]             the score accumulator IS the B operand (k-slot kq of MFMA r <-> key 4 kq + r)
+// The chunk's (maximum, sum, unnormalised context) go to global memory; k_tamos_xmerge joins the chunks.  DT = D / 16.
+template <int DT>
+__global__ __launch_bounds__(64) void k_tamos_xattn(XAttnArgs a) {
+    const int lane = threadIdx.x, li = lane & 15, kq = lane >> 4;
+    const int ch = blockIdx.x, rt = blockIdx.y, b = blockIdx.z, c0 = ch * 64;
+    const __amdgpu_buffer_rsrc_t rm = pt_rsrc(a.mem, (unsigned)((long)a.B * a.L * a.D * 4));
+    const __amdgpu_buffer_rsrc_t rp = pt_rsrc(a.pos, (unsigned)((long)a.HW * a.D * 4));
+    const __amdgpu_buffer_rsrc_t rq = pt_rsrc(a.qk, (unsigned)((long)a.B * a.R * a.D * 4));
+    const int row = rt * 16 + li;
+    const int mlo = a.mlo[b], mhi = a.mhi[b];
+    f32x4 qf[DT];
+    {
+        const unsigned oq = row < a.R ? (unsigned)((((long)b * a.R + row) * a.D + 4 * kq) * 4) : OOB;
+#pragma unroll
+        for (int v = 0; v < DT; ++v) qf[v] = pt_bload4(rq, oq == OOB ? OOB : oq + 64u * v);
+    }
+    f32x4 st[4];
+    float mc = -INFINITY;
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+        const int l = min(c0 + kt * 16 + li, a.L - 1);
+        const unsigned om = (unsigned)((((long)b * a.L + l) * a.D + 4 * kq) * 4);
+        const unsigned op = (unsigned)(((long)(l % a.HW) * a.D + 4 * kq) * 4);
+        f32x4 sc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int v0 = 0; v0 < DT; v0 += 4) {                     // 8 loads in flight, then 16 MFMAs
+            f32x4 m[4], pp[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                m[u] = pt_bload4(rm, om + 64u * (v0 + u));
+                pp[u] = pt_bload4(rp, op + 64u * (v0 + u));
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) sc = mfma16(m[u][e] + pp[u][e], qf[v0 + u][e], sc);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int key = c0 + kt * 16 + 4 * kq + r;
+            if (key >= a.L || (key >= mlo && key < mhi)) sc[r] = -INFINITY;
+            mc = fmaxf(mc, sc[r]);
+        }
+        st[kt] = sc;
+    }
+    mc = fmaxf(mc, __shfl_xor(mc, 16, 64));
+    mc = fmaxf(mc, __shfl_xor(mc, 32, 64));
+    const float m_use = mc == -INFINITY ? 0.f : mc;              // a chunk of nothing but padding: every weight exp(-inf) = 0
+    f32x4 ot[DT];
+#pragma unroll
+    for (int d = 0; d < DT; ++d) ot[d] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float lsum = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float pe = expf(st[kt][r] - m_use);
+            lsum += pe;
+            const int key = min(c0 + kt * 16 + 4 * kq + r, a.L - 1);   // past L: weight 0 on a finite value
+            const unsigned ov = (unsigned)((((long)b * a.L + key) * a.D + li) * 4);
+            float vf[DT];
+#pragma unroll
+            for (int d = 0; d < DT; ++d) vf[d] = pt_bload1(rm, ov + 64u * d);
+#pragma unroll
+            for (int d = 0; d < DT; ++d) ot[d] = mfma16(vf[d], pe, ot[d]);
+        }
+    }
+    lsum += __shfl_xor(lsum, 16, 64);
+    lsum += __shfl_xor(lsum, 32, 64);
+    const long prow = ((long)b * a.nch + ch) * a.R16 + row;        // row < R16 = 16 gridDim.y
+    if (kq == 0) {
+        a.pm[prow] = mc;
+        a.ps[prow] = lsum;
+    }
+#pragma unroll
+    for (int d = 0; d < DT; ++d)                                    // rows 16 d + 4 kq + r of O^T = 4 consecutive channels
+        *reinterpret_cast<f32x4*>(&a.part[prow * a.D + 16 * d + 4 * kq]) = ot[d];
+}
+
+// ctx[b][row] = sum_ch exp(m_ch - M) part[ch] / sum_ch exp(m_ch - M) s_ch, M = max_ch m_ch, chunks in ascending order: grid (R, B)
+__global__ __launch_bounds__(256) void k_tamos_xmerge(const float* __restrict__ part, const float* __restrict__ pm,
+                                                      const float* __restrict__ ps, float* __restrict__ ctx, int R, int R16, int D,
+                                                      int nch) {
+    const int row = blockIdx.x, b = blockIdx.y;
+    const long base = (long)b * nch * R16 + row;
+    float M = -INFINITY;
+    for (int c = 0; c < nch; ++c) M = fmaxf(M, pm[base + (long)c * R16]);
+    float den = 0.f;
+    for (int c = 0; c < nch; ++c) den += ps[base + (long)c * R16] * expf(pm[base + (long)c * R16] - M);
+    const float inv = 1.f / den;
+    for (int k = threadIdx.x; k < D; k += 256) {
+        float acc = 0.f;
+        for (int c = 0; c < nch; ++c) acc += expf(pm[base + (long)c * R16] - M) * part[(base + (long)c * R16) * D + k];
+        ctx[((long)b * R + row) * D + k] = acc * inv;
+    }
+}
+
+// ---- layouts ----------------------------------------------------------------------------------------------------------------------
+// parameter pack: pt_tomp's transformer and box_encoding tensors, then query_embed_fg.weight (T, D); no test-frame token
+struct TamosPack { PackOff po; size_t E, total; };
+TamosPack tamos_pack(const pt_tomp_dims* d, int T) {
+    TamosPack t{};
+    t.po = pack_layout(d->d_model, d->dim_ff, d->n_enc, d->n_dec);
+    t.E = t.po.fg;                                               // pack_layout's last two entries (fg, testtok: D floats each) give way
+    t.total = t.E + (size_t)T * d->d_model;
+    return t;
+}
+
+struct TamosPrepOff { size_t mq, cq, wov, bov; };
+struct TamosPrep { TamosPrepOff dec[16]; size_t w3e, b3e, sc2, sh2, total; };
+TamosPrep tamos_prep(int D, int nhead, int n_dec, int T) {
+    TamosPrep o{};
+    size_t c = 0;
+    auto take = [&](size_t n) { size_t r = c; c += pt_align_floats(n); return r; };
+    for (int i = 0; i < n_dec; ++i) {
+        TamosPrepOff& p = o.dec[i];
+        p.mq = take((size_t)nhead * D * D); p.cq = take((size_t)nhead * D); p.wov = take((size_t)D * nhead * D); p.bov = take(D);
+    }
+    o.w3e = take((size_t)D * T * D); o.b3e = take(D); o.sc2 = take(D); o.sh2 = take(D);
+    o.total = c;
+    return o;
+}
+
+constexpr int TAMOS_KCH = 64;                                    // keys per k_tamos_xattn chunk
+
+struct TamosCarve { size_t X, QKV, AO, Y, Hd, E1, E2, tgt, sqkv, sao, y, t1, qk, part, pm, ps, ctx, t2, hdn, total; int nch, R, R16; };
+TamosCarve tamos_carve(const pt_tomp_dims* d, int T, int B, int nf) {
+    TamosCarve w{};
+    const size_t D = d->d_model, HW = (size_t)d->H * d->W, L = (nf + 1) * HW, rows = B * L, BT = (size_t)B * T;
+    w.nch = (int)((L + TAMOS_KCH - 1) / TAMOS_KCH);
+    w.R = T * d->nhead;
+    w.R16 = (w.R + 15) / 16 * 16;
+    size_t c = 0;
+    auto take = [&](size_t n) { size_t r = c; c += pt_align_floats(n); return r; };
+    w.X = take(rows * D); w.QKV = take(rows * 3 * D); w.AO = take(rows * D); w.Y = take(rows * D);
+    w.Hd = take(rows * d->dim_ff);
+    w.E1 = take((size_t)B * nf * HW * T * (D / 4)); w.E2 = take((size_t)B * nf * HW * T * D);
+    w.tgt = take(BT * D); w.sqkv = take(BT * 3 * D); w.sao = take(BT * D); w.y = take(BT * D); w.t1 = take(BT * D);
+    w.qk = take(BT * d->nhead * D);
+    w.part = take((size_t)B * w.nch * w.R16 * D); w.pm = take((size_t)B * w.nch * w.R16); w.ps = take((size_t)B * w.nch * w.R16);
+    w.ctx = take(BT * d->nhead * D); w.t2 = take(BT * D); w.hdn = take(BT * d->dim_ff);
+    w.total = c;
+    return w;
+}
+
+// PT_OK when pt_tamos_predict_* covers the call: pt_tomp's dims, 1 <= T <= 16, <= 8 batch rows, and every buffer a kernel addresses
+// through a raw buffer descriptor (pt_rsrc: 32-bit byte offsets) under 4 GiB
+int tamos_check(const pt_tomp_dims* d, int T, int n_train, int n_seq, int parallel) {
+    int rc = dims_check(d);
+    if (rc) return rc;
+    if (n_train <= 0 || n_seq <= 0) return PT_ERR_SHAPE;
+    if (T < 1 || T > 16) return PT_ERR_UNSUPPORTED;
+    const int B = parallel ? 2 : n_seq;
+    if (B > 8 || (parallel && n_seq != 1)) return PT_ERR_UNSUPPORTED;
+    const size_t D = d->d_model, HW = (size_t)d->H * d->W, L = (size_t)(n_train + 1) * HW, rows = B * L;
+    const size_t widest = std::max<size_t>(std::max<size_t>(3 * D, d->dim_ff), (size_t)T * D);
+    const size_t nch = (L + TAMOS_KCH - 1) / TAMOS_KCH, R16 = ((size_t)T * d->nhead + 15) / 16 * 16;
+    if (rows * widest * 4 >= 0xFFFFFFE0ull || (size_t)B * nch * R16 * D * 4 >= 0xFFFFFFE0ull || L > 0x7FFFFFFFull / 8) return PT_ERR_UNSUPPORTED;
+    return PT_OK;
+}
+
+int xattn_route(int D) {
+    return D == 128 ? PT_TAMOS_R_XATTN128 : D == 256 ? PT_TAMOS_R_XATTN256 : D == 384 ? PT_TAMOS_R_XATTN384 : PT_TAMOS_R_XATTN512;
+}
+
+int launch_xattn(const XAttnArgs& a, hipStream_t st, PtRouteLog* log) {
+    const int route = xattn_route(a.D);
+    if (log) {
+        pt_route_note(log, route);
+        return PT_OK;
+    }
+    const dim3 grid(a.nch, a.R16 / 16, a.B), block(64);
+    switch (route) {
+    case PT_TAMOS_R_XATTN128: hipLaunchKernelGGL((k_tamos_xattn<8>), grid, block, 0, st, a); break;
+    case PT_TAMOS_R_XATTN256: hipLaunchKernelGGL((k_tamos_xattn<16>), grid, block, 0, st, a); break;
+    case PT_TAMOS_R_XATTN384: hipLaunchKernelGGL((k_tamos_xattn<24>), grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL((k_tamos_xattn<32>), grid, block, 0, st, a); break;
+    }
+    PT_CHECK_LAUNCH();
+    return PT_OK;
+}
+
+int tamos_predict_impl(const pt_tomp_dims* d, int T, const float* params, const float* prepared, const float* pos, const float* train_feat,
+                       const float* test_feat, const float* train_label, const float* train_ltrb, int n_train, int n_seq, int parallel,
+                       int num_gth_frames, float* filters, float* enc_feat, void* ws, size_t ws_bytes, void* stream, PtRouteLog* log) {
+    if (!d || !params || !prepared || !pos || !train_feat || !test_feat || !train_label || !train_ltrb || !filters || !enc_feat || !ws)
+        return PT_ERR_NULL;
+    int rc = tamos_check(d, T, n_train, n_seq, parallel);
+    if (rc) return rc;
+    if (num_gth_frames < 0 || num_gth_frames > n_train) return PT_ERR_SHAPE;
+    const int B = parallel ? 2 : n_seq;
+    const int D = d->d_model, ff = d->dim_ff, NH = d->nhead, HD = D / NH, HW = d->H * d->W, Ltr = n_train * HW, L = Ltr + HW, D4 = D / 4,
+              BT = B * T;
+    const TamosCarve cv = tamos_carve(d, T, B, n_train);
+    if (ws_bytes < cv.total * sizeof(float) || ((uintptr_t)ws % 256) != 0) return PT_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    float* base = (float*)ws;
+    const TamosPack tp = tamos_pack(d, T);
+    const PackOff& po = tp.po;
+    const TamosPrep pl = tamos_prep(D, NH, d->n_dec, T);
+    const float* P = params;
+    const float* E = P + tp.E;
+    float *X = base + cv.X, *QKV = base + cv.QKV, *AO = base + cv.AO, *Y = base + cv.Y, *Hd = base + cv.Hd;
+
+    // ---- tokens (filter_predictor.py:204-222)
+    {
+        TamosTokArgs t{train_feat, test_feat, train_label, E, X, n_train, n_seq, parallel ? 1 : 0, D, HW, L, T, base + cv.tgt, BT * D};
+        PT_TOMP_LAUNCH(PT_TAMOS_R_TOKENS, k_tamos_tokens, dim3((HW + 31) / 32, (D + 31) / 32, (n_train + 1) * B), dim3(256), 0, st, t);
+        TamosBoxArgs bx{train_ltrb, P + po.bw1, P + po.bb1, P + po.bn1, base + cv.E1, n_train, n_seq, parallel ? 1 : 0, D4, HW, T};
+        const long tot = (long)B * Ltr * T * D4;
+        PT_TOMP_LAUNCH(PT_TAMOS_R_BOX1, k_tamos_box1, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, bx);
+        const int Mo = B * Ltr * T;                               // one row per (batch row, position, object)
+        GemmArgs g = gemm_args(base + cv.E1, D4, Mo, P + po.bw2, Mo, D, D4, P + po.bb2, base + cv.E2, D);
+        g.scale = prepared + pl.sc2; g.shift = prepared + pl.sh2; g.relu = 1;
+        if ((rc = launch_gemm(g, st, false, log))) return rc;
+        // the same buffer as (B Ltr) rows of T D: X += E2 (diag(E[o]) W3)^T + b3 sum_o E[o]
+        g = gemm_args(base + cv.E2, (long)T * D, (long)B * Ltr, prepared + pl.w3e, B * Ltr, D, T * D, prepared + pl.b3e, X, D);
+        g.R = X; g.c_seg = Ltr; g.c_segstride = L;
+        if ((rc = launch_gemm(g, st, false, log))) return rc;
+    }
+    AttnArgs at{};
+    at.qkv = QKV; at.qkv_bytes = (unsigned)((long)B * L * 3 * D * 4); at.out = AO; at.L = L; at.D = D; at.nhead = NH;
+    at.scale = 1.0f / sqrtf((float)HD);
+    for (int b = 0; b < 8; ++b) at.mlo[b] = at.mhi[b] = 0;
+    if (parallel) {                                               // filter_predictor.py:298-299: batch row 1 only
+        at.mlo[1] = num_gth_frames * HW;
+        at.mhi[1] = L - HW;
+    }
+    if ((rc = run_encoder(d, po, P, pos, at, B, L, HW, X, QKV, AO, Y, Hd, st, log))) return rc;
+
+    // ---- decoder (transformer.py:224-238), T queries per batch row, post-norm; tgt starts as zeros (cleared by k_tamos_tokens)
+    float *tgt = base + cv.tgt, *sqkv = base + cv.sqkv, *sao = base + cv.sao, *y = base + cv.y, *t1 = base + cv.t1, *t2 = base + cv.t2;
+    XAttnArgs xa{};
+    xa.mem = X; xa.pos = pos; xa.qk = base + cv.qk; xa.part = base + cv.part; xa.pm = base + cv.pm; xa.ps = base + cv.ps;
+    xa.B = B; xa.L = L; xa.D = D; xa.R = cv.R; xa.R16 = cv.R16; xa.HW = HW; xa.nch = cv.nch;
+    for (int b = 0; b < 8; ++b) { xa.mlo[b] = at.mlo[b]; xa.mhi[b] = at.mhi[b]; }
+    auto with_qpos = [&](GemmArgs& g, int cols) {                  // A[r] + E[r % T] on the leading `cols` output columns
+        g.pos = E; g.pos_bytes = (unsigned)((long)T * D * 4); g.pos_cols = cols; g.L = T; g.HW = T;
+    };
+    for (int i = 0; i < d->n_dec; ++i) {
+        const DecOff& dc = po.dec[i];
+        const TamosPrepOff& pp = pl.dec[i];
+        // self-attention: q = k = tgt + query_pos, v = tgt
+        GemmArgs g = gemm_args(tgt, D, BT, P + dc.sa.w_in, BT, 3 * D, D, P + dc.sa.b_in, sqkv, 3 * D);
+        with_qpos(g, 2 * D);
+        if ((rc = launch_gemm(g, st, false, log))) return rc;
+        PT_TOMP_LAUNCH(PT_TAMOS_R_SELF_ATTN, k_tamos_self_attn, dim3(NH, B), dim3(256), 0, st, sqkv, sao, T, D, HD, at.scale);
+        g = gemm_args(sao, D, BT, P + dc.sa.w_out, BT, D, D, P + dc.sa.b_out, y, D);
+        g.R = tgt;
+        if ((rc = launch_gemm(g, st, false, log))) return rc;
+        if ((rc = launch_ln_rows(y, t1, P + dc.n1g, P + dc.n1b, BT, D, st, log))) return rc;
+        // cross-attention, query folded onto the keys: qk[b][t][h] = Wk_h^T (Wq_h (t1 + query_pos) + bq_h) / sqrt(HD)
+        g = gemm_args(t1, D, BT, prepared + pp.mq, BT, NH * D, D, prepared + pp.cq, base + cv.qk, (long)NH * D);
+        with_qpos(g, NH * D);
+        if ((rc = launch_gemm(g, st, false, log))) return rc;
+        if ((rc = launch_xattn(xa, st, log))) return rc;
+        PT_TOMP_LAUNCH(PT_TAMOS_R_XMERGE, k_tamos_xmerge, dim3(cv.R, B), dim3(256), 0, st, base + cv.part, base + cv.pm, base + cv.ps,
+                       base + cv.ctx, cv.R, cv.R16, D, cv.nch);
+        // value projection + out_proj folded over the heads' contexts, residual t1
+        g = gemm_args(base + cv.ctx, (long)NH * D, BT, prepared + pp.wov, BT, D, NH * D, prepared + pp.bov, y, D);
+        g.R = t1;
+        if ((rc = launch_gemm(g, st, false, log))) return rc;
+        if ((rc = launch_ln_rows(y, t2, P + dc.n2g, P + dc.n2b, BT, D, st, log))) return rc;
+        g = gemm_args(t2, D, BT, P + dc.w1, BT, ff, D, P + dc.b1, base + cv.hdn, ff);
+        g.relu = 1;
+        if ((rc = launch_gemm(g, st, false, log))) return rc;
+        g = gemm_args(base + cv.hdn, ff, BT, P + dc.w2, BT, D, ff, P + dc.b2, y, D);
+        g.R = t2;
+        if ((rc = launch_gemm(g, st, false, log))) return rc;
+        if ((rc = launch_ln_rows(y, tgt, P + dc.n3g, P + dc.n3b, BT, D, st, log))) return rc;
+    }
+    // the decoder's final norm (transformer.py:140-141)
+    if ((rc = launch_ln_rows(tgt, filters, P + po.dng, P + po.dnb, BT, D, st, log))) return rc;
+    PT_TOMP_LAUNCH(PT_TOMP_R_TO_NCHW, k_tokens_to_nchw, dim3((HW + 31) / 32, (D + 31) / 32, B), dim3(256), 0, st, X, enc_feat, B, L, D,
+                   HW, Ltr);
+    return PT_OK;
+}
+}  // namespace
+
+extern "C" size_t pt_tamos_param_floats(const pt_tomp_dims* d, int num_tokens) {
+    if (dims_check(d) || num_tokens < 1 || num_tokens > 16) return 0;
+    return tamos_pack(d, num_tokens).total;
+}
+
+extern "C" size_t pt_tamos_prepared_floats(const pt_tomp_dims* d, int num_tokens) {
+    if (dims_check(d) || num_tokens < 1 || num_tokens > 16) return 0;
+    return tamos_prep(d->d_model, d->nhead, d->n_dec, num_tokens).total;
+}
+
+extern "C" int pt_tamos_prepare_f32(const pt_tomp_dims* d, int num_tokens, const float* params, float* prepared, void* stream) {
+    if (!d || !params || !prepared) return PT_ERR_NULL;
+    int rc = dims_check(d);
+    if (rc) return rc;
+    if (num_tokens < 1 || num_tokens > 16) return PT_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    const int D = d->d_model, NH = d->nhead, T = num_tokens;
+    const TamosPack tp = tamos_pack(d, T);
+    const TamosPrep pl = tamos_prep(D, NH, d->n_dec, T);
+    const float scale = 1.0f / sqrtf((float)(D / NH));
+    for (int i = 0; i < d->n_dec; ++i) {
+        const DecOff& dc = tp.po.dec[i];
+        const TamosPrepOff& pp = pl.dec[i];
+        const float *ca_w = params + dc.ca.w_in, *ca_b = params + dc.ca.b_in;
+        hipLaunchKernelGGL(k_prep_mq, dim3((unsigned)(((long)NH * D * D + 255) / 256)), dim3(256), 0, st, ca_w, ca_b, ca_w + (size_t)D * D,
+                           prepared + pp.mq, prepared + pp.cq, D, NH, scale);
+        PT_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_prep_ov, dim3((unsigned)(((long)NH * D * D + 255) / 256)), dim3(256), 0, st, params + dc.ca.w_out,
+                           params + dc.ca.b_out, ca_w + (size_t)2 * D * D, ca_b + 2 * D, prepared + pp.wov, prepared + pp.bov, D, NH);
+        PT_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(k_tamos_prep_box, dim3((unsigned)(((long)D * T * D + 255) / 256)), dim3(256), 0, st, params + tp.po.bw3,
+                       params + tp.po.bb3, params + tp.E, params + tp.po.bn2, prepared + pl.w3e, prepared + pl.b3e, prepared + pl.sc2,
+                       prepared + pl.sh2, D, T);
+    PT_CHECK_LAUNCH();
+    return PT_OK;
+}
+
+extern "C" size_t pt_tamos_predict_ws_bytes(const pt_tomp_dims* d, int num_tokens, int n_train, int n_seq, int parallel) {
+    if (!d || tamos_check(d, num_tokens, n_train, n_seq, parallel)) return 0;
+    return tamos_carve(d, num_tokens, parallel ? 2 : n_seq, n_train).total * sizeof(float);
+}
+
+extern "C" int pt_tamos_predict_f32(const pt_tomp_dims* d, int num_tokens, const float* params, const float* prepared, const float* pos,
+                                    const float* train_feat, const float* test_feat, const float* train_label, const float* train_ltrb,
+                                    int n_train, int n_seq, int parallel, int num_gth_frames, float* filters, float* enc_feat, void* ws,
+                                    size_t ws_bytes, void* stream) {
+    return tamos_predict_impl(d, num_tokens, params, prepared, pos, train_feat, test_feat, train_label, train_ltrb, n_train, n_seq, parallel,
+                              num_gth_frames, filters, enc_feat, ws, ws_bytes, stream, nullptr);
+}
+
+extern "C" int pt_tamos_predict_routes(const pt_tomp_dims* d, int num_tokens, int n_train, int n_seq, int parallel, int* routes, int cap,
+                                       int* n_routes) {
+    if (!routes || !n_routes || !d) return PT_ERR_NULL;
+    if (cap < 0) return PT_ERR_SHAPE;
+    PtRouteLog log{routes, cap, 0};
+    const int rc = tamos_predict_impl(d, num_tokens, route_fake(0), route_fake(1), route_fake(2), route_fake(3), route_fake(4),
+                                      route_fake(5), route_fake(6), n_train, n_seq, parallel, 0, route_fake(7), route_fake(8),
+                                      route_fake(9), ~(size_t)0, nullptr, &log);
     return route_finish(rc, log, routes, cap, n_routes);
 }
 

@@ -64,6 +64,9 @@ What gets rebound (import path = contract; nothing in the reference tree is edit
   localize_target / update_memory, pytracking.tracker.eco.optim.FilterOptim.run
                                              (ECO's per-frame Fourier-domain path and filter update; only with install(eco=True))
                                                                                       -> pytracking_amd.eco
+  ltr.models.transformer.filter_predictor.GOTFilterPredictor
+                                             (TaMOs multi-object filter predictor, inference; only with install(tamos=True))
+                                                                                      -> pytracking_amd.tamos
 
 Dispatch rule of the rebound *functions*: device fp32 tensors of a shape the gfx950 kernels cover go to the C ABI;
 everything else (CPU tensors, dilations, grouped filters, K*K > 16, more than 16 filters) is outside the hot path and
@@ -326,6 +329,21 @@ def _install_tomp():
     _rebind(hmod, "DenseBoxRegressor", _choosing_class(
         hmod.DenseBoxRegressor, lambda num_channels, *args, **kw: num_channels % 64 == 0 and num_channels <= 512,
         _tm.DenseBoxRegressor, "DenseBoxRegressor: channel count outside the gfx950 hot path"))
+
+
+def _install_tamos():
+    """TaMOs multi-object filter predictor (inference): `tamosnet_resnet50` / `tamosnet_swin_base` (ltr/models/tracking/tamosnet.py) reach
+    `GOTFilterPredictor` through the module attribute.  The gfx950 class is chosen for the gfx950 transformer container with
+    label_enc 'gaussian', box_enc 'ltrb_token' and 1 <= num_tokens <= 16; anything else builds the reference class."""
+    from . import tamos as _ta
+    try:
+        pmod = importlib.import_module("ltr.models.transformer.filter_predictor")
+    except Exception:
+        return
+    _rebind(pmod, "GOTFilterPredictor", _choosing_class(
+        pmod.GOTFilterPredictor, _ta.covered, _ta.GOTFilterPredictor,
+        "GOTFilterPredictor: configuration outside the gfx950 hot path",
+        doc="Covered configuration -> gfx950 multi-object predictor; anything else -> the reference class."))
 
 
 def _install_clf_head(feature_heads=False):
@@ -892,7 +910,7 @@ def _install_atom_cg():
 
 def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=True, iou_refine=True, preprocessing=True,
             candidate_matching=True, kys=True, iou_feat=False, label_encoder=False, decoder=False, feature_heads=False,
-            rts_fusion=False, seg_readout=False, eco=False):
+            rts_fusion=False, seg_readout=False, eco=False, tamos=False):
     """Rebind the boundary symbols.  Call after the reference is importable (`sys.path`) and before networks or
     trackers are constructed.  Idempotent.  If an installer raises, what was rebound so far is undone before the exception
     propagates (an optional reference module that does not import is not a failure: its family is skipped)."""
@@ -914,7 +932,7 @@ def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=T
                                 (candidate_matching, _install_candidate_matching), (kys, _install_kys), (atom_cg, _install_atom_cg),
                                 (iou_feat, _install_iou_feat), (label_encoder, _install_label_encoder),
                                 (decoder, _install_lwl_decoder), (rts_fusion, _install_rts_fusion),
-                                (seg_readout, _install_seg_readout), (eco, _install_eco)):
+                                (seg_readout, _install_seg_readout), (eco, _install_eco), (tamos, _install_tamos)):
             if flag:
                 installer()
     except BaseException:

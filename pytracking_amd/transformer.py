@@ -12,7 +12,8 @@ loads with `strict=True` and `pytracking/tracker/tomp/tomp.py:282-303` runs unch
 
 The torch submodules (nn.MultiheadAttention, nn.Linear, ...) are parameter holders only: their forward is never called.
 Inference only (the tracker runs under `torch.no_grad()`, tomp.py:284); training mode, pre-norm layers, non-ReLU
-activations and multi-object attention raise NotImplementedError -- there is no stock-PyTorch fallback.
+activations raise NotImplementedError -- there is no stock-PyTorch fallback.  The multi-object predictor of TaMOs (T object queries
+per batch row) is `pytracking_amd.tamos.GOTFilterPredictor`; the multi-object box regressor is not on the hot path.
 """
 import ctypes
 
@@ -275,12 +276,11 @@ class FilterPredictor(nn.Module):
 def _project(linear, filt, C):
     x = filt.reshape(-1, C).contiguous()
     _require_device(x)
-    if x.shape[0] > 8:
-        raise NotImplementedError("more than 8 filters per call")
     y = torch.empty_like(x)
-    rc = _lib.lib().pt_tomp_linear_f32(_ptr(linear.weight), _ptr(linear.bias), _ptr(x), _ptr(y), x.shape[0], C, C, 0,
-                                       _stream())
-    _lib.check(rc, "pt_tomp_linear_f32")
+    for r0 in range(0, x.shape[0], 8):                      # pt_tomp_linear_f32 takes at most 8 rows (TaMOs: up to 16 filters per sequence)
+        n = min(8, x.shape[0] - r0)
+        rc = _lib.lib().pt_tomp_linear_f32(_ptr(linear.weight), _ptr(linear.bias), _ptr(x[r0:]), _ptr(y[r0:]), n, C, C, 0, _stream())
+        _lib.check(rc, "pt_tomp_linear_f32")
     return y.reshape(filt.shape)
 
 
