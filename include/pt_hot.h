@@ -311,7 +311,8 @@ int pt_tomp_linear_routes(int B, int N, int K, int* routes, int cap, int* n_rout
  *   Transformer.forward with T = num_tokens object queries  (ltr/models/transformer/transformer.py:90-96,172-180,224-238)
  * for label_enc = 'gaussian' and box_enc = 'ltrb_token' (ltr/train_settings/tamos/*.py), as the tracker calls it every frame
  * (pytracking/tracker/tamos/tamos.py:289-306).  The classifier's scores come from the multi-filter correlation that exists already.
- * Out of scope: heads.FPN, the multi-object DenseBoxRegressor on the FPN map, TaMOs.track end to end, training.  pt_tomp_* is unchanged.
+ * heads.FPN and the multi-object DenseBoxRegressor on the FPN map: pt_fpn2_f32 / pt_tamos_bbreg_f32 below.  Out of scope: TaMOs.track's
+ * host glue, training.  pt_tomp_* is unchanged.
  *
  * Pack: pt_tomp's transformer tensors in pt_tomp's order, then the 14 box_encoding tensors in pt_tomp's order, then
  * query_embed_fg.weight (T, D).  There is no test-frame token.  pt_tamos_param_floats() is the length (0: not covered).
@@ -358,6 +359,47 @@ int pt_tamos_predict_f32(const pt_tomp_dims* dims, int num_tokens, const float* 
                          void* ws, size_t ws_bytes, void* stream);
 int pt_tamos_predict_routes(const pt_tomp_dims* dims, int num_tokens, int n_train, int n_seq, int parallel, int* routes, int cap,
                             int* n_routes);
+
+/* ------------------------------------------------------------------------------------------------
+ * TaMOs heads -- replace, for inference, what pytracking/tracker/tamos/tamos.py:308-317 runs behind the filter predictor:
+ *   FPN.forward with two levels                     (ltr/models/transformer/heads.py:144-162, torchvision FeaturePyramidNetwork)
+ *   DenseBoxRegressor.forward with T filters / seq  (ltr/models/transformer/heads.py:119-141, the `attention.dim() == 5` branch)
+ * Both stand on one kernel, k_conv3: a direct 3x3 token convolution (stride 1, padding 1, fp32 MFMA) in which one workgroup owns a
+ * 128 x 64 output tile of one image and walks K = 9 Cin itself -- no per-tap partial buffer, no atomics, the same bits every call.
+ *
+ * pt_tamos_bbreg_f32: feat (n_img, D, H, W) NCHW; filters (n_img, T, D), the unprojected filters of each image's sequence;
+ * ltrb (n_img, T, 4, H, W); params = the pack of pt_tomp_bbreg_f32 (pt_tomp_bbreg_param_floats), one pack serves both.  Computes
+ *   filter_proj = linear(filters); attention[o] = feat . filter_proj[o]; tower(attention[o] (.) feat) over n_img T images;
+ *   exp(bbreg_layer(.)).  The attended copies are never written: the first layer's loader multiplies by the per-pixel scalar.  Every
+ *   tower layer leaves per-tile (sum, sum of squares) of its output (bias included); they are summed per image in slot order in double and
+ *   the next layer's loader applies GroupNorm(1, D) + affine + ReLU, zero padding after the transform.
+ * pt_fpn2_f32: feat_hi (n, C_hi, H2, W2), feat_lo (n, C_lo, H3, W3) -> feat2 (n, D, H2, W2) and, if want_feat3, feat3 (n, D, H3, W3)
+ *   (feat3 may be NULL and is left untouched otherwise).  pack (pt_fpn2_param_floats): inner_blocks.0 weight (D, C_hi), bias (D);
+ *   inner_blocks.1 weight (D, C_lo), bias (D); layer_blocks.0 weight (D, ky, kx, D), bias (D); layer_blocks.1 weight (D, ky, kx, D),
+ *   bias (D).  feat3 = layer1(lat_lo); feat2 = layer0(lat_hi + nearest(lat_lo -> (H2, W2))) with the source index
+ *   min(floor(dst * (float)in / out), in - 1) of F.interpolate(mode="nearest", size=...), added in the 3x3 loader.
+ * Covered: D (and d_model) a multiple of 64 up to 512, C_hi / C_lo multiples of 64 up to 2048, 1 <= T <= 16, any H, W >= 1, every
+ * buffer under 4 GiB (32-bit byte offsets), at most 65535 images.  Otherwise the *_ws_bytes queries return 0 and the entry points
+ * PT_ERR_SHAPE / PT_ERR_UNSUPPORTED before any launch.  Asynchronous on `stream`, no host synchronisation, graph-capturable.
+ * pt_tamos_bbreg_routes / pt_fpn2_routes: host only, like pt_tomp_bbreg_routes: the shared launchers report their
+ * PT_TOMP_R_* ids, the new launches ids of enum pt_heads_route below (from 2000: no existing id moves) --
+ * k_nchw_to_tokens, k_conv3<plain | per-row scalar | GroupNorm loader | top-down resize + add>, k_conv3_gn_finish, k_reg_out.
+ * ---------------------------------------------------------------------------------------------- */
+enum pt_heads_route {
+    PT_HEADS_R_NCHW_TOKENS = 2000, PT_HEADS_R_CONV3_PLAIN, PT_HEADS_R_CONV3_ROWSCALE, PT_HEADS_R_CONV3_GN, PT_HEADS_R_CONV3_UPADD,
+    PT_HEADS_R_CONV3_GN_FINISH, PT_HEADS_R_REG_OUT,
+    PT_HEADS_R_END
+};
+size_t pt_tamos_bbreg_ws_bytes(int n_img, int T, int d_model, int H, int W);
+int pt_tamos_bbreg_f32(const float* params, const float* feat, const float* filters, float* ltrb, int n_img, int T, int d_model,
+                       int H, int W, void* ws, size_t ws_bytes, void* stream);
+int pt_tamos_bbreg_routes(int n_img, int T, int d_model, int H, int W, int* routes, int cap, int* n_routes);
+size_t pt_fpn2_param_floats(int C_hi, int C_lo, int d_out);
+size_t pt_fpn2_ws_bytes(int n, int C_hi, int C_lo, int d_out, int H2, int W2, int H3, int W3);
+int pt_fpn2_f32(const float* params, const float* feat_hi, const float* feat_lo, float* feat2, float* feat3, int n, int C_hi,
+                int C_lo, int d_out, int H2, int W2, int H3, int W3, int want_feat3, void* ws, size_t ws_bytes, void* stream);
+int pt_fpn2_routes(int n, int C_hi, int C_lo, int d_out, int H2, int W2, int H3, int W3, int want_feat3, int* routes, int cap,
+                   int* n_routes);
 
 /* ------------------------------------------------------------------------------------------------
  * Classification-feature head -- `residual_bottleneck(num_blocks=0, final_conv=True, l2norm=True)`

@@ -95,6 +95,10 @@ TAMOS_ROUTE_BASE = 1000
 TAMOS_ROUTES = ("TAMOS_TOKENS", "TAMOS_BOX1", "TAMOS_SELF_ATTN", "TAMOS_XATTN128", "TAMOS_XATTN256", "TAMOS_XATTN384", "TAMOS_XATTN512",
                 "TAMOS_XMERGE")
 PT_TAMOS_MAX_ROUTES = 512
+# `enum pt_heads_route` of include/pt_hot.h (the launches pt_tamos_bbreg_routes / pt_fpn2_routes report next to TOMP_ROUTES): from 2000
+HEADS_ROUTE_BASE = 2000
+HEADS_ROUTES = ("HEADS_NCHW_TOKENS", "HEADS_CONV3_PLAIN", "HEADS_CONV3_ROWSCALE", "HEADS_CONV3_GN", "HEADS_CONV3_UPADD", "HEADS_CONV3_GN_FINISH",
+                "HEADS_REG_OUT")
 
 EXPORTS = [
     "pt_strerror", "pt_abi_version",
@@ -111,6 +115,8 @@ EXPORTS = [
     "pt_tomp_predict_routes", "pt_tomp_bbreg_routes", "pt_tomp_linear_routes",
     "pt_tamos_param_floats", "pt_tamos_prepared_floats", "pt_tamos_prepare_f32", "pt_tamos_predict_ws_bytes", "pt_tamos_predict_f32",
     "pt_tamos_predict_routes",
+    "pt_tamos_bbreg_ws_bytes", "pt_tamos_bbreg_f32", "pt_tamos_bbreg_routes",
+    "pt_fpn2_param_floats", "pt_fpn2_ws_bytes", "pt_fpn2_f32", "pt_fpn2_routes",
     "pt_clf_head_ws_bytes", "pt_clf_head_f32", "pt_feat_head_ws_bytes", "pt_feat_head_f32", "pt_max2d_f32", "pt_localize_f32", "pt_localize_decide_f32",
     "pt_localize_constants_f32", "pt_localize_advanced_f32", "pt_localize_advanced_sync_f32",
     "pt_iou_param_floats", "pt_iou_prepared_floats", "pt_iou_prepare_f32", "pt_iou_refine_ws_bytes", "pt_iou_refine_f32", "pt_iou_refine_sync_f32",
@@ -361,6 +367,20 @@ def lib():
     L.pt_tamos_predict_f32.argtypes = [dp, i, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, vp, vp, vp, sz, vp]
     L.pt_tamos_predict_routes.restype = i
     L.pt_tamos_predict_routes.argtypes = [dp, i, i, i, i, ip, i, ip]
+    L.pt_tamos_bbreg_ws_bytes.restype = sz
+    L.pt_tamos_bbreg_ws_bytes.argtypes = [i] * 5
+    L.pt_tamos_bbreg_f32.restype = i
+    L.pt_tamos_bbreg_f32.argtypes = [vp, vp, vp, vp] + [i] * 5 + [vp, sz, vp]
+    L.pt_tamos_bbreg_routes.restype = i
+    L.pt_tamos_bbreg_routes.argtypes = [i] * 5 + [ip, i, ip]
+    L.pt_fpn2_param_floats.restype = sz
+    L.pt_fpn2_param_floats.argtypes = [i] * 3
+    L.pt_fpn2_ws_bytes.restype = sz
+    L.pt_fpn2_ws_bytes.argtypes = [i] * 8
+    L.pt_fpn2_f32.restype = i
+    L.pt_fpn2_f32.argtypes = [vp] * 5 + [i] * 9 + [vp, sz, vp]
+    L.pt_fpn2_routes.restype = i
+    L.pt_fpn2_routes.argtypes = [i] * 9 + [ip, i, ip]
     L.pt_clf_head_ws_bytes.restype = sz
     L.pt_clf_head_ws_bytes.argtypes = [i] * 5
     L.pt_clf_head_f32.restype = i

@@ -2459,3 +2459,489 @@ extern "C" int pt_feat_head_f32(const float* feat, const float* weight_tap_major
     PT_CHECK_LAUNCH();
     return PT_OK;
 }
+
+// ==================================================================================================================
+// TaMOs heads (pt_tamos_bbreg_*, pt_fpn2_*, include/pt_hot.h): the two-level FPN of heads.py:144-162 and the multi-object
+// DenseBoxRegressor of heads.py:119-141 on the FPN map (T attended copies of a 48 x 72 map: 34 560 token rows per tower layer).
+//   k_conv3<MODE>   direct 3x3 token convolution, stride 1, padding 1: one workgroup owns a 128 x 64 output tile of ONE image and walks
+//                   K = 9 Cin itself (no per-tap partial buffer, no split-K, no atomics); the loader applies, per MODE, nothing / a
+//                   per-row scalar (attention (.) feature) / the previous layer's GroupNorm + affine + ReLU / the FPN's top-down
+//                   "nearest resize + add"; the zero padding is applied AFTER that transform (a halo pixel contributes 0); the epilogue
+//                   adds the bias, writes token-major or NCHW and leaves the tile's (sum, sum of squares) in a fixed slot
+//   k_conv3_gn_finish   the slots of an image summed in slot order in double -> (mean, rstd) per image, which the next loader reads
+//   k_reg_out       the 4-channel bbreg_layer + exp on the last GroupNorm'ed map, one wavefront per run of 8 pixels
+// ==================================================================================================================
+namespace {
+
+constexpr int C3_BM = 128, C3_BN = 64;
+enum { C3_PLAIN = 0, C3_ROWSCALE = 1, C3_GN = 2, C3_UPADD = 3 };
+
+struct Conv3Args {
+    const float* A; unsigned a_bytes; int a_div;      // token-major (source image, HW, Cin); grid image z reads source image z / a_div
+    const float* Wt; unsigned w_bytes;                // (N, 9, Cin) tap-major
+    const float* bias;
+    float* C; int nchw;                               // (z, HW, N) token-major, or (z, N, H, W)
+    int H, W, HW, Cin, N;
+    const float* rowscale; unsigned rs_bytes;         // C3_ROWSCALE: (source image, HW, a_div): the gathered pixel q of the source image
+                                                      // enters as rowscale[src][q][z % a_div] * A[src][q][k]
+    const float* gn_mr; const float* gn_gam; const float* gn_bet;     // C3_GN: (mean, rstd) per grid image, affine per channel
+    const float* A2; unsigned a2_bytes; int H3, W3; float sy, sx;     // C3_UPADD: + A2[src][nearest(y, x)][k], (source image, H3 W3, Cin)
+    float* stats;                                     // optional: (z, row tile, column tile, 2) tile sums of the output incl. bias
+};
+
+// Tile choice: 128 x 64 x 32, eight wavefronts (4 x 2, each 32 x 32 = 2 x 2 MFMA fragments), 54 KB of LDS in two
+// stages -> two workgroups per CU; LDS layout, fragment permutation (gemm_prow) and register ring as gemm_tile (mfma_gemm.h).
+template <int MODE>
+__global__ __launch_bounds__(512) void k_conv3(Conv3Args g) {
+    constexpr int BM = C3_BM, BN = C3_BN, BK = 32, LS = 36, MT = 2, NT = 2, WGN = 2, STAGE = (BM + BN) * LS, PD = 2;
+    __shared__ __attribute__((aligned(16))) float lds[2][STAGE];
+    __shared__ double red[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), wm = wave / WGN, wn = wave % WGN;
+    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN, z = blockIdx.z;
+    const int simg = z / g.a_div, K = 9 * g.Cin;
+    const __amdgpu_buffer_rsrc_t rsA = pt_rsrc(g.A, g.a_bytes), rsW = pt_rsrc(g.Wt, g.w_bytes);
+    const __amdgpu_buffer_rsrc_t rsA2 = pt_rsrc(MODE == C3_UPADD ? g.A2 : g.A, MODE == C3_UPADD ? g.a2_bytes : 16u);
+    const __amdgpu_buffer_rsrc_t rsS = pt_rsrc(MODE == C3_ROWSCALE ? g.rowscale : g.A, MODE == C3_ROWSCALE ? g.rs_bytes : 16u);
+    // loader: thread t covers 16 bytes (k-quad t & 7) of A rows t / 8 and t / 8 + 64 and of W row t / 8
+    const int lr = tid >> 3, lc4 = (tid & 7) * 4;
+    unsigned arow[2], amask[2];
+    int py[2], px[2];
+    unsigned soff[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int p = m0 + lr + 64 * i;
+        const bool ok = p < g.HW;
+        const int pc = ok ? p : 0;
+        py[i] = pc / g.W;
+        px[i] = pc - py[i] * g.W;
+        unsigned m = 0u;
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int y = py[i] + tap / 3 - 1, x = px[i] + tap % 3 - 1;
+            m |= (ok && y >= 0 && y < g.H && x >= 0 && x < g.W) ? (1u << tap) : 0u;
+        }
+        amask[i] = m;                                                     // the taps of this row that fall inside the map
+        arow[i] = (unsigned)((((long)simg * g.HW + pc) * g.Cin + lc4) * 4);
+        soff[i] = (unsigned)((((long)simg * g.HW + pc) * g.a_div + (z - simg * g.a_div)) * 4);
+    }
+    const unsigned woff = n0 + lr < g.N ? (unsigned)((((long)(n0 + lr)) * K + lc4) * 4) : OOB;
+    const int nst = K / BK;                                               // Cin % 64 == 0: a stage never straddles two taps
+    f32x4 ra[PD][2], ra2[PD][2], rb[PD], rgam[PD], rbet[PD];
+    float rsc[PD][2];                                                     // C3_ROWSCALE: the scalar of the gathered pixel
+    unsigned inm[PD] = {0u, 0u};
+    float gmean = 0.f, grstd = 1.f;
+    auto fetch = [&](int s, int sl) {                                     // a stage past the end re-fetches the last one (never consumed)
+        const int sc = min(s, nst - 1), k0 = sc * BK, tap = k0 / g.Cin, c0 = k0 - tap * g.Cin;
+        const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
+        const unsigned delta = (unsigned)(dy * g.W + dx) * (unsigned)(g.Cin * 4) + (unsigned)(c0 * 4);     // modulo 2^32: arow + delta is exact
+        unsigned m = 0u;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const bool in = ((amask[i] >> tap) & 1u) != 0u;
+            m |= in ? (1u << i) : 0u;
+            ra[sl][i] = pt_bload4(rsA, in ? arow[i] + delta : OOB);
+            if (MODE == C3_ROWSCALE) rsc[sl][i] = pt_bload1(rsS, in ? soff[i] + (unsigned)(dy * g.W + dx) * (unsigned)(g.a_div * 4) : OOB);
+            if (MODE == C3_UPADD) {                                       // F.interpolate(mode='nearest', size=...): floor(dst * (in / out)) in fp32
+                const int ly = min((int)floorf((float)(py[i] + dy) * g.sy), g.H3 - 1), lx = min((int)floorf((float)(px[i] + dx) * g.sx), g.W3 - 1);
+                ra2[sl][i] = pt_bload4(rsA2, in ? (unsigned)((((long)simg * g.H3 * g.W3 + ly * g.W3 + lx) * g.Cin + c0 + lc4) * 4) : OOB);
+            }
+        }
+        inm[sl] = m;
+        if (MODE == C3_GN) {
+            rgam[sl] = *reinterpret_cast<const f32x4*>(g.gn_gam + c0 + lc4);
+            rbet[sl] = *reinterpret_cast<const f32x4*>(g.gn_bet + c0 + lc4);
+        }
+        rb[sl] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsW, woff, (unsigned)sc * (BK * 4u), 0));
+    };
+    auto stash = [&](int sl, int buf) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            f32x4 v = ra[sl][i];
+            const bool in = ((inm[sl] >> i) & 1u) != 0u;
+            if (MODE == C3_UPADD) v += ra2[sl][i];                        // both are zero outside the map
+            if (MODE == C3_ROWSCALE) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = in ? rsc[sl][i] * v[e] : 0.f;
+            }
+            if (MODE == C3_GN) {                                          // the expression of k_gn_apply; the padding stays 0
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = in ? fmaxf((v[e] - gmean) * grstd * rgam[sl][e] + rbet[sl][e], 0.f) : 0.f;
+            }
+            *reinterpret_cast<f32x4*>(&lds[buf][(lr + 64 * i) * LS + lc4]) = v;
+        }
+        *reinterpret_cast<f32x4*>(&lds[buf][(BM + lr) * LS + lc4]) = rb[sl];
+    };
+    f32x4 acc[MT][NT];
+#pragma unroll
+    for (int a = 0; a < MT; ++a)
+#pragma unroll
+        for (int b = 0; b < NT; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int qoff = ((lane >> 4) & 1) * 2 + (lane >> 5);                 // conflict-free fragment maps of gemm_tile
+    const int aso = (wm * 32 + gemm_prow(lane & 15)) * LS + qoff * 4, bso = (BM + wn * 32 + gemm_prow(lane & 15)) * LS + qoff * 4;
+#pragma unroll
+    for (int sl = 0; sl < PD; ++sl) fetch(sl, sl);
+    if (MODE == C3_GN) { gmean = g.gn_mr[2 * z]; grstd = g.gn_mr[2 * z + 1]; }
+    stash(0, 0);
+    __syncthreads();
+    for (int t0 = 0; t0 < nst; t0 += PD) {
+#pragma unroll
+        for (int u = 0; u < PD; ++u) {
+            const int s = t0 + u, buf = u & 1;
+            fetch(s + PD, u);                                             // slot u (stage s) already sits in lds[buf]
+            if (s < nst) {                                                // workgroup-uniform
+                const float* as = &lds[buf][aso];
+                const float* bs = &lds[buf][bso];
+                f32x4 fa[BK / 16][MT], fb[BK / 16][NT];
+#pragma unroll
+                for (int hh = 0; hh < BK / 16; ++hh) {
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt) fa[hh][mt] = *reinterpret_cast<const f32x4*>(as + mt * 16 * LS + hh * 16);
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) fb[hh][nt] = *reinterpret_cast<const f32x4*>(bs + nt * 16 * LS + hh * 16);
+                }
+#pragma unroll
+                for (int hh = 0; hh < BK / 16; ++hh)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+#pragma unroll
+                        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                            for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = mfma16(fa[hh][mt][j], fb[hh][nt][j], acc[mt][nt]);
+            }
+            stash((u + 1) % PD, buf ^ 1);                                 // stage s + 1 (past the end: never read)
+            __syncthreads();
+        }
+    }
+    // epilogue: bias, tile statistics of what GroupNorm(1, N) sees, stores (rows past the image's last pixel are dropped)
+    const __amdgpu_buffer_rsrc_t rsC = pt_rsrc(g.C, 0xFFFFFFE0u);
+    float s = 0.f, q = 0.f;
+    unsigned rbase[MT][4];
+    bool rok[MT][4];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int p = m0 + wm * 32 + mt * 16 + gemm_prow(4 * (lane >> 4) + r);
+            rok[mt][r] = p < g.HW;
+            const long o = g.nchw ? (long)z * g.N * g.HW + p : ((long)z * g.HW + p) * g.N;
+            rbase[mt][r] = rok[mt][r] ? (unsigned)(o * 4) : OOB;
+        }
+    const unsigned cstep = (unsigned)(g.nchw ? g.HW : 1) * 4u;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const int col = n0 + wn * 32 + nt * 16 + gemm_prow(lane & 15);
+        const bool cok = col < g.N;
+        const float bv = g.bias ? g.bias[cok ? col : 0] : 0.f;
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float v = acc[mt][nt][r] + bv;
+                const bool ok = cok && rok[mt][r];
+                s += ok ? v : 0.f;
+                q += ok ? v * v : 0.f;
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsC, ok ? rbase[mt][r] + (unsigned)col * cstep : OOB, 0, 0);
+            }
+    }
+    if (g.stats) {                                                        // uniform; fixed order: lanes (xor tree), then wavefronts 0..7
+        double sd = (double)s, qd = (double)q;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { sd += __shfl_xor(sd, off, 64); qd += __shfl_xor(qd, off, 64); }
+        if (lane == 0) { red[2 * wave] = sd; red[2 * wave + 1] = qd; }
+        __syncthreads();
+        if (tid == 0) {
+            double ts = 0.0, tq = 0.0;
+            for (int w = 0; w < 8; ++w) { ts += red[2 * w]; tq += red[2 * w + 1]; }
+            float* dst = g.stats + (((long)z * gridDim.x + blockIdx.x) * gridDim.y + blockIdx.y) * 2;
+            dst[0] = (float)ts;
+            dst[1] = (float)tq;
+        }
+    }
+}
+
+// (mean, rstd) of every image from its tile slots, summed in slot order in double (the arithmetic of k_gn_apply); one workgroup per image
+__global__ __launch_bounds__(64) void k_conv3_gn_finish(const float* __restrict__ stats, int nslots, float* __restrict__ mr, int count) {
+    __shared__ double ps[64], pq[64];
+    const int z = blockIdx.x, t = threadIdx.x;
+    const int per = (nslots + 63) / 64, k0 = t * per, k1 = min(nslots, k0 + per);     // thread t: a contiguous run of slots
+    double s = 0.0, q = 0.0;
+    for (int k = k0; k < k1; ++k) {
+        s += (double)stats[((long)z * nslots + k) * 2];
+        q += (double)stats[((long)z * nslots + k) * 2 + 1];
+    }
+    ps[t] = s; pq[t] = q;
+    __syncthreads();
+    if (t == 0) {
+        double ts = 0.0, tq = 0.0;
+        for (int w = 0; w < 64; ++w) { ts += ps[w]; tq += pq[w]; }
+        const double mean_d = ts / count;
+        mr[2 * z] = (float)mean_d;
+        mr[2 * z + 1] = (float)(1.0 / sqrt(fmax(tq / count - mean_d * mean_d, 0.0) + 1e-5));
+    }
+}
+
+// ltrb[z][n][p] = exp(bias[n] + sum_{tap, c} w[n][tap][c] relu(GroupNorm(x))[z][p + tap][c]) (heads.py:135): one wavefront per run of 8
+// pixels of a map row, lane l owns channels 4 l + 256 i; the 10 input pixels of a row of taps are normalised once and serve all three
+// horizontal taps; the 32 dot products are reduced across the wavefront in fixed order (wave_sum).  Halo pixels contribute 0.
+__global__ __launch_bounds__(256) void k_reg_out(const float* __restrict__ X, const float* __restrict__ gn_mr, const float* __restrict__ gam,
+                                                 const float* __restrict__ bet, const float* __restrict__ Wt, const float* __restrict__ bias,
+                                                 float* __restrict__ out, int H, int W, int D, int nimg) {
+    const int lane = threadIdx.x & 63, wv = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int runs = (W + 7) / 8;
+    if (wv >= nimg * H * runs) return;                                    // whole wavefronts leave; no barrier below
+    const int z = wv / (H * runs), rem = wv - z * H * runs, y = rem / runs, x0 = (rem - y * runs) * 8;
+    const float mean = gn_mr[2 * z], rstd = gn_mr[2 * z + 1];
+    const long HW = (long)H * W;
+    float acc[8][4];
+#pragma unroll
+    for (int a = 0; a < 8; ++a)
+#pragma unroll
+        for (int n = 0; n < 4; ++n) acc[a][n] = 0.f;
+    for (int c = lane * 4; c < D; c += 256) {
+        const f32x4 g4 = *reinterpret_cast<const f32x4*>(gam + c), b4 = *reinterpret_cast<const f32x4*>(bet + c);
+        for (int dy = 0; dy < 3; ++dy) {
+            const int yy = y + dy - 1;
+            if (yy < 0 || yy >= H) continue;                              // uniform
+            f32x4 xv[10];
+#pragma unroll
+            for (int j = 0; j < 10; ++j) {
+                const int xx = x0 - 1 + j;
+                const bool in = xx >= 0 && xx < W;
+                const f32x4 v = *reinterpret_cast<const f32x4*>(X + ((long)z * HW + (long)yy * W + min(max(xx, 0), W - 1)) * D + c);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) xv[j][e] = in ? fmaxf((v[e] - mean) * rstd * g4[e] + b4[e], 0.f) : 0.f;
+            }
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx) {
+                f32x4 w[4];
+#pragma unroll
+                for (int n = 0; n < 4; ++n) w[n] = *reinterpret_cast<const f32x4*>(Wt + ((long)n * 9 + dy * 3 + dx) * D + c);
+#pragma unroll
+                for (int a = 0; a < 8; ++a)
+#pragma unroll
+                    for (int n = 0; n < 4; ++n) {
+                        const f32x4 v = xv[a + dx];
+                        acc[a][n] += (v[0] * w[n][0] + v[1] * w[n][1]) + (v[2] * w[n][2] + v[3] * w[n][3]);
+                    }
+            }
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 8; ++a)
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            const float t = wave_sum(acc[a][n]);
+            if (lane == a * 4 + n && x0 + a < W) out[((long)z * 4 + n) * HW + (long)y * W + x0 + a] = expf(t + bias[n]);
+        }
+}
+
+int conv3_route(int mode) {
+    return mode == C3_PLAIN ? PT_HEADS_R_CONV3_PLAIN : mode == C3_ROWSCALE ? PT_HEADS_R_CONV3_ROWSCALE : mode == C3_GN ? PT_HEADS_R_CONV3_GN
+                                                                                                                    : PT_HEADS_R_CONV3_UPADD;
+}
+
+// Cin, N multiples of 64 up to 512; every operand and the output inside the 32-bit byte offsets of the raw buffer accesses; the grid's z
+bool conv3_ok(long nimg, long nsrc, int Cin, int N, int H, int W) {
+    if (nimg <= 0 || nsrc <= 0 || H <= 0 || W <= 0 || Cin <= 0 || N <= 0) return false;
+    if (Cin % 64 != 0 || N % 64 != 0 || Cin > 512 || N > 512 || nimg > 65535 || nsrc > 65535) return false;
+    const unsigned long lim = 0xFFFFFFE0ul / 4 / (unsigned long)std::max(Cin, N);     // pixels whose channel rows stay addressable
+    if ((unsigned long)H > lim || (unsigned long)W > lim || (unsigned long)H * W > lim) return false;
+    return (unsigned long)nimg * H * W <= lim && (unsigned long)nsrc * H * W <= lim;
+}
+
+int launch_conv3(int mode, const Conv3Args& g, int nimg, hipStream_t st, PtRouteLog* log) {
+    if (!conv3_ok(nimg, (nimg + g.a_div - 1) / g.a_div, g.Cin, g.N, g.H, g.W)) return PT_ERR_UNSUPPORTED;
+    if (log) {
+        pt_route_note(log, conv3_route(mode));
+        return PT_OK;
+    }
+    const dim3 grid((g.HW + C3_BM - 1) / C3_BM, g.N / C3_BN, nimg), block(512);
+    if (mode == C3_PLAIN) hipLaunchKernelGGL((k_conv3<C3_PLAIN>), grid, block, 0, st, g);
+    else if (mode == C3_ROWSCALE) hipLaunchKernelGGL((k_conv3<C3_ROWSCALE>), grid, block, 0, st, g);
+    else if (mode == C3_GN) hipLaunchKernelGGL((k_conv3<C3_GN>), grid, block, 0, st, g);
+    else hipLaunchKernelGGL((k_conv3<C3_UPADD>), grid, block, 0, st, g);
+    PT_CHECK_LAUNCH();
+    return PT_OK;
+}
+
+Conv3Args conv3_args(const float* A, long src_imgs, int a_div, const float* Wt, const float* bias, float* C, int nchw, int H, int W, int Cin,
+                     int N) {
+    Conv3Args g{};
+    g.A = A; g.a_bytes = (unsigned)(src_imgs * H * W * Cin * 4); g.a_div = a_div;
+    g.Wt = Wt; g.w_bytes = (unsigned)((long)N * 9 * Cin * 4); g.bias = bias;
+    g.C = C; g.nchw = nchw; g.H = H; g.W = W; g.HW = H * W; g.Cin = Cin; g.N = N;
+    return g;
+}
+
+struct TamosRegCarve { size_t X, fproj, att, T0, T1, stats, mr, total; int nslots; };
+TamosRegCarve tamos_reg_carve(int n_img, int T, int D, int H, int W) {
+    TamosRegCarve c{};
+    const size_t HW = (size_t)H * W, Mz = (size_t)n_img * T * HW;
+    size_t o = 0;
+    auto take = [&](size_t k) { size_t r = o; o += pt_align_floats(k); return r; };
+    c.nslots = (int)((HW + C3_BM - 1) / C3_BM) * (D / C3_BN);
+    c.X = take((size_t)n_img * HW * D); c.fproj = take((size_t)n_img * T * D); c.att = take((size_t)n_img * HW * T);
+    c.T0 = take(Mz * D); c.T1 = take(Mz * D);
+    c.stats = take((size_t)2 * n_img * T * c.nslots); c.mr = take((size_t)2 * n_img * T);
+    c.total = o;
+    return c;
+}
+
+int tamos_reg_check(int n_img, int T, int D, int H, int W) {
+    if (n_img <= 0 || T <= 0 || D <= 0 || H <= 0 || W <= 0) return PT_ERR_SHAPE;
+    if (T > 16 || !conv3_ok((long)n_img * T, n_img, D, D, H, W)) return PT_ERR_UNSUPPORTED;
+    return PT_OK;
+}
+
+int tamos_bbreg_impl(const float* params, const float* feat, const float* filters, float* ltrb, int n_img, int T, int D, int H, int W,
+                     void* ws, size_t ws_bytes, void* stream, PtRouteLog* log) {
+    if (!params || !feat || !filters || !ltrb || !ws) return PT_ERR_NULL;
+    int rc = tamos_reg_check(n_img, T, D, H, W);
+    if (rc) return rc;
+    const TamosRegCarve cv = tamos_reg_carve(n_img, T, D, H, W);
+    if (ws_bytes < cv.total * sizeof(float) || ((uintptr_t)ws % 256) != 0) return PT_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const RegOff ro = reg_layout(D);
+    const int HW = H * W, nz = n_img * T;
+    float* base = (float*)ws;
+    float *X = base + cv.X, *fproj = base + cv.fproj, *att = base + cv.att, *stats = base + cv.stats, *mr = base + cv.mr;
+    PT_TOMP_LAUNCH(PT_HEADS_R_NCHW_TOKENS, k_nchw_to_tokens, dim3((HW + 31) / 32, (D + 31) / 32, n_img), dim3(256), 0, st, feat, X, D, HW);
+    // the T filters of every image through `linear` (heads.py:123), then the T attention maps of an image as one HW x D by D x T product
+    GemmArgs gp = gemm_args(filters, D, nz, params + ro.lw, nz, D, D, params + ro.lb, fproj, D);
+    if ((rc = launch_gemm(gp, st, false, log))) return rc;
+    for (int i = 0; i < n_img; ++i) {
+        GemmArgs ga = gemm_args(X + (size_t)i * HW * D, D, HW, fproj + (size_t)i * T * D, HW, T, D, nullptr, att + (size_t)i * HW * T, T);
+        if ((rc = launch_gemm(ga, st, false, log))) return rc;
+    }
+    // tower: layer 0 reads attention (.) feature through the per-row scalar, layers 1..3 the previous layer's raw output through its
+    // GroupNorm + ReLU; every layer leaves its tile statistics, k_conv3_gn_finish turns them into (mean, rstd) per image
+    float *src = base + cv.T0, *dst = base + cv.T1;
+    for (int i = 0; i < 4; ++i) {
+        Conv3Args g = i == 0 ? conv3_args(X, n_img, T, params + ro.cw[0], params + ro.cb[0], src, 0, H, W, D, D)
+                             : conv3_args(src, nz, 1, params + ro.cw[i], params + ro.cb[i], dst, 0, H, W, D, D);
+        g.stats = stats;
+        if (i == 0) {
+            g.rowscale = att; g.rs_bytes = (unsigned)((size_t)n_img * HW * T * 4);
+        } else {
+            g.gn_mr = mr; g.gn_gam = params + ro.gg[i - 1]; g.gn_bet = params + ro.gb[i - 1];
+        }
+        if ((rc = launch_conv3(i == 0 ? C3_ROWSCALE : C3_GN, g, nz, st, log))) return rc;
+        PT_TOMP_LAUNCH(PT_HEADS_R_CONV3_GN_FINISH, k_conv3_gn_finish, dim3(nz), dim3(64), 0, st, stats, cv.nslots, mr, HW * D);
+        if (i > 0) std::swap(src, dst);
+    }
+    const int waves = nz * H * ((W + 7) / 8);
+    PT_TOMP_LAUNCH(PT_HEADS_R_REG_OUT, k_reg_out, dim3((waves + 3) / 4), dim3(256), 0, st, src, mr, params + ro.gg[3], params + ro.gb[3],
+                   params + ro.fw, params + ro.fb, ltrb, H, W, D, nz);
+    return PT_OK;
+}
+
+// ---- heads.FPN with two levels (heads.py:144-162 around torchvision's FeaturePyramidNetwork) ----------------------------------------
+// pack: inner_blocks.0 weight (D, C_hi), bias (D); inner_blocks.1 weight (D, C_lo), bias (D); layer_blocks.0 weight (D, 9, D) tap-major,
+// bias (D); layer_blocks.1 weight (D, 9, D) tap-major, bias (D)
+struct FpnOff { size_t iw0, ib0, iw1, ib1, lw0, lb0, lw1, lb1, total; };
+FpnOff fpn_layout(int C_hi, int C_lo, int D) {
+    FpnOff o{};
+    size_t c = 0;
+    auto take = [&](size_t n) { size_t r = c; c += n; return r; };
+    o.iw0 = take((size_t)D * C_hi); o.ib0 = take(D); o.iw1 = take((size_t)D * C_lo); o.ib1 = take(D);
+    o.lw0 = take((size_t)D * 9 * D); o.lb0 = take(D); o.lw1 = take((size_t)D * 9 * D); o.lb1 = take(D);
+    o.total = c;
+    return o;
+}
+
+struct FpnCarve { size_t X2, X3, L2, L3, total; };
+FpnCarve fpn_carve(int n, int C_hi, int C_lo, int D, int H2, int W2, int H3, int W3) {
+    FpnCarve c{};
+    size_t o = 0;
+    auto take = [&](size_t k) { size_t r = o; o += pt_align_floats(k); return r; };
+    const size_t M2 = (size_t)n * H2 * W2, M3 = (size_t)n * H3 * W3;
+    c.X2 = take(M2 * C_hi); c.X3 = take(M3 * C_lo); c.L2 = take(M2 * D); c.L3 = take(M3 * D);
+    c.total = o;
+    return c;
+}
+
+int fpn_check(int n, int C_hi, int C_lo, int D, int H2, int W2, int H3, int W3) {
+    if (n <= 0 || C_hi <= 0 || C_lo <= 0 || D <= 0 || H2 <= 0 || W2 <= 0 || H3 <= 0 || W3 <= 0) return PT_ERR_SHAPE;
+    if (C_hi % 64 != 0 || C_lo % 64 != 0 || C_hi > 2048 || C_lo > 2048) return PT_ERR_UNSUPPORTED;
+    if (!conv3_ok(n, n, D, D, H2, W2) || !conv3_ok(n, n, D, D, H3, W3)) return PT_ERR_UNSUPPORTED;
+    if ((size_t)n * H2 * W2 * C_hi * 4 >= 0xFFFFFFE0ull || (size_t)n * H3 * W3 * C_lo * 4 >= 0xFFFFFFE0ull) return PT_ERR_UNSUPPORTED;
+    return PT_OK;
+}
+
+int fpn2_impl(const float* params, const float* feat_hi, const float* feat_lo, float* feat2, float* feat3, int n, int C_hi, int C_lo, int D,
+              int H2, int W2, int H3, int W3, int want_feat3, void* ws, size_t ws_bytes, void* stream, PtRouteLog* log) {
+    if (!params || !feat_hi || !feat_lo || !feat2 || !ws || (want_feat3 && !feat3)) return PT_ERR_NULL;
+    int rc = fpn_check(n, C_hi, C_lo, D, H2, W2, H3, W3);
+    if (rc) return rc;
+    const FpnCarve cv = fpn_carve(n, C_hi, C_lo, D, H2, W2, H3, W3);
+    if (ws_bytes < cv.total * sizeof(float) || ((uintptr_t)ws % 256) != 0) return PT_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const FpnOff fo = fpn_layout(C_hi, C_lo, D);
+    float* base = (float*)ws;
+    const int HW2 = H2 * W2, HW3 = H3 * W3, M2 = n * HW2, M3 = n * HW3;
+    PT_TOMP_LAUNCH(PT_HEADS_R_NCHW_TOKENS, k_nchw_to_tokens, dim3((HW2 + 31) / 32, (C_hi + 31) / 32, n), dim3(256), 0, st, feat_hi, base + cv.X2,
+                   C_hi, HW2);
+    PT_TOMP_LAUNCH(PT_HEADS_R_NCHW_TOKENS, k_nchw_to_tokens, dim3((HW3 + 31) / 32, (C_lo + 31) / 32, n), dim3(256), 0, st, feat_lo, base + cv.X3,
+                   C_lo, HW3);
+    // the 1x1 lateral convolutions are plain products over the tokens
+    GemmArgs g2 = gemm_args(base + cv.X2, C_hi, M2, params + fo.iw0, M2, D, C_hi, params + fo.ib0, base + cv.L2, D);
+    if ((rc = launch_gemm(g2, st, false, log))) return rc;
+    GemmArgs g3 = gemm_args(base + cv.X3, C_lo, M3, params + fo.iw1, M3, D, C_lo, params + fo.ib1, base + cv.L3, D);
+    if ((rc = launch_gemm(g3, st, false, log))) return rc;
+    // top-down: the high map's 3x3 loader adds the nearest low lateral to the high lateral on the way into LDS (no pass of its own)
+    Conv3Args c2 = conv3_args(base + cv.L2, n, 1, params + fo.lw0, params + fo.lb0, feat2, 1, H2, W2, D, D);
+    c2.A2 = base + cv.L3; c2.a2_bytes = (unsigned)((long)M3 * D * 4); c2.H3 = H3; c2.W3 = W3;
+    c2.sy = (float)H3 / (float)H2; c2.sx = (float)W3 / (float)W2;
+    if ((rc = launch_conv3(C3_UPADD, c2, n, st, log))) return rc;
+    if (want_feat3) {
+        Conv3Args c3 = conv3_args(base + cv.L3, n, 1, params + fo.lw1, params + fo.lb1, feat3, 1, H3, W3, D, D);
+        if ((rc = launch_conv3(C3_PLAIN, c3, n, st, log))) return rc;
+    }
+    return PT_OK;
+}
+
+}  // namespace
+
+extern "C" size_t pt_tamos_bbreg_ws_bytes(int n_img, int T, int d_model, int H, int W) {
+    if (tamos_reg_check(n_img, T, d_model, H, W)) return 0;
+    return tamos_reg_carve(n_img, T, d_model, H, W).total * sizeof(float);
+}
+
+extern "C" int pt_tamos_bbreg_f32(const float* params, const float* feat, const float* filters, float* ltrb, int n_img, int T, int d_model,
+                                  int H, int W, void* ws, size_t ws_bytes, void* stream) {
+    return tamos_bbreg_impl(params, feat, filters, ltrb, n_img, T, d_model, H, W, ws, ws_bytes, stream, nullptr);
+}
+
+extern "C" int pt_tamos_bbreg_routes(int n_img, int T, int d_model, int H, int W, int* routes, int cap, int* n_routes) {
+    if (!routes || !n_routes) return PT_ERR_NULL;
+    if (cap < 0) return PT_ERR_SHAPE;
+    PtRouteLog log{routes, cap, 0};
+    const int rc = tamos_bbreg_impl(route_fake(0), route_fake(1), route_fake(2), route_fake(3), n_img, T, d_model, H, W, route_fake(4),
+                                    ~(size_t)0, nullptr, &log);
+    return route_finish(rc, log, routes, cap, n_routes);
+}
+
+extern "C" size_t pt_fpn2_param_floats(int C_hi, int C_lo, int d_out) {
+    if (C_hi <= 0 || C_lo <= 0 || d_out <= 0 || C_hi % 64 != 0 || C_lo % 64 != 0 || d_out % 64 != 0 || d_out > 512) return 0;
+    return fpn_layout(C_hi, C_lo, d_out).total;
+}
+
+extern "C" size_t pt_fpn2_ws_bytes(int n, int C_hi, int C_lo, int d_out, int H2, int W2, int H3, int W3) {
+    if (fpn_check(n, C_hi, C_lo, d_out, H2, W2, H3, W3)) return 0;
+    return fpn_carve(n, C_hi, C_lo, d_out, H2, W2, H3, W3).total * sizeof(float);
+}
+
+extern "C" int pt_fpn2_f32(const float* params, const float* feat_hi, const float* feat_lo, float* feat2, float* feat3, int n, int C_hi,
+                           int C_lo, int d_out, int H2, int W2, int H3, int W3, int want_feat3, void* ws, size_t ws_bytes, void* stream) {
+    return fpn2_impl(params, feat_hi, feat_lo, feat2, feat3, n, C_hi, C_lo, d_out, H2, W2, H3, W3, want_feat3, ws, ws_bytes, stream, nullptr);
+}
+
+extern "C" int pt_fpn2_routes(int n, int C_hi, int C_lo, int d_out, int H2, int W2, int H3, int W3, int want_feat3, int* routes, int cap,
+                              int* n_routes) {
+    if (!routes || !n_routes) return PT_ERR_NULL;
+    if (cap < 0) return PT_ERR_SHAPE;
+    PtRouteLog log{routes, cap, 0};
+    const int rc = fpn2_impl(route_fake(0), route_fake(1), route_fake(2), route_fake(3), route_fake(4), n, C_hi, C_lo, d_out, H2, W2, H3, W3,
+                             want_feat3, route_fake(5), ~(size_t)0, nullptr, &log);
+    return route_finish(rc, log, routes, cap, n_routes);
+}

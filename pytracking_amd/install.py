@@ -67,6 +67,9 @@ What gets rebound (import path = contract; nothing in the reference tree is edit
   ltr.models.transformer.filter_predictor.GOTFilterPredictor
                                              (TaMOs multi-object filter predictor, inference; only with install(tamos=True))
                                                                                       -> pytracking_amd.tamos
+  ltr.models.transformer.heads.FPN, ltr.models.transformer.heads.DenseBoxRegressor
+                                             (TaMOs two-level FPN and multi-object box regressor; only with install(tamos=True))
+                                                                                      -> pytracking_amd.tamos
 
 Dispatch rule of the rebound *functions*: device fp32 tensors of a shape the gfx950 kernels cover go to the C ABI;
 everything else (CPU tensors, dilations, grouped filters, K*K > 16, more than 16 filters) is outside the hot path and
@@ -189,6 +192,7 @@ def _choosing_class(ref, covered, ours, message=None, doc=None):
             return ref.__new__(cls)
 
     Choosing.__name__ = Choosing.__qualname__ = ref.__name__
+    Choosing._pt_reference = ref
     return Choosing
 
 
@@ -332,7 +336,7 @@ def _install_tomp():
 
 
 def _install_tamos():
-    """TaMOs multi-object filter predictor (inference): `tamosnet_resnet50` / `tamosnet_swin_base` (ltr/models/tracking/tamosnet.py) reach
+    """TaMOs multi-object filter predictor, FPN and box regressor (inference): `tamosnet_resnet50` / `tamosnet_swin_base` (ltr/models/tracking/tamosnet.py) reach
     `GOTFilterPredictor` through the module attribute.  The gfx950 class is chosen for the gfx950 transformer container with
     label_enc 'gaussian', box_enc 'ltrb_token' and 1 <= num_tokens <= 16; anything else builds the reference class."""
     from . import tamos as _ta
@@ -344,6 +348,23 @@ def _install_tamos():
         pmod.GOTFilterPredictor, _ta.covered, _ta.GOTFilterPredictor,
         "GOTFilterPredictor: configuration outside the gfx950 hot path",
         doc="Covered configuration -> gfx950 multi-object predictor; anything else -> the reference class."))
+    # the heads behind the predictor (tamos.py:308-317): heads.FPN and the DenseBoxRegressor that also takes T filters per sequence
+    try:
+        hmod = importlib.import_module("ltr.models.transformer.heads")
+    except Exception:                   # torchvision (heads.py:3) missing: leave the heads alone
+        return
+    ref_reg = hmod.DenseBoxRegressor
+    while "_pt_reference" in vars(ref_reg):                 # the default install()'s choosing class stands there already
+        ref_reg = ref_reg._pt_reference
+    _rebind(hmod, "DenseBoxRegressor", _choosing_class(
+        ref_reg, _ta.regressor_covered, _ta.DenseBoxRegressor, "DenseBoxRegressor: channel count outside the gfx950 hot path"))
+
+    def fpn_covered(high_res_layer="layer2", output_dim=256, input_dims=(512, 256)):
+        dims = tuple(input_dims)
+        return (len(dims) == 2 and all(isinstance(c, int) and c % 64 == 0 and 0 < c <= 2048 for c in dims)
+                and isinstance(output_dim, int) and output_dim % 64 == 0 and 0 < output_dim <= 512)
+
+    _rebind(hmod, "FPN", _choosing_class(hmod.FPN, fpn_covered, _ta.FPN, "FPN: configuration outside the gfx950 hot path"))
 
 
 def _install_clf_head(feature_heads=False):

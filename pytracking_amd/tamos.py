@@ -16,16 +16,26 @@ The mirror never writes to its inputs.  The reference does: its `train_feat_seq 
 the caller's `train_feat` when there is one memory frame (the permute + flatten is then a view).  The tracker never reads that tensor
 again (tamos.py:296-306), so nothing depends on it.
 
-The classifier's scores come from `pytracking_amd.transformer.LinearFilterClassifier` with T filters per sequence.  Not here: `heads.FPN`,
-the multi-object `DenseBoxRegressor` on the FPN map, `TaMOs.track` end to end, training.
+The classifier's scores come from `pytracking_amd.transformer.LinearFilterClassifier` with T filters per sequence.
+
+What `pytracking/tracker/tamos/tamos.py:308-317` runs behind the predictor is here as well (`ltr/models/transformer/heads.py`):
+
+    FPN(high_res_layer='layer2', output_dim=256, input_dims=(512, 256)).forward(test_feat_enc, test_feat_backbone)   heads.py:144-162
+    DenseBoxRegressor(num_channels, project_filter).forward(feat, filter) with T filters per sequence               heads.py:119-141
+
+both on the direct 3x3 token convolution of `pytracking_amd/csrc/tomp.hip` (pt_fpn2_f32, pt_tamos_bbreg_f32).  Not here: training; the
+`box_enc` / `label_enc` variants refused above; `TaMOs.track`'s own host glue, which runs unchanged -- including `classify_target`
+computing a classification FPN map it never reads when `cls_feature_type == 'trafo'`.
 """
 import ctypes
+from collections import OrderedDict
 
 import torch
 import torch.nn as nn
 
 from . import _lib
 from .filter import _ptr, _require_device, _stream, device_guarded, workspace
+from . import transformer as _tm
 from .transformer import MLP, Transformer, _inference_only, _Pack
 
 MAX_TOKENS = 16
@@ -169,3 +179,138 @@ class GOTFilterPredictor(nn.Module):
         filters, enc = self._run(train_feat, test_feat, train_label, train_ltrb_target, True, num_gth_frames)
         T, D = filters.shape[1:]
         return (filters[0].reshape(1, T, D, 1, 1), filters[1].reshape(1, T, D, 1, 1), enc[0][None, None], enc[1][None, None])
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# heads.py: FPN and the multi-object box regressor
+# ------------------------------------------------------------------------------------------------------------------
+def _device_only(who, *tensors):
+    if not all(t.is_cuda for t in tensors):
+        raise NotImplementedError(f"{who}: the gfx950 path takes device tensors only (there is no stock-PyTorch fallback)")
+
+
+class _PyramidParams(nn.Module):
+    """Parameter holder with the state_dict keys of torchvision's `FeaturePyramidNetwork(in_channels_list, out_channels)`:
+    `inner_blocks.{i}.0.{weight,bias}` (1x1) and `layer_blocks.{i}.0.{weight,bias}` (3x3, padding 1) -- its blocks are
+    `Conv2dNormActivation` with neither norm nor activation, i.e. a Sequential around one Conv2d.  Checkpoints written before that
+    wrapper existed carry `inner_blocks.{i}.{weight,bias}`; they are renamed on load, as torchvision itself upgrades them."""
+
+    def __init__(self, in_channels_list, out_channels):
+        super().__init__()
+        self.inner_blocks = nn.ModuleList(nn.Sequential(nn.Conv2d(c, out_channels, 1)) for c in in_channels_list)
+        self.layer_blocks = nn.ModuleList(nn.Sequential(nn.Conv2d(out_channels, out_channels, 3, padding=1)) for _ in in_channels_list)
+        for m in self.modules():                            # torchvision's initialisation
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_uniform_(m.weight, a=1)
+                nn.init.constant_(m.bias, 0)
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        for block in ("inner_blocks", "layer_blocks"):
+            for i in range(len(self.inner_blocks)):
+                for t in ("weight", "bias"):
+                    old, new = f"{prefix}{block}.{i}.{t}", f"{prefix}{block}.{i}.0.{t}"
+                    if old in state_dict and new not in state_dict:
+                        state_dict[new] = state_dict.pop(old)
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+
+
+class FPN(nn.Module):
+    """`heads.FPN` (heads.py:144-162) without torchvision.  torchvision is not installed where this project is built, so both the
+    parameter names (`fpn.inner_blocks.{0,1}.0.*`, `fpn.layer_blocks.{0,1}.0.*`, and the older `fpn.inner_blocks.{i}.*` layout) and the
+    top-down arithmetic are written from torchvision's documented behaviour, not compared with a run of it:
+
+        lat3 = inner_blocks[1](feat3);  out3 = layer_blocks[1](lat3)
+        lat2 = inner_blocks[0](feat2) + F.interpolate(lat3, size=feat2.shape[-2:], mode="nearest");  out2 = layer_blocks[0](lat2)
+
+    Two levels, inference, device tensors; anything else raises NotImplementedError before a launch.  `compute_feat3 = False` skips the
+    low-resolution output map, which the tracker never reads (the reference always computes it)."""
+
+    def __init__(self, high_res_layer="layer2", output_dim=256, input_dims=(512, 256)):
+        super().__init__()
+        if len(tuple(input_dims)) != 2:
+            raise NotImplementedError("FPN: the gfx950 path covers the two-level pyramid of heads.FPN")
+        self.high_res_layer = high_res_layer
+        self.output_dim = int(output_dim)
+        self.input_dims = tuple(int(c) for c in input_dims)
+        if _lib.lib().pt_fpn2_param_floats(self.input_dims[0], self.input_dims[1], self.output_dim) == 0:
+            raise NotImplementedError("FPN: channel counts outside the gfx950 kernels (multiples of 64, output_dim <= 512)")
+        self.fpn = _PyramidParams(self.input_dims, self.output_dim)
+        self.compute_feat3 = True
+        self._pack = _Pack()
+
+    def _params(self):
+        f = self.fpn
+        return self._pack.get([f.inner_blocks[0][0].weight, f.inner_blocks[0][0].bias, f.inner_blocks[1][0].weight, f.inner_blocks[1][0].bias,
+                               f.layer_blocks[0][0].weight.permute(0, 2, 3, 1), f.layer_blocks[0][0].bias,
+                               f.layer_blocks[1][0].weight.permute(0, 2, 3, 1), f.layer_blocks[1][0].bias])
+
+    @device_guarded
+    def forward(self, test_feat_enc, test_feat_backbone):
+        _inference_only(self)
+        num_sequences = test_feat_enc.shape[1]
+        lo = test_feat_enc.reshape(-1, *test_feat_enc.shape[-3:])
+        hi = test_feat_backbone[self.high_res_layer]
+        if hi.dim() == 5:
+            hi = hi.reshape(-1, *hi.shape[-3:])
+        _device_only("FPN", lo, hi)
+        _require_device(lo, hi)
+        n, c_lo, h3, w3 = lo.shape
+        if hi.dim() != 4 or hi.shape[0] != n or (hi.shape[1], c_lo) != self.input_dims:
+            raise ValueError("FPN: maps do not match input_dims / each other's batch")
+        c_hi, h2, w2 = hi.shape[1:]
+        D = self.output_dim
+        L = _lib.lib()
+        nb = L.pt_fpn2_ws_bytes(n, c_hi, c_lo, D, h2, w2, h3, w3)
+        if nb == 0:
+            raise NotImplementedError("FPN: configuration not covered by the gfx950 kernels")
+        lo, hi = lo.contiguous(), hi.contiguous()
+        dev = lo.device
+        ws = workspace(nb, dev)
+        feat2 = torch.empty(n, D, h2, w2, dtype=torch.float32, device=dev)
+        feat3 = torch.empty(n, D, h3, w3, dtype=torch.float32, device=dev) if self.compute_feat3 else None
+        rc = L.pt_fpn2_f32(_ptr(self._params()), _ptr(hi), _ptr(lo), _ptr(feat2), _ptr(feat3) if feat3 is not None else None, n, c_hi,
+                           c_lo, D, h2, w2, h3, w3, int(feat3 is not None), _ptr(ws), ws.numel(), _stream())
+        _lib.check(rc, "pt_fpn2_f32")
+        out = OrderedDict()
+        out["feat2"] = feat2.reshape(-1, num_sequences, D, h2, w2)
+        if feat3 is not None:
+            out["feat3"] = feat3.reshape(-1, num_sequences, D, h3, w3)
+        return out
+
+
+def regressor_covered(num_channels, project_filter=True, *args, **kw):
+    """The constructor arguments the gfx950 regressor takes (what `install(tamos=True)` asks before it chooses the class below)."""
+    return isinstance(num_channels, int) and num_channels % 64 == 0 and 0 < num_channels <= 512
+
+
+class DenseBoxRegressor(_tm.DenseBoxRegressor):
+    """`heads.DenseBoxRegressor` with one filter per sequence (the parent's path, unchanged) or T filters per sequence
+    (heads.py:127-141): feat (nf, ns, C, h, w), filter (ns, T, C, 1, 1) -> ltrb (1, nf*ns, T, 4, h, w).  Same state_dict keys as the
+    parent and the reference."""
+
+    @device_guarded
+    def forward(self, feat, filter):
+        nf, ns, c, h, w = feat.shape
+        if filter.numel() == ns * c and filter.dim() != 5:
+            return super().forward(feat, filter)
+        _inference_only(self)
+        _device_only("DenseBoxRegressor", feat, filter)
+        _require_device(feat, filter)
+        if filter.dim() != 5 or filter.shape[0] != ns or filter.shape[2] != c or filter.shape[-1] * filter.shape[-2] != 1:
+            raise ValueError("DenseBoxRegressor: filter (n_seq, T, C, 1, 1) expected")
+        T = filter.shape[1]
+        if not 1 <= T <= MAX_TOKENS:
+            raise NotImplementedError(f"DenseBoxRegressor: 1 <= T <= {MAX_TOKENS} filters per sequence on the gfx950 path")
+        L = _lib.lib()
+        n_img = nf * ns
+        nb = L.pt_tamos_bbreg_ws_bytes(n_img, T, c, h, w)
+        if nb == 0:
+            raise NotImplementedError("DenseBoxRegressor: configuration not covered by the gfx950 kernels")
+        params = self._params()
+        fmap = feat.reshape(n_img, c, h, w).contiguous()
+        filt = filter.reshape(1, ns, T, c).expand(nf, ns, T, c).contiguous()           # image f * ns + s reads sequence s's filters
+        out = torch.empty(n_img, T, 4, h, w, dtype=torch.float32, device=feat.device)
+        ws = workspace(nb, feat.device)
+        rc = L.pt_tamos_bbreg_f32(_ptr(params), _ptr(fmap), _ptr(filt), _ptr(out), n_img, T, c, h, w, _ptr(ws), ws.numel(), _stream())
+        _lib.check(rc, "pt_tamos_bbreg_f32")
+        return out.reshape(1, n_img, T, 4, h, w)

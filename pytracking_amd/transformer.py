@@ -13,7 +13,7 @@ loads with `strict=True` and `pytracking/tracker/tomp/tomp.py:282-303` runs unch
 The torch submodules (nn.MultiheadAttention, nn.Linear, ...) are parameter holders only: their forward is never called.
 Inference only (the tracker runs under `torch.no_grad()`, tomp.py:284); training mode, pre-norm layers, non-ReLU
 activations raise NotImplementedError -- there is no stock-PyTorch fallback.  The multi-object predictor of TaMOs (T object queries
-per batch row) is `pytracking_amd.tamos.GOTFilterPredictor`; the multi-object box regressor is not on the hot path.
+per batch row) is `pytracking_amd.tamos.GOTFilterPredictor`; the multi-object box regressor is `pytracking_amd.tamos.DenseBoxRegressor`.
 """
 import ctypes
 
