@@ -7,25 +7,19 @@
 Each function takes the reference's own module objects and returns the reference's types, dtypes and shapes.  `covered_*`
 say whether a call runs here; install() hands every other call to the reference.
 
-The matcher's weights are packed once per module state (BatchNorm folded, see include/pt_hot.h for the layout).  The pack is
-cached outside the module (a WeakKeyDictionary: not in `state_dict`, `deepcopy` or pickles) under a key of every parameter's
-and buffer's (data_ptr, _version): `load_state_dict`, `.to()` and in-place updates through ordinary ops all change it.  A write
-through `.data` bumps no version counter: after one, call `refresh(module)`.
+The matcher's weights are packed once per module state (BatchNorm folded into the weights, see include/pt_hot.h for the layout)
+and cached outside the module (_packs.py: the key, here with the GNN layer config, and when `refresh(module)` is needed).
 """
 import ctypes
-import weakref
 
 import torch
 
-from . import _lib
+from . import _lib, _packs
+from ._packs import no_grad_needed as _no_grad_needed
 from .filter import _ptr, _stream, device_guarded, workspace
 
 MAX_POINTS = _lib.PT_TCM_MAX_POINTS
-_PACKS = weakref.WeakKeyDictionary()
-
-
-def _no_grad_needed(*tensors):
-    return not (torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors))
+_PACKS = _packs.PackCache()
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -181,27 +175,15 @@ def covered_match(sg, data) -> bool:
     return _no_grad_needed(d0, d1, k0, k1, s0, s1, *params)
 
 
-def _state_key(sg):
-    key = []
-    for t in list(sg.parameters()) + list(sg.buffers()):
-        key.append((t.data_ptr(), t._version, tuple(t.shape)))
-    return tuple(key) + (str(sg.conf.get("GNN_layers")), bool(sg.conf.get("skip_gnn")))
-
-
 def refresh(sg):
     """Drop the packed weights of `sg` (needed only after a write through `.data`, which bumps no version counter)."""
-    _PACKS.pop(sg, None)
+    _PACKS.drop(sg)
 
 
 def _fold(conv, bn=None):
     """(W, b) of a 1x1 Conv1d in float64, with an eval-mode BatchNorm1d behind it folded in."""
-    w = conv.weight.detach().double().reshape(conv.weight.shape[0], -1)
-    b = conv.bias.detach().double()
-    if bn is not None:
-        s = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
-        w = w * s[:, None]
-        b = (b - bn.running_mean.detach().double()) * s + bn.bias.detach().double()
-    return w, b
+    w, b = _packs.bn_fold_weights(conv, bn)
+    return w.reshape(w.shape[0], -1), b
 
 
 def pack_weights(sg):
@@ -230,13 +212,8 @@ def pack_weights(sg):
 
 
 def packed_weights(sg):
-    key = _state_key(sg)
-    hit = _PACKS.get(sg)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    pack = pack_weights(sg)
-    _PACKS[sg] = (key, pack)
-    return pack
+    key = _packs.state_key(list(sg.parameters()) + list(sg.buffers()), str(sg.conf.get("GNN_layers")), bool(sg.conf.get("skip_gnn")))
+    return _PACKS.get(sg, key, pack_weights)
 
 
 def _kpt_norm(kpts, shape):

@@ -26,10 +26,12 @@
 #include <math.h>
 #include "common.h"
 #include "pt_internal.h"
+#include "ds16_enc.h"
 
 namespace {
 
 constexpr int LE_MAX_C = 64, LE_MAX_DIM = 8192, LE_MAX_N = 65535;
+constexpr Ds16Limits LE_LIMITS{LE_MAX_C, LE_MAX_DIM, LE_MAX_N};
 constexpr int ST_TH = 4, ST_TW = 32, ST_THREADS = ST_TH * ST_TW;
 constexpr int ST_LR = 4 * ST_TH + 3, ST_LC = 4 * ST_TW + 4;              // LDS tile: origin row 4*py0 - 3, origin column 4*px0 - 4
 
@@ -160,47 +162,6 @@ __global__ __launch_bounds__(256) void k_le_conv(LeConv a) {
     }
 }
 
-struct LeLayer { int Cin, Cout; size_t w_off, s_off, b_off; };           // offsets into the pack, floats
-struct LePlan {
-    int n, C[4], H[5], W[5];                     // H[0] mask, H[1] stem conv, H[2] pool, H[3] block 1, H[4] block 2 and the heads
-    LeLayer stem, conv[5];                       // conv: res1.conv1|downsample, res1.conv2, res2.conv1|downsample, res2.conv2, heads
-    size_t s0, t1, r1, t2, r2, ws_floats, pack_floats;                   // workspace offsets, floats
-};
-
-int le_plan(int n, int H, int W, int c0, int c1, int c2, int f, LePlan* out) {
-    if (n <= 0 || H <= 0 || W <= 0 || c0 <= 0 || c1 <= 0 || c2 <= 0 || f <= 0) return PT_ERR_SHAPE;
-    for (int c : {c0, c1, c2, f})
-        if (c % 16 || c > LE_MAX_C) return PT_ERR_UNSUPPORTED;
-    if (n > LE_MAX_N || H > LE_MAX_DIM || W > LE_MAX_DIM) return PT_ERR_UNSUPPORTED;
-    LePlan p{};
-    p.n = n; p.C[0] = c0; p.C[1] = c1; p.C[2] = c2; p.C[3] = f;
-    p.H[0] = H; p.W[0] = W;
-    for (int k = 1; k < 5; ++k) { p.H[k] = (p.H[k - 1] - 1) / 2 + 1; p.W[k] = (p.W[k - 1] - 1) / 2 + 1; }
-    size_t pk = 0;
-    auto layer = [&](LeLayer& L, int cin, int cout) {
-        L.Cin = cin; L.Cout = cout;
-        L.w_off = pk; pk += (size_t)cout * 9 * cin;
-        L.s_off = pk; pk += cout;
-        L.b_off = pk; pk += cout;
-    };
-    layer(p.stem, 1, c0);
-    layer(p.conv[0], c0, 2 * c1); layer(p.conv[1], c1, c1);
-    layer(p.conv[2], c1, 2 * c2); layer(p.conv[3], c2, c2);
-    layer(p.conv[4], c2, 2 * f);
-    p.pack_floats = pk;
-    size_t ws = 0;
-    auto take = [&](size_t k) { size_t r = ws; ws += pt_align_floats(k); return r; };
-    const size_t hw2 = (size_t)p.H[2] * p.W[2], hw3 = (size_t)p.H[3] * p.W[3], hw4 = (size_t)p.H[4] * p.W[4];
-    p.s0 = take((size_t)n * c0 * hw2);
-    p.t1 = take((size_t)n * 2 * c1 * hw3);
-    p.r1 = take((size_t)n * c1 * hw3);
-    p.t2 = take((size_t)n * 2 * c2 * hw4);
-    p.r2 = take((size_t)n * c2 * hw4);
-    p.ws_floats = ws;
-    if (out) *out = p;
-    return PT_OK;
-}
-
 template <int S, int M>
 int le_launch_t(const LeConv& a, int T, dim3 grid, hipStream_t st) {
     switch (T) {
@@ -231,57 +192,28 @@ int le_conv(LeConv a, int S, int n, hipStream_t st) {
 
 }  // namespace
 
-size_t pt_label_enc_pack_floats_impl(int c0, int c1, int c2, int f) {
-    LePlan p;
-    return le_plan(1, 1, 1, c0, c1, c2, f, &p) == PT_OK ? p.pack_floats : 0;
-}
+size_t pt_label_enc_pack_floats_impl(int c0, int c1, int c2, int f) { return ds16_pack_floats(2, LE_LIMITS, c0, c1, c2, f); }
 
 size_t pt_label_enc_ws_bytes_impl(int n, int H, int W, int c0, int c1, int c2, int f) {
-    LePlan p;
-    return le_plan(n, H, W, c0, c1, c2, f, &p) == PT_OK ? p.ws_floats * sizeof(float) : 0;
+    return ds16_ws_bytes(2, LE_LIMITS, n, H, W, c0, c1, c2, f);
 }
 
 int pt_label_enc_impl(const float* masks, const float* pack, float* label_enc, float* sample_w, int n, int H, int W, int c0, int c1,
                       int c2, int f, void* ws, size_t ws_bytes, hipStream_t st) {
-    if (!masks || !pack || !label_enc || !sample_w || !ws) return PT_ERR_NULL;
-    LePlan p;
-    int rc = le_plan(n, H, W, c0, c1, c2, f, &p);
-    if (rc) return rc;
-    if ((uintptr_t)pack % 16) return PT_ERR_UNSUPPORTED;                 // 16-byte weight loads
-    for (const void* q : {(const void*)masks, (const void*)label_enc, (const void*)sample_w})
-        if ((uintptr_t)q % 4) return PT_ERR_UNSUPPORTED;
-    if (ws_bytes < p.ws_floats * sizeof(float) || ((uintptr_t)ws % 256) != 0) return PT_ERR_WORKSPACE;
-    float* base = (float*)ws;
-    const long hw3 = (long)p.H[3] * p.W[3], hw4 = (long)p.H[4] * p.W[4];
-    hipLaunchKernelGGL(k_le_stem, dim3(pt_ceil_div(p.W[2], ST_TW), pt_ceil_div(p.H[2], ST_TH), n), dim3(ST_THREADS), 0, st, masks,
-                       pack + p.stem.w_off, pack + p.stem.s_off, pack + p.stem.b_off, base + p.s0, c0, H, W, p.H[1], p.W[1], p.H[2],
-                       p.W[2]);
-    PT_CHECK_LAUNCH();
-    auto conv = [&](int k, const float* in, long in_img, int Hi, int Wi, int Ho, int Wo) {
-        const LeLayer& L = p.conv[k];
-        LeConv a{};
-        a.in = in; a.in_img = in_img;
-        a.w = pack + L.w_off; a.scale = pack + L.s_off; a.shift = pack + L.b_off;
-        a.Cin = L.Cin; a.Cout = L.Cout; a.Hi = Hi; a.Wi = Wi; a.Ho = Ho; a.Wo = Wo;
-        a.csplit = L.Cout; a.out0_img = (long)L.Cout * Ho * Wo;
-        return a;
+    auto stem = [&](const Ds16Plan& p, const float* pk, float* out) -> int {
+        hipLaunchKernelGGL(k_le_stem, dim3(pt_ceil_div(p.W[2], ST_TW), pt_ceil_div(p.H[2], ST_TH), n), dim3(ST_THREADS), 0, st, masks,
+                           pk + p.stem.w_off, pk + p.stem.s_off, pk + p.stem.b_off, out, c0, H, W, p.H[1], p.W[1], p.H[2], p.W[2]);
+        PT_CHECK_LAUNCH();
+        return PT_OK;
     };
-    // block 1: conv1 | downsample as one convolution with 2 C1 outputs (ReLU on the conv1 half), then conv2 + residual + ReLU
-    LeConv a = conv(0, base + p.s0, (long)c0 * p.H[2] * p.W[2], p.H[2], p.W[2], p.H[3], p.W[3]);
-    a.out0 = base + p.t1; a.relu_n = c1;
-    if ((rc = le_conv(a, 2, n, st))) return rc;
-    a = conv(1, base + p.t1, 2 * c1 * hw3, p.H[3], p.W[3], p.H[3], p.W[3]);
-    a.res = base + p.t1 + c1 * hw3; a.res_img = 2 * c1 * hw3; a.out0 = base + p.r1; a.relu_n = c1;
-    if ((rc = le_conv(a, 1, n, st))) return rc;
-    // block 2
-    a = conv(2, base + p.r1, c1 * hw3, p.H[3], p.W[3], p.H[4], p.W[4]);
-    a.out0 = base + p.t2; a.relu_n = c2;
-    if ((rc = le_conv(a, 2, n, st))) return rc;
-    a = conv(3, base + p.t2, 2 * c2 * hw4, p.H[4], p.W[4], p.H[4], p.W[4]);
-    a.res = base + p.t2 + c2 * hw4; a.res_img = 2 * c2 * hw4; a.out0 = base + p.r2; a.relu_n = c2;
-    if ((rc = le_conv(a, 1, n, st))) return rc;
-    // heads: label_pred | samp_w_pred as one convolution with 2 F outputs, ReLU on label_pred's half, written to the two results
-    a = conv(4, base + p.r2, c2 * hw4, p.H[4], p.W[4], p.H[4], p.W[4]);
-    a.csplit = f; a.out0 = label_enc; a.out0_img = f * hw4; a.out1 = sample_w; a.out1_img = f * hw4; a.relu_n = f;
-    return le_conv(a, 1, n, st);
+    auto conv = [&](const Ds16Conv& c, int images) {
+        LeConv a{};
+        a.in = c.in; a.in_img = c.in_img;
+        a.w = c.w; a.scale = c.scale; a.shift = c.shift;
+        a.res = c.res; a.res_img = c.res_img;
+        a.out0 = c.out0; a.out0_img = c.out0_img; a.out1 = c.out1; a.out1_img = c.out1_img;
+        a.csplit = c.csplit; a.Cin = c.Cin; a.Cout = c.Cout; a.Hi = c.Hi; a.Wi = c.Wi; a.Ho = c.Ho; a.Wo = c.Wo; a.relu_n = c.relu_n;
+        return le_conv(a, c.stride, images, st);
+    };
+    return ds16_encode(2, LE_LIMITS, false, masks, pack, label_enc, sample_w, n, H, W, c0, c1, c2, f, ws, ws_bytes, stem, conv);
 }

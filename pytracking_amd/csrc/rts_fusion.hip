@@ -32,10 +32,12 @@
 #include <math.h>
 #include "common.h"
 #include "pt_internal.h"
+#include "ds16_enc.h"
 
 namespace {
 
 constexpr int SE_MAX_C = 64, SE_MAX_DIM = 1024, SE_MAX_N = 1024;
+constexpr Ds16Limits SE_LIMITS{SE_MAX_C, SE_MAX_DIM, SE_MAX_N};
 constexpr int SS_TH = 4, SS_TW = 16, SS_THREADS = SS_TH * SS_TW, SS_CG = 4;
 constexpr int SS_LR = SS_TH + 4, SS_LC = SS_TW + 4;                      // LDS tile: origin row y0 - 2, origin column x0 - 2
 constexpr int SE_CHUNK = 64, SE_CS = 148;                                // channels staged at once; floats per channel (144, padded)
@@ -198,45 +200,6 @@ __global__ __launch_bounds__(256) void k_fuse_add(const float* __restrict__ seg,
     }
 }
 
-struct SeLayer { int Cin, Cout; size_t w_off, s_off, b_off; };           // offsets into the pack, floats
-struct SePlan {
-    int n, C[4], H, W;
-    SeLayer stem, conv[5];                       // conv: res1.conv1|downsample, res1.conv2, res2.conv1|downsample, res2.conv2, heads
-    size_t s0, t1, r1, t2, r2, ws_floats, pack_floats;                   // workspace offsets, floats
-};
-
-int se_plan(int n, int H, int W, int c0, int c1, int c2, int f, SePlan* out) {
-    if (n <= 0 || H <= 0 || W <= 0 || c0 <= 0 || c1 <= 0 || c2 <= 0 || f <= 0) return PT_ERR_SHAPE;
-    for (int c : {c0, c1, c2, f})
-        if (c % 16 || c > SE_MAX_C) return PT_ERR_UNSUPPORTED;
-    if (n > SE_MAX_N || H > SE_MAX_DIM || W > SE_MAX_DIM) return PT_ERR_UNSUPPORTED;
-    SePlan p{};
-    p.n = n; p.C[0] = c0; p.C[1] = c1; p.C[2] = c2; p.C[3] = f; p.H = H; p.W = W;
-    size_t pk = 0;
-    auto layer = [&](SeLayer& L, int cin, int cout) {
-        L.Cin = cin; L.Cout = cout;
-        L.w_off = pk; pk += (size_t)cout * 9 * cin;
-        L.s_off = pk; pk += cout;
-        L.b_off = pk; pk += cout;
-    };
-    layer(p.stem, 1, c0);
-    layer(p.conv[0], c0, 2 * c1); layer(p.conv[1], c1, c1);
-    layer(p.conv[2], c1, 2 * c2); layer(p.conv[3], c2, c2);
-    layer(p.conv[4], c2, 2 * f);
-    p.pack_floats = pk;
-    size_t ws = 0;
-    auto take = [&](size_t k) { size_t r = ws; ws += pt_align_floats(k); return r; };
-    const size_t hw = (size_t)H * W;
-    p.s0 = take((size_t)n * c0 * hw);
-    p.t1 = take((size_t)n * 2 * c1 * hw);
-    p.r1 = take((size_t)n * c1 * hw);
-    p.t2 = take((size_t)n * 2 * c2 * hw);
-    p.r2 = take((size_t)n * c2 * hw);
-    p.ws_floats = ws;
-    if (out) *out = p;
-    return PT_OK;
-}
-
 // Tile choice from the shape alone: waves (= tiles of 16 output channels) per workgroup.  A workgroup stages its pixels' patch once for
 // all its waves, so more waves mean less staging -- but the deployed problem is 27 pixel tiles of one map, and the chip has 256 CUs: the
 // largest count that still gives about a hundred workgroups, else one wave per workgroup (the most workgroups there are).
@@ -263,60 +226,31 @@ int se_conv(const SeConv& a, int n, hipStream_t st) {
 
 }  // namespace
 
-size_t pt_score_enc_pack_floats_impl(int c0, int c1, int c2, int f) {
-    SePlan p;
-    return se_plan(1, 1, 1, c0, c1, c2, f, &p) == PT_OK ? p.pack_floats : 0;
-}
+size_t pt_score_enc_pack_floats_impl(int c0, int c1, int c2, int f) { return ds16_pack_floats(1, SE_LIMITS, c0, c1, c2, f); }
 
 size_t pt_score_enc_ws_bytes_impl(int n, int H, int W, int c0, int c1, int c2, int f) {
-    SePlan p;
-    return se_plan(n, H, W, c0, c1, c2, f, &p) == PT_OK ? p.ws_floats * sizeof(float) : 0;
+    return ds16_ws_bytes(1, SE_LIMITS, n, H, W, c0, c1, c2, f);
 }
 
 int pt_score_enc_impl(const float* scores, const float* pack, float* label_enc, float* sample_w, int n, int H, int W, int c0, int c1,
                       int c2, int f, void* ws, size_t ws_bytes, hipStream_t st) {
-    if (!scores || !pack || !label_enc || !ws) return PT_ERR_NULL;       // sample_w may be null: that half of the heads is skipped
-    SePlan p;
-    int rc = se_plan(n, H, W, c0, c1, c2, f, &p);
-    if (rc) return rc;
-    if ((uintptr_t)pack % 16) return PT_ERR_UNSUPPORTED;                 // 16-byte weight loads
-    for (const void* q : {(const void*)scores, (const void*)label_enc, (const void*)sample_w})
-        if ((uintptr_t)q % 4) return PT_ERR_UNSUPPORTED;
-    if (ws_bytes < p.ws_floats * sizeof(float) || ((uintptr_t)ws % 256) != 0) return PT_ERR_WORKSPACE;
-    float* base = (float*)ws;
-    const long hw = (long)H * W;
-    hipLaunchKernelGGL(k_se_stem, dim3(pt_ceil_div(W, SS_TW), pt_ceil_div(H, SS_TH) * (c0 / SS_CG), n), dim3(SS_THREADS), 0, st, scores,
-                       pack + p.stem.w_off, pack + p.stem.s_off, pack + p.stem.b_off, base + p.s0, c0, H, W);
-    PT_CHECK_LAUNCH();
-    auto conv = [&](int k, const float* in, long in_img) {
-        const SeLayer& L = p.conv[k];
-        SeConv a{};
-        a.in = in; a.in_img = in_img; a.Cin1 = L.Cin;
-        a.w = pack + L.w_off; a.scale = pack + L.s_off; a.shift = pack + L.b_off;
-        a.Cin = L.Cin; a.Cout = L.Cout; a.H = H; a.W = W;
-        a.csplit = L.Cout; a.out0_img = (long)L.Cout * hw;
-        return a;
+    auto stem = [&](const Ds16Plan& p, const float* pk, float* out) -> int {
+        hipLaunchKernelGGL(k_se_stem, dim3(pt_ceil_div(W, SS_TW), pt_ceil_div(H, SS_TH) * (c0 / SS_CG), n), dim3(SS_THREADS), 0, st, scores,
+                           pk + p.stem.w_off, pk + p.stem.s_off, pk + p.stem.b_off, out, c0, H, W);
+        PT_CHECK_LAUNCH();
+        return PT_OK;
     };
-    // block 1: conv1 | downsample as one convolution with 2 C1 outputs (ReLU on the conv1 half), then conv2 + residual + ReLU
-    SeConv a = conv(0, base + p.s0, c0 * hw);
-    a.out0 = base + p.t1; a.relu_n = c1;
-    if ((rc = se_conv<false>(a, n, st))) return rc;
-    a = conv(1, base + p.t1, 2 * c1 * hw);
-    a.res = base + p.t1 + c1 * hw; a.res_img = 2 * c1 * hw; a.out0 = base + p.r1; a.relu_n = c1;
-    if ((rc = se_conv<false>(a, n, st))) return rc;
-    // block 2
-    a = conv(2, base + p.r1, c1 * hw);
-    a.out0 = base + p.t2; a.relu_n = c2;
-    if ((rc = se_conv<false>(a, n, st))) return rc;
-    a = conv(3, base + p.t2, 2 * c2 * hw);
-    a.res = base + p.t2 + c2 * hw; a.res_img = 2 * c2 * hw; a.out0 = base + p.r2; a.relu_n = c2;
-    if ((rc = se_conv<false>(a, n, st))) return rc;
-    // heads: label_pred | samp_w_pred as one convolution with 2 F outputs, ReLU on label_pred's half, written to the two results; without
-    // sample_w only label_pred's F channels (the leading rows of the weights, scales and shifts) are computed
-    a = conv(4, base + p.r2, c2 * hw);
-    if (!sample_w) a.Cout = f;
-    a.csplit = f; a.out0 = label_enc; a.out0_img = f * hw; a.out1 = sample_w; a.out1_img = f * hw; a.relu_n = f;
-    return se_conv<false>(a, n, st);
+    auto conv = [&](const Ds16Conv& c, int images) {
+        SeConv a{};
+        a.in = c.in; a.in_img = c.in_img; a.Cin1 = c.Cin;
+        a.w = c.w; a.scale = c.scale; a.shift = c.shift;
+        a.res = c.res; a.res_img = c.res_img;
+        a.out0 = c.out0; a.out0_img = c.out0_img; a.out1 = c.out1; a.out1_img = c.out1_img;
+        a.csplit = c.csplit; a.Cin = c.Cin; a.Cout = c.Cout; a.H = c.Ho; a.W = c.Wo; a.relu_n = c.relu_n;
+        return se_conv<false>(a, images, st);
+    };
+    // sample_w may be null: that half of the heads is skipped
+    return ds16_encode(1, SE_LIMITS, true, scores, pack, label_enc, sample_w, n, H, W, c0, c1, c2, f, ws, ws_bytes, stem, conv);
 }
 
 size_t pt_learners_fuse_pack_floats_impl(int f) {

@@ -23,15 +23,8 @@ import math
 import torch
 
 from . import _lib
+from ._packs import dev_f32 as _dev_f32, no_grad_needed as _no_grad_needed, require_device as _require_device
 from .filter import _ptr, _stream, device_guarded, workspace
-
-
-def _dev_f32(t, dim=None):
-    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and (dim is None or t.dim() == dim)
-
-
-def _no_grad_needed(*tensors):
-    return not (torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors))
 
 
 def series_sizes(H, W):
@@ -172,12 +165,6 @@ def insert_torch(samples, xf, ind, shift=None):
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # the kernels
-
-def _require_device(*tensors):
-    for t in tensors:
-        if isinstance(t, torch.Tensor) and not t.is_cuda:
-            raise RuntimeError("pytracking_amd ops run on the MI355X only (got a CPU tensor)")
-
 
 def covered_sample(x, proj, window, interp) -> bool:
     if not _dev_f32(x, 4) or min(x.shape) < 1 or max(x.shape[-2:]) > _lib.PT_ECO_MAX_FEAT:

@@ -5,22 +5,16 @@
 Both towers -- conv3_2t(conv3_1t(layer2)) and conv4_2t(conv4_1t(layer3)), each block Conv2d(3x3, pad 1, bias) -> BatchNorm2d (eval) ->
 ReLU -- in one call.  `covered(module, feat2)` says whether a call runs here; install(iou_feat=True) hands every other call to the
 reference.  The weights are packed once per module state (tap-major weights, bias + eval BatchNorm as per-channel scale / shift; layout
-in include/pt_hot.h) and cached outside the module like the KeepTrack matcher's: the key is every parameter's and buffer's
-(data_ptr, _version), so `load_state_dict` and in-place updates are picked up; after a write through `.data` call `refresh(module)`.
+in include/pt_hot.h) and cached outside the module (_packs.py: the key, and when `refresh(module)` is needed).
 """
-import weakref
-
 import torch
 
 from . import _lib
+from ._packs import CPU_TENSOR, PackCache, aligned as _aligned, bn_fold, bn_ok, conv_ok, layers_key, tap_major, tensors as _tensors
 from .filter import _ptr, _stream, device_guarded, workspace
 
 BLOCKS = ("conv3_1t", "conv3_2t", "conv4_1t", "conv4_2t")
-_PACKS = weakref.WeakKeyDictionary()
-
-
-def _one(v):
-    return v[0] if isinstance(v, (tuple, list)) and len(v) == 2 and v[0] == v[1] else v
+_PACKS = PackCache()
 
 
 def _blocks(module):
@@ -31,15 +25,7 @@ def _blocks(module):
         if not isinstance(blk, torch.nn.Sequential) or len(blk) != 3:
             return None
         conv, bn, act = blk[0], blk[1], blk[2]
-        if not (isinstance(conv, torch.nn.Conv2d) and isinstance(bn, torch.nn.BatchNorm2d) and isinstance(act, torch.nn.ReLU)):
-            return None
-        if (_one(conv.kernel_size), _one(conv.stride), _one(conv.padding), _one(conv.dilation)) != (3, 1, 1, 1):
-            return None
-        if conv.groups != 1 or conv.bias is None or conv.padding_mode != "zeros":
-            return None
-        if not bn.track_running_stats or bn.running_mean is None or bn.running_var is None or not bn.affine:
-            return None
-        if bn.num_features != conv.out_channels:
+        if not (conv_ok(conv, 3, 1, True) and bn_ok(bn, conv.out_channels) and isinstance(act, torch.nn.ReLU)):
             return None
         out.append((conv, bn))
     if out[1][0].in_channels != out[0][0].out_channels or out[3][0].in_channels != out[2][0].out_channels:
@@ -50,13 +36,6 @@ def _blocks(module):
 def _channels(blocks):
     return (blocks[0][0].in_channels, blocks[0][0].out_channels, blocks[1][0].out_channels,
             blocks[2][0].in_channels, blocks[2][0].out_channels, blocks[3][0].out_channels)
-
-
-def _tensors(blocks):
-    out = []
-    for conv, bn in blocks:
-        out += [conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var]
-    return out
 
 
 def _maps(feat2):
@@ -77,34 +56,23 @@ def pack_weights(module):
                                   "Cmid % 16 == 0, Cout % 16 == 0")
     parts = []
     for conv, bn in blocks:
-        s = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
-        shift = (conv.bias.detach().double() - bn.running_mean.detach().double()) * s + bn.bias.detach().double()
-        parts += [conv.weight.detach().permute(0, 2, 3, 1).reshape(-1).float(), s.float(), shift.float()]
+        s, shift = bn_fold(conv, bn)
+        parts += [tap_major(conv).reshape(-1), s.float(), shift.float()]
     pack = torch.cat(parts).contiguous()
     assert pack.numel() == n, (pack.numel(), n)
     return pack
 
 
-def _state_key(blocks):
-    return tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in _tensors(blocks)) + tuple(bn.eps for _, bn in blocks)
-
-
 def refresh(module):
     """Drop the packed weights of `module` (needed only after a write through `.data`, which bumps no version counter)."""
-    _PACKS.pop(module, None)
+    _PACKS.drop(module)
 
 
 def packed_weights(module, blocks=None):
     blocks = _blocks(module) if blocks is None else blocks
     if blocks is None:
         return pack_weights(module)                            # raises
-    key = _state_key(blocks)
-    hit = _PACKS.get(module)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    pack = pack_weights(module)
-    _PACKS[module] = (key, pack)
-    return pack
+    return _PACKS.get(module, layers_key(blocks), pack_weights)
 
 
 def covered(module, feat2) -> bool:
@@ -128,18 +96,13 @@ def covered(module, feat2) -> bool:
                                            f4.shape[3]) > 0
 
 
-def _aligned(t):
-    t = t.contiguous()
-    return t if t.data_ptr() % 16 == 0 else t.clone()
-
-
 @device_guarded
 def get_iou_feat(module, feat2, checked=False):
     """reference: AtomIoUNet.get_iou_feat -> (c3_t (n, Cout3, H3, W3), c4_t (n, Cout4, H4, W4))."""
     maps = _maps(feat2)
     for f in (maps or []):
         if not f.is_cuda:
-            raise RuntimeError("pytracking_amd ops run on the MI355X only (got a CPU tensor)")
+            raise RuntimeError(CPU_TENSOR)
     if not checked and not covered(module, feat2):
         raise NotImplementedError("get_iou_feat: eval mode, device fp32, no grad, Conv2d(3x3, pad 1, bias) + BatchNorm2d + ReLU blocks, "
                                   "Cin % 64 == 0, Cmid % 16 == 0, Cout % 16 == 0, H * W <= 4096, n <= 8")

@@ -12,28 +12,20 @@ volume is pinned by goldens of the unmodified reference.
 
 Each function takes the reference's own module objects and returns the reference's types and shapes; `covered_*` say whether a call runs
 here, install() hands every other call to the reference.  The predictor's weights are packed once per module state (eval BatchNorm
-folded; layout in include/pt_hot.h) and cached outside the module like the KeepTrack matcher's: after a write through `.data` call
-`refresh(module)`.
+folded into the weights; layout in include/pt_hot.h) and cached outside the module (_packs.py: the key, here with `conf_measure`, and
+when `refresh(module)` is needed).
 """
 import ctypes
 import warnings
-import weakref
 
 import torch
 
-from . import _lib
+from . import _lib, _packs
+from ._packs import dev_f32 as _dev_f32, no_grad_needed as _no_grad_needed, one
 from .filter import _ptr, _stream, device_guarded, workspace
 
-_PACKS = weakref.WeakKeyDictionary()
+_PACKS = _packs.PackCache()
 _SHIFT_PX = []
-
-
-def _no_grad_needed(*tensors):
-    return not (torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors))
-
-
-def _dev_f32(t, dim=None):
-    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and (dim is None or t.dim() == dim)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -56,7 +48,7 @@ def cost_volume(feat_cur, feat_prev, max_displacement, remap=True, kernel_size=3
     (B, (2 md + 1)^2, H, W) (channel = displacement).  Definition in include/pt_hot.h."""
     for t in (feat_cur, feat_prev):
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise RuntimeError("pytracking_amd ops run on the MI355X only (got a CPU tensor)")
+            raise RuntimeError(_packs.CPU_TENSOR)
     if not _covered_cv(feat_cur, feat_prev, kernel_size, max_displacement, stride):
         raise NotImplementedError("cost volume: device fp32 (B, C, H, W) pairs, kernel_size 3, stride 1, max_displacement >= 1, "
                                   f"H*W <= {_lib.PT_KYS_CV_MAX_HW}, no grad")
@@ -91,8 +83,6 @@ class SpatialCorrelationSampler(torch.nn.Module):
 
 def _sampler_md(layer):
     """max_displacement of a sampler object this module covers (this module's class or the upstream one), else None."""
-    def one(v):
-        return v[0] if isinstance(v, (tuple, list)) and len(v) == 2 and v[0] == v[1] else v
     try:
         k, p, s, pad = one(layer.kernel_size), one(layer.patch_size), one(layer.stride), one(layer.padding)
         dil, dilp = one(getattr(layer, "dilation", 1)), one(getattr(layer, "dilation_patch", 1))
@@ -163,12 +153,7 @@ def _dims(pred):
 
 
 def _fold(conv, bn=None):
-    w = conv.weight.detach().double()
-    b = conv.bias.detach().double() if conv.bias is not None else None
-    if bn is not None:
-        s = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
-        w = w * s[:, None, None, None]
-        b = (b - bn.running_mean.detach().double()) * s + bn.bias.detach().double()
+    w, b = _packs.bn_fold_weights(conv, bn)
     return [w] + ([b] if b is not None else [])
 
 
@@ -193,23 +178,13 @@ def pack_weights(pred):
     return pack
 
 
-def _state_key(pred):
-    return tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in list(pred.parameters()) + list(pred.buffers())) + (pred.conf_measure,)
-
-
 def refresh(pred):
     """Drop the packed weights of `pred` (needed only after a write through `.data`, which bumps no version counter)."""
-    _PACKS.pop(pred, None)
+    _PACKS.drop(pred)
 
 
 def packed_weights(pred):
-    key = _state_key(pred)
-    hit = _PACKS.get(pred)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    pack = pack_weights(pred)
-    _PACKS[pred] = (key, pack)
-    return pack
+    return _PACKS.get(pred, _packs.state_key(list(pred.parameters()) + list(pred.buffers()), pred.conf_measure), pack_weights)
 
 
 def covered_predict_response(wrapper, data, dimp_thresh=None, output_window=None) -> bool:
@@ -256,9 +231,7 @@ def covered_predict_response(wrapper, data, dimp_thresh=None, output_window=None
 def predict_response(wrapper, data, dimp_thresh=None, output_window=None, checked=False):
     """reference: PredictorWrapper.predict_response (predictor_wrapper.py:88-153) -> the reference's dict: response (the shape of
     dimp_score_cur), state_cur (B, 8, H, W), cost_volume (B, H*W, H, W), auxiliary_outputs with every key the reference fills."""
-    for t in (data.get("feat1"), data.get("feat2"), data.get("dimp_score_cur")):
-        if isinstance(t, torch.Tensor) and not t.is_cuda:
-            raise RuntimeError("pytracking_amd ops run on the MI355X only (got a CPU tensor)")
+    _packs.require_device(data.get("feat1"), data.get("feat2"), data.get("dimp_score_cur"))
     if not checked and not covered_predict_response(wrapper, data, dimp_thresh, output_window):
         raise NotImplementedError("predict_response: eval mode, one reference frame, device fp32, conf_measure 'max' / 'none', state_dim 8, "
                                   f"representation dims (64, 32), H*W <= {_lib.PT_KYS_PRED_MAX_HW}, no grad")

@@ -7,29 +7,24 @@ Every level (score resize, proj, TSE, RRB, CAB, RRB) and the Upsampler in one as
 NCHW, 3x3 convolutions on the banded tap-major correlation or the per-tap GEMM route with one epilogue kernel behind them, small kernels
 for the means, the CAB gate, the resizes and the last one-channel convolution.  `covered(...)` says whether a call runs here;
 install(decoder=True) hands every other call to the reference.  The weights are packed once per module state (tap-major 3x3 weights; bias
-and eval BatchNorm as per-channel scale / shift folded in float64; layout in include/pt_hot.h) and cached outside the module: the key is
-every parameter's and buffer's (data_ptr, _version, shape) plus the BatchNorm eps values, so `load_state_dict` and in-place updates are
-picked up; after a write through `.data` call `refresh(module)`.
+and eval BatchNorm as per-channel scale / shift folded in float64; layout in include/pt_hot.h) and cached outside the module (_packs.py:
+the key, and when `refresh(module)` is needed).
 """
 import ctypes
-import weakref
 from collections import OrderedDict
 
 import torch
 
-from . import _lib
+from . import _lib, _packs
 from .filter import _ptr, _stream, device_guarded, workspace
-from .label_encoder import _bn_ok, _one
 
-_PACKS = weakref.WeakKeyDictionary()
+_PACKS = _packs.PackCache()
 _OC = {"layer1": 1, "layer2": 2, "layer3": 2, "layer4": 4}                       # decoder.py:104
 _ORDERS = (("layer4", "layer3", "layer2", "layer1"), ("layer3", "layer2", "layer1"))
 
 
 def _conv_ok(conv, k, i, o, bias=True):
-    return (type(conv) is torch.nn.Conv2d and (_one(conv.kernel_size), _one(conv.stride), _one(conv.padding), _one(conv.dilation))
-            == (k, 1, k // 2, 1) and conv.groups == 1 and conv.padding_mode == "zeros" and (conv.bias is not None) == bias
-            and (conv.in_channels, conv.out_channels) == (i, o))
+    return _packs.conv_ok(conv, k, 1, bias) and (conv.in_channels, conv.out_channels) == (i, o)
 
 
 def _relu_ok(m):
@@ -54,7 +49,7 @@ def _rrb(m, oc):
     bn = b[1] if b is not None else None
     if b is None:
         b = _seq(m.bblock, "crc")
-    if b is None or not _conv_ok(b[0], 3, oc, oc) or not _conv_ok(b[-1], 3, oc, oc, bias=False) or (bn is not None and not _bn_ok(bn, oc)):
+    if b is None or not _conv_ok(b[0], 3, oc, oc) or not _conv_ok(b[-1], 3, oc, oc, bias=False) or (bn is not None and not _packs.bn_ok(bn, oc)):
         return None
     return [(m.conv1x1, None), (b[0], bn), (b[-1], None)]
 
@@ -112,15 +107,6 @@ def _structure(module):
     return dict(levels=levels, fc=tuple(fcs), ic=ic, mdim=mdim, use_bn=bool(use_bn), layers=layers)
 
 
-def _tensors(layers):
-    out = []
-    for conv, bn in layers:
-        out += [conv.weight] + ([conv.bias] if conv.bias is not None else [])
-        if bn is not None:
-            out += [bn.weight, bn.bias, bn.running_mean, bn.running_var]
-    return out
-
-
 def _ints(values):
     values = [int(v) for v in values]
     return (ctypes.c_int * len(values))(*values)
@@ -128,16 +114,6 @@ def _ints(values):
 
 def _pack_floats(st):
     return _lib.lib().pt_lwl_decoder_pack_floats(len(st["levels"]), _ints(st["fc"]), st["ic"], st["mdim"], int(st["use_bn"]))
-
-
-def _folded(conv, bn):
-    """(scale, shift) of one 3x3 convolution, float32; the fold is done in float64."""
-    o = conv.out_channels
-    bias = conv.bias.detach().double() if conv.bias is not None else torch.zeros(o, dtype=torch.float64, device=conv.weight.device)
-    if bn is None:
-        return torch.ones_like(bias).float(), bias.float()
-    s = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
-    return s.float(), ((bias - bn.running_mean.detach().double()) * s + bn.bias.detach().double()).float()
 
 
 def pack_weights(module):
@@ -149,38 +125,26 @@ def pack_weights(module):
     parts = []
     last = st["layers"][-1][0]
     for conv, bn in st["layers"]:
-        w = conv.weight.detach().float()
-        if conv is last:                                              # (1, mdim/2, 3, 3) -> (9, mdim/2), then the bias
-            parts += [w.permute(0, 2, 3, 1).reshape(-1), conv.bias.detach().float().reshape(-1)]
-        elif w.shape[-1] == 1:                                        # 1x1: (o, i), bias
-            parts += [w.reshape(-1), conv.bias.detach().float().reshape(-1)]
-        else:                                                         # 3x3: tap-major (o, 9, i), scale, shift
-            parts += [w.permute(0, 2, 3, 1).reshape(-1), *_folded(conv, bn)]
+        w = _packs.tap_major(conv).reshape(-1)                        # 1x1: (o, i); 3x3: tap-major (o, 9, i)
+        if conv is last or conv.weight.shape[-1] == 1:                # then the bias
+            parts += [w, conv.bias.detach().float().reshape(-1)]
+        else:                                                         # then scale, shift
+            parts += [w] + [v.float() for v in _packs.bn_fold(conv, bn)]
     pack = torch.cat(parts).contiguous()
     assert pack.numel() == n, (pack.numel(), n)
     return pack
 
 
-def _state_key(layers):
-    return tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in _tensors(layers)) + tuple(bn.eps for _, bn in layers if bn is not None)
-
-
 def refresh(module):
     """Drop the packed weights of `module` (needed only after a write through `.data`, which bumps no version counter)."""
-    _PACKS.pop(module, None)
+    _PACKS.drop(module)
 
 
 def packed_weights(module, st=None):
     st = _structure(module) if st is None else st
     if st is None:
         return pack_weights(module)                            # raises
-    key = _state_key(st["layers"])
-    hit = _PACKS.get(module)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    pack = pack_weights(module)
-    _PACKS[module] = (key, pack)
-    return pack
+    return _PACKS.get(module, _packs.layers_key(st["layers"]), pack_weights)
 
 
 def _image_hw(image_size):
@@ -216,32 +180,19 @@ def covered(module, scores, features, image_size, output_layers=(), num_objects=
     st = _structure(module)
     if st is None or num_objects is not None:
         return False
-    if module.training or any(m.training for m in module.modules()):
-        return False
     shp = _shapes(st, scores, features, image_size)
     if shp is None:
         return False
     acts = [scores] + [features[L] for L in st["levels"]]
-    if not all(t.is_cuda and t.dtype == torch.float32 and t.device == scores.device for t in acts):
-        return False
-    tens = _tensors(st["layers"])
-    if any(t.device != scores.device or t.dtype != torch.float32 for t in tens):
-        return False
-    if torch.is_grad_enabled() and any(t.requires_grad for t in tens + acts):
+    if not scores.is_cuda or not _packs.quiet(module, _packs.tensors(st["layers"]) + acts, scores):
         return False
     return _ws_bytes(st, shp) > 0
-
-
-def _dense(t):
-    t = t.contiguous()
-    return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
 @device_guarded
 def forward(module, scores, features, image_size, output_layers=(), num_objects=None, checked=False):
     """reference: LWTLDecoder.forward -> (mask (n, 1, H, W), OrderedDict of the '{L}_dec' maps named in `output_layers`)."""
-    if any(isinstance(t, torch.Tensor) and not t.is_cuda for t in [scores] + (list(features.values()) if hasattr(features, "values") else [])):
-        raise RuntimeError("pytracking_amd ops run on the MI355X only (got a CPU tensor)")
+    _packs.require_device(scores, *(features.values() if hasattr(features, "values") else []))
     if not checked and not covered(module, scores, features, image_size, output_layers, num_objects):
         raise NotImplementedError("decoder: eval mode, device fp32 5-D scores, one feature map per level with batch frames * sequences, no "
                                   "grad, num_objects=None, the structure of LWTLDecoder, ic % 16 == 0, mdim % 32 == 0, fc % 16 == 0, n <= 8")
@@ -249,8 +200,8 @@ def forward(module, scores, features, image_size, output_layers=(), num_objects=
     pack = packed_weights(module, st)
     n, hw, shw, ihw = _shapes(st, scores, features, image_size)
     levels = st["levels"]
-    s = _dense(scores.reshape(n, *scores.shape[-3:]))
-    feats = [_dense(features[L]) for L in levels]
+    s = _packs.aligned(scores.reshape(n, *scores.shape[-3:]))
+    feats = [_packs.aligned(features[L]) for L in levels]
     mask = torch.empty((n, 1) + ihw, dtype=torch.float32, device=s.device)
     outputs = OrderedDict()
     for k, L in enumerate(levels):

@@ -11,82 +11,34 @@ sample-weight half of the heads (the tracker discards it).  `segment_target` res
 .apply_target_model` and `net.decoder` are called as they are (so whatever install() bound there is used) and the bilinear resize of the
 encoded scores plus the fusion ('add', or 'concat' + Conv2d(2F, F, 3, padding=1)) run in ONE launch in between.  `encoder_covered` /
 `segment_covered` say whether a call runs here; install(rts_fusion=True) hands every other call to the reference.  The weights are packed
-once per module state and cached outside the module exactly as the label encoder's are (key: every parameter's and buffer's (data_ptr,
-_version, shape) plus the BatchNorm eps values); after a write through `.data` call `refresh(module)`.
+once per module state by the recogniser and packer the label encoder uses, and cached outside the module (_packs.py: the key, and when
+`refresh(module)` is needed).
 """
-import weakref
-
 import torch
 
 from . import _lib
+from ._packs import CPU_TENSOR, PackCache, aligned as _aligned, conv_ok, dev_f32 as _dev_f32, ds16_channels as _channels, ds16_layers, ds16_pack, layers_key, quiet as _quiet, tap_major, tensors as _tensors
 from .filter import _ptr, _stream, device_guarded
 from .filter import workspace
-from .label_encoder import _aligned, _bn_ok, _channels, _conv_block, _conv_ok, _folded, _one, _state_key, _tensors
 
-_PACKS = weakref.WeakKeyDictionary()
+_PACKS = PackCache()
 FUSION_TYPES = {"add": _lib.PT_FUSE_ADD, "concat": _lib.PT_FUSE_CONCAT}
 
 
-def _basic_block(blk):
-    """[(Conv2d, BatchNorm2d or None)] x 3 -- conv1, downsample, conv2 -- of a BasicBlock(stride 1, downsample = biased 3x3 stride-1 conv)
-    (ltr/models/backbone/resnet.py:15-53), else None."""
-    need = ("conv1", "conv2", "downsample", "relu", "use_bn")
-    if blk is None or type(blk).__name__ != "BasicBlock" or not all(hasattr(blk, a) for a in need):
-        return None
-    if not (_conv_ok(blk.conv1, 1, False) and _conv_ok(blk.conv2, 1, False) and _conv_ok(blk.downsample, 1, True)):
-        return None
-    if not isinstance(blk.relu, torch.nn.ReLU):
-        return None
-    c = blk.conv1.out_channels
-    if (blk.conv2.in_channels, blk.conv2.out_channels, blk.downsample.in_channels, blk.downsample.out_channels) != (c, c, blk.conv1.in_channels, c):
-        return None
-    bn1, bn2 = (getattr(blk, "bn1", None), getattr(blk, "bn2", None)) if blk.use_bn else (None, None)
-    if blk.use_bn and not (_bn_ok(bn1, c) and _bn_ok(bn2, c)):
-        return None
-    return [(blk.conv1, bn1), (blk.downsample, None), (blk.conv2, bn2)]
-
-
 def _layers(module):
-    """[(Conv2d, BatchNorm2d or None)] in pack order -- stem, res1.conv1, res1.downsample, res1.conv2, res2.conv1, res2.downsample,
-    res2.conv2, label_pred, samp_w_pred -- if `module` has exactly the structure of ResidualDS16SW_Clf, else None."""
-    if type(module).__name__ != "ResidualDS16SW_Clf" or not all(hasattr(module, a) for a in ("conv_block", "pool", "res1", "res2",
-                                                                                             "label_pred", "samp_w_pred")):
-        return None
-    pool = module.pool
-    if type(pool) is not torch.nn.MaxPool2d or (_one(pool.kernel_size), _one(pool.stride), _one(pool.padding), _one(pool.dilation)) != (3, 1, 1, 1):
-        return None
-    if pool.ceil_mode or pool.return_indices:
-        return None
-    stem, head = _conv_block(module.conv_block, 1, True), _conv_block(module.label_pred, 1, True)
-    b1, b2 = _basic_block(module.res1), _basic_block(module.res2)
-    if stem is None or head is None or b1 is None or b2 is None or not _conv_ok(module.samp_w_pred, 1, True):
-        return None
-    out = [stem] + b1 + b2 + [head, (module.samp_w_pred, None)]
-    c0, c1, c2, f = _channels(out)
-    chain = (stem[0].in_channels == 1 and b1[0][0].in_channels == c0 and b2[0][0].in_channels == c1 and head[0].in_channels == c2
-             and module.samp_w_pred.in_channels == c2 and module.samp_w_pred.out_channels == f)
-    return out if chain else None
+    """[(Conv2d, BatchNorm2d or None)] in pack order if `module` has exactly the structure of ResidualDS16SW_Clf, else None."""
+    return ds16_layers(module, "ResidualDS16SW_Clf", 1)
 
 
 def pack_weights(module):
     """The pt_score_enc_f32 pack of a ResidualDS16SW_Clf (float32, on its device; include/pt_hot.h): the label encoder's layout."""
-    layers = _layers(module)
-    n = _lib.lib().pt_score_enc_pack_floats(*_channels(layers)) if layers is not None else 0
-    if n == 0:
-        raise NotImplementedError("score encoder: the structure of ResidualDS16SW_Clf with layer dims that are multiples of 16 up to 64")
-    parts = []
-    for group in ([0], [1, 2], [3], [4, 5], [6], [7, 8]):              # a block's conv1 | downsample and the two heads are one layer each
-        w, s, b = zip(*[_folded(*layers[k]) for k in group])
-        parts += [torch.cat(w).reshape(-1), torch.cat(s), torch.cat(b)]
-    pack = torch.cat(parts).contiguous()
-    assert pack.numel() == n, (pack.numel(), n)
-    return pack
+    return ds16_pack(_layers(module), "pt_score_enc_pack_floats", "score encoder: the structure of ResidualDS16SW_Clf")
 
 
 def _fusion_conv(fusion):
     """The Conv2d of a 'concat' LearnersFusion if it is Conv2d(2F, F, 3, padding=1, bias), else None."""
     conv = getattr(fusion, "fusion_conv1", None)
-    if conv is None or not _conv_ok(conv, 1, True) or conv.in_channels != 2 * conv.out_channels:
+    if conv is None or not conv_ok(conv, 3, 1, True) or conv.in_channels != 2 * conv.out_channels:
         return None
     return conv
 
@@ -107,54 +59,35 @@ def pack_fusion(fusion):
     n = _lib.lib().pt_learners_fuse_pack_floats(conv.out_channels) if conv is not None else 0
     if n == 0:
         raise NotImplementedError("learners fusion: a 'concat' LearnersFusion with Conv2d(2F, F, 3, padding=1), F a multiple of 16 up to 64")
-    pack = torch.cat([conv.weight.detach().permute(0, 2, 3, 1).reshape(-1).float(), conv.bias.detach().float()]).contiguous()
+    pack = torch.cat([tap_major(conv).reshape(-1), conv.bias.detach().float()]).contiguous()
     assert pack.numel() == n, (pack.numel(), n)
     return pack
 
 
 def refresh(module):
     """Drop the packed weights of `module` (needed only after a write through `.data`, which bumps no version counter)."""
-    _PACKS.pop(module, None)
-
-
-def _cached(module, layers, make):
-    key = _state_key(layers)
-    hit = _PACKS.get(module)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    pack = make(module)
-    _PACKS[module] = (key, pack)
-    return pack
+    _PACKS.drop(module)
 
 
 def packed_weights(module, layers=None):
     layers = _layers(module) if layers is None else layers
     if layers is None:
         return pack_weights(module)                            # raises
-    return _cached(module, layers, pack_weights)
+    return _PACKS.get(module, layers_key(layers), pack_weights)
 
 
 def packed_fusion(fusion):
     conv = _fusion_conv(fusion) if _fusion_kind(fusion) == "concat" else None
     if conv is None:
         return pack_fusion(fusion)                             # raises
-    return _cached(fusion, [(conv, None)], pack_fusion)
-
-
-def _quiet(module, tensors, like):
-    """Eval mode, everything fp32 on the device of `like`, nothing that asks for a gradient."""
-    if module.training or any(m.training for m in module.modules()):
-        return False
-    if any(t.device != like.device or t.dtype != torch.float32 for t in tensors):
-        return False
-    return not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors))
+    return _PACKS.get(fusion, layers_key([(conv, None)]), pack_fusion)
 
 
 def encoder_covered(module, scores, feature=None) -> bool:
     layers = _layers(module)
     if layers is None or not isinstance(scores, torch.Tensor) or scores.dim() != 4:
         return False
-    if not (scores.is_cuda and scores.dtype == torch.float32) or scores.numel() == 0:
+    if not _dev_f32(scores) or scores.numel() == 0:
         return False
     if not _quiet(module, _tensors(layers) + [scores], scores):
         return False
@@ -167,7 +100,7 @@ def encode(module, scores, feature=None, checked=False, want_sample_w=True):
     """reference: ResidualDS16SW_Clf.forward -> (label_enc, sample_w), each (frames, seq, F, H, W); sample_w is None when it is not
     wanted."""
     if isinstance(scores, torch.Tensor) and not scores.is_cuda:
-        raise RuntimeError("pytracking_amd ops run on the MI355X only (got a CPU tensor)")
+        raise RuntimeError(CPU_TENSOR)
     if not checked and not encoder_covered(module, scores, feature):
         raise NotImplementedError("score encoder: eval mode, device fp32 4-D score maps, no grad, the structure of ResidualDS16SW_Clf, "
                                   "layer dims multiples of 16 up to 64")
@@ -213,7 +146,7 @@ def fuse_covered(fusion, seg_enc, clf_enc) -> bool:
 def fuse(fusion, seg_enc, clf_enc, checked=False):
     """fusion(seg_enc, bilinear resize of clf_enc to seg_enc's size), shaped as seg_enc; one launch."""
     if isinstance(seg_enc, torch.Tensor) and not seg_enc.is_cuda:
-        raise RuntimeError("pytracking_amd ops run on the MI355X only (got a CPU tensor)")
+        raise RuntimeError(CPU_TENSOR)
     if not checked and not fuse_covered(fusion, seg_enc, clf_enc):
         raise NotImplementedError("learners fusion: eval mode, device fp32 maps with equal leading dimensions, no grad, a LearnersFusion "
                                   "of type 'add' or 'concat' (Conv2d(2F, F, 3, padding=1)), F up to 64")
@@ -240,9 +173,7 @@ def segment_covered(net, target_filter, test_feat_tm, test_feat, encoded_clf_sco
     if target_filter.shape[0] != 1 or encoded_clf_scores.shape[1] != 1 or encoded_clf_scores.shape[2] != target_filter.shape[1]:
         return False                                           # more than one sequence, or not one encoding per target-model filter
     tens = [target_filter, test_feat_tm, encoded_clf_scores]
-    if not all(t.is_cuda and t.dtype == torch.float32 for t in tens):
-        return False
-    if torch.is_grad_enabled() and any(t.requires_grad for t in tens):
+    if not all(_dev_f32(t) for t in tens):
         return False
     return _fuse_ok(net.fusion_module, tens, (1, 1), target_filter.shape[1], test_feat_tm.shape[-2:], encoded_clf_scores.shape[-2:])
 
