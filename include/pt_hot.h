@@ -922,6 +922,60 @@ int pt_label_enc_f32(const float* masks, const float* pack, float* label_enc, fl
                      int c2, int f, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Box label encoders -- ResidualDS16FeatSWBox.forward and ResidualDS16FeatSWBoxCatMultiBlock.forward with use_gauss = False
+ * (ltr/models/lwl/label_encoder.py:58-216, ltr/models/rts/label_encoder.py:106-265), box_enc.hip: the box-to-mask initialisation of RTS
+ * (STAHelper.predict_mask) and of box-initialised LWL.  fp32, eval mode.  `boxes` (n, 4) = (x, y, w, h) fp32 on the DEVICE, read there:
+ * no host synchronisation.  `feat` (n, feat_dim, h, w) fp32 with dense channel planes and an image stride of feat_img_stride floats
+ * (>= feat_dim h w).  Every convolution is 3x3, padding 1, on the exact fp32 MFMA; no atomics and no split sums, so repeated calls are
+ * bit-identical; asynchronous on `stream`, no allocation, graph-capturable.
+ *
+ * The mask: v = int(b) truncates toward zero and the reference's int(v + 0.5) then maps a negative integer k to k + 1; the mask is 1 on
+ * rows range(H)[y : y + h] and columns range(W)[x : x + w] with Python's slice rules (a negative bound counts from the end, every bound
+ * is clipped to [0, len]); pt_box_enc clamps the two starts with max(0, .) first, pt_box_cat_enc does not.
+ * pt_box_slice (host only): that slice for integers, lo <= i < hi (empty where hi <= lo).  |start|, |extent|, len <= 2^29.
+ *
+ * pt_box_enc_f32:  mask (n,1,H,W), never stored -> the trunk of the mask label encoder above (stem, pool, BasicBlock(c0->c1, s2),
+ *   BasicBlock(c1->c2, s2)) -> (n,c2,h,w), h, w = H, W after four stride-2 stages, which must be the feature's size
+ *   -> res3 = BasicBlock(c2 + feat_dim -> c3, s1) over cat(trunk, feat) -- the concatenation is never written --
+ *   -> label_enc (n,f,h,w) = [relu](conv3x3(c3->f)) (relu iff final_relu) and sample_w (n,f,h,w) = conv3x3(c3->f).
+ *   `sample_w` may be NULL (a module with use_sample_w = False): that half is neither computed nor packed.  Eight launches.
+ *   `pack` (pt_box_enc_pack_floats floats, 16-byte aligned): the first five layers of pt_label_enc_f32's pack (stem ... res2.conv2), then
+ *       res3.conv1 | downsample   Cout = 2 c3,      Cin = feat_dim + c2   input channels ordered [feat | trunk] (the module's order is
+ *                                                                          [trunk | feat]: the packer permutes)
+ *       res3.conv2                Cout = c3,        Cin = c3
+ *       label_pred [| samp_w_pred] Cout = 2 f or f, Cin = c3
+ *   with the per-layer layout and arithmetic of pt_label_enc_f32 (tap-major weight | scale | shift; conv_without_bias(x) * scale + shift).
+ *   Covered: c0, c1, c2 multiples of 16 up to 64 and H, W <= 8192 (the label encoder's limits); c3, f multiples of 16 up to 128;
+ *   feat_dim a multiple of 16 up to 1024; h, w <= 1024; n <= 1024.
+ *
+ * pt_box_cat_enc_f32:  mask (n,1,H,W) resized to (n,1,h,w) (F.interpolate bilinear, align_corners = False: src = (dst + 0.5) in / out
+ *   - 0.5 clamped below at 0, second tap clamped at in - 1; the identity when (H, W) = (h, w)), evaluated from the box, one launch
+ *   -> nblocks BasicBlock(stride 1, biased 3x3 downsample, [BatchNorm]); the first over cat(feat, mask) (feat_dim + 1 channels)
+ *   -> label_enc (n,F,h,w) = [relu]([BN](conv3x3)).  dims = the nblocks block widths, then F.  1 + 2 nblocks + 1 launches.
+ *   `pack` (pt_box_cat_enc_pack_floats floats, 16-byte aligned): per block  conv1 | downsample (Cout = 2 d_b), conv2 (Cout = d_b), then
+ *   label_pred (Cout = F); layer layout as above, except that a weight's input channels are padded with zeros to the next multiple
+ *   of 16: weight (Cout, 3, 3, ceil16(Cin)).  The first block's Cin = feat_dim + 1 in the module's order [feat | mask].
+ *   Covered: nblocks 1..4; every dim a multiple of 16 up to 128; feat_dim a multiple of 16 up to 1024; H, W <= 8192; h, w, n <= 1024.
+ *
+ * Status: NULL pointer PT_ERR_NULL, non-positive size or an image stride below feat_dim h w PT_ERR_SHAPE, uncovered size (a feature size
+ * that is not the trunk's output size included) / misaligned pack PT_ERR_UNSUPPORTED, workspace too small or not 256-byte aligned
+ * PT_ERR_WORKSPACE -- in this order, all before anything is queued; one exception: nblocks > 4 is PT_ERR_UNSUPPORTED before the entries
+ * of `dims` are looked at (only nblocks + 1 of them are known to exist), so a non-positive dim behind too many blocks is not reported
+ * as PT_ERR_SHAPE.  The *_ws_bytes and *_pack_floats queries return 0 for what is not covered.
+ * ---------------------------------------------------------------------------------------------- */
+int pt_box_slice(int start, int extent, int len, int clamp_start, int* lo, int* hi);
+size_t pt_box_enc_pack_floats(int c0, int c1, int c2, int c3, int f, int feat_dim, int with_sample_w);
+size_t pt_box_enc_ws_bytes(int n, int H, int W, int h, int w, int c0, int c1, int c2, int c3, int f, int feat_dim);
+int pt_box_enc_f32(const float* boxes, const float* feat, long feat_img_stride, const float* pack, float* label_enc, float* sample_w,
+                   int n, int H, int W, int h, int w, int c0, int c1, int c2, int c3, int f, int feat_dim, int final_relu, void* ws,
+                   size_t ws_bytes, void* stream);
+size_t pt_box_cat_enc_pack_floats(int nblocks, const int* dims, int feat_dim);
+size_t pt_box_cat_enc_ws_bytes(int n, int H, int W, int h, int w, int nblocks, const int* dims, int feat_dim);
+int pt_box_cat_enc_f32(const float* boxes, const float* feat, long feat_img_stride, const float* pack, float* label_enc, int n, int H,
+                       int W, int h, int w, int nblocks, const int* dims, int feat_dim, int final_relu, void* ws, size_t ws_bytes,
+                       void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Segmentation decoder -- LWTLDecoder.forward (ltr/models/lwl/decoder.py:130-160) = RTSDecoder.forward (ltr/models/rts/decoder.py),
  * lwl_decoder.hip.  LWL and RTS run it once per frame (lwl_net.py segment_target) on the target-model scores and the backbone features.
  * fp32, eval mode, num_objects = None.

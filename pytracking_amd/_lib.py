@@ -9,8 +9,8 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PT_HOT_LIB", os.path.join(_HERE, "libpt_hot.so"))   # override: experiments only
-SOURCES = ["filter_kernels.hip", "fast_passes.hip", "sd_solver.hip", "mf_kernels.hip", "lwl_solver.hip", "atom_cg.hip", "atom_gn.hip", "tomp.hip", "localize.hip", "iou_refine.hip", "prroi.hip", "patch.hip", "frame_full.hip", "api.hip", "gn_hinge.hip", "tcm.hip", "kys.hip", "iou_feat.hip", "label_enc.hip", "lwl_decoder.hip", "rts_fusion.hip", "seg_readout.hip", "eco.hip"]
-HEADERS = ["common.h", "pt_internal.h", "rbuild.h", "sd_common.h", "mfma_gemm.h", "conv_tokens.h", "prroi_dev.h", "localize_dev.h", "frame_mid.h", "ds16_enc.h", os.path.join("..", "..", "include", "pt_hot.h")]
+SOURCES = ["filter_kernels.hip", "fast_passes.hip", "sd_solver.hip", "mf_kernels.hip", "lwl_solver.hip", "atom_cg.hip", "atom_gn.hip", "tomp.hip", "localize.hip", "iou_refine.hip", "prroi.hip", "patch.hip", "frame_full.hip", "api.hip", "gn_hinge.hip", "tcm.hip", "kys.hip", "iou_feat.hip", "label_enc.hip", "box_enc.hip", "lwl_decoder.hip", "rts_fusion.hip", "seg_readout.hip", "eco.hip"]
+HEADERS = ["common.h", "pt_internal.h", "rbuild.h", "sd_common.h", "mfma_gemm.h", "conv_tokens.h", "prroi_dev.h", "localize_dev.h", "frame_mid.h", "ds16_enc.h", "box_slice.h", os.path.join("..", "..", "include", "pt_hot.h")]
 # kernarg preload: leading scalar kernel parameters arrive in SGPRs at wave launch (kernels that take them that way only)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-pass-failed", "-mllvm", "-amdgpu-kernarg-preload-count=14"]
 
@@ -130,6 +130,8 @@ EXPORTS = [
     "pt_kys_cost_volume_ws_bytes", "pt_kys_cost_volume_f32", "pt_kys_weight_floats", "pt_kys_predict_ws_bytes", "pt_kys_predict_response_f32",
     "pt_iou_feat_pack_floats", "pt_iou_feat_ws_bytes", "pt_iou_feat_f32", "pt_mf_corr_tm_plan",
     "pt_label_enc_pack_floats", "pt_label_enc_ws_bytes", "pt_label_enc_f32",
+    "pt_box_enc_pack_floats", "pt_box_enc_ws_bytes", "pt_box_enc_f32",
+    "pt_box_cat_enc_pack_floats", "pt_box_cat_enc_ws_bytes", "pt_box_cat_enc_f32", "pt_box_slice",
     "pt_lwl_decoder_pack_floats", "pt_lwl_decoder_ws_bytes", "pt_lwl_decoder_f32",
     "pt_score_enc_pack_floats", "pt_score_enc_ws_bytes", "pt_score_enc_f32", "pt_learners_fuse_pack_floats", "pt_learners_fuse_f32",
     "pt_seg_readout_ws_bytes", "pt_seg_readout_f32", "pt_seg_state_ws_bytes", "pt_seg_state_f32", "pt_seg_merge_ws_bytes", "pt_seg_merge_f32",
@@ -479,6 +481,20 @@ def lib():
     L.pt_label_enc_f32.restype = i
     L.pt_label_enc_f32.argtypes = [vp] * 4 + [i] * 7 + [vp, sz, vp]
     ip = ctypes.POINTER(ctypes.c_int)
+    L.pt_box_slice.restype = i
+    L.pt_box_slice.argtypes = [i] * 4 + [ip, ip]
+    L.pt_box_enc_pack_floats.restype = sz
+    L.pt_box_enc_pack_floats.argtypes = [i] * 7
+    L.pt_box_enc_ws_bytes.restype = sz
+    L.pt_box_enc_ws_bytes.argtypes = [i] * 11
+    L.pt_box_enc_f32.restype = i
+    L.pt_box_enc_f32.argtypes = [vp, vp, ctypes.c_long, vp, vp, vp] + [i] * 12 + [vp, sz, vp]
+    L.pt_box_cat_enc_pack_floats.restype = sz
+    L.pt_box_cat_enc_pack_floats.argtypes = [i, ip, i]
+    L.pt_box_cat_enc_ws_bytes.restype = sz
+    L.pt_box_cat_enc_ws_bytes.argtypes = [i] * 6 + [ip, i]
+    L.pt_box_cat_enc_f32.restype = i
+    L.pt_box_cat_enc_f32.argtypes = [vp, vp, ctypes.c_long, vp, vp] + [i] * 6 + [ip] + [i] * 2 + [vp, sz, vp]
     L.pt_lwl_decoder_pack_floats.restype = sz
     L.pt_lwl_decoder_pack_floats.argtypes = [i, ip, i, i, i]
     L.pt_lwl_decoder_ws_bytes.restype = sz

@@ -417,6 +417,41 @@ extern "C" int pt_label_enc_f32(const float* masks, const float* pack, float* la
     return pt_label_enc_impl(masks, pack, label_enc, sample_w, n, H, W, c0, c1, c2, f, ws, ws_bytes, (hipStream_t)stream);
 }
 
+// box label encoders: ResidualDS16FeatSWBox.forward and ResidualDS16FeatSWBoxCatMultiBlock.forward (box_enc.hip)
+extern "C" int pt_box_slice(int start, int extent, int len, int clamp_start, int* lo, int* hi) {
+    return pt_box_slice_impl(start, extent, len, clamp_start, lo, hi);
+}
+
+extern "C" size_t pt_box_enc_pack_floats(int c0, int c1, int c2, int c3, int f, int feat_dim, int with_sample_w) {
+    return pt_box_enc_pack_floats_impl(c0, c1, c2, c3, f, feat_dim, with_sample_w);
+}
+
+extern "C" size_t pt_box_enc_ws_bytes(int n, int H, int W, int h, int w, int c0, int c1, int c2, int c3, int f, int feat_dim) {
+    return pt_box_enc_ws_bytes_impl(n, H, W, h, w, c0, c1, c2, c3, f, feat_dim);
+}
+
+extern "C" int pt_box_enc_f32(const float* boxes, const float* feat, long feat_img_stride, const float* pack, float* label_enc,
+                              float* sample_w, int n, int H, int W, int h, int w, int c0, int c1, int c2, int c3, int f, int feat_dim,
+                              int final_relu, void* ws, size_t ws_bytes, void* stream) {
+    return pt_box_enc_impl(boxes, feat, feat_img_stride, pack, label_enc, sample_w, n, H, W, h, w, c0, c1, c2, c3, f, feat_dim, final_relu,
+                           ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" size_t pt_box_cat_enc_pack_floats(int nblocks, const int* dims, int feat_dim) {
+    return pt_box_cat_enc_pack_floats_impl(nblocks, dims, feat_dim);
+}
+
+extern "C" size_t pt_box_cat_enc_ws_bytes(int n, int H, int W, int h, int w, int nblocks, const int* dims, int feat_dim) {
+    return pt_box_cat_enc_ws_bytes_impl(n, H, W, h, w, nblocks, dims, feat_dim);
+}
+
+extern "C" int pt_box_cat_enc_f32(const float* boxes, const float* feat, long feat_img_stride, const float* pack, float* label_enc, int n,
+                                  int H, int W, int h, int w, int nblocks, const int* dims, int feat_dim, int final_relu, void* ws,
+                                  size_t ws_bytes, void* stream) {
+    return pt_box_cat_enc_impl(boxes, feat, feat_img_stride, pack, label_enc, n, H, W, h, w, nblocks, dims, feat_dim, final_relu, ws,
+                               ws_bytes, (hipStream_t)stream);
+}
+
 // RTS instance-score encoder (ResidualDS16SW_Clf.forward) and learners fusion (rts_fusion.hip)
 extern "C" size_t pt_score_enc_pack_floats(int c0, int c1, int c2, int f) { return pt_score_enc_pack_floats_impl(c0, c1, c2, f); }
 

@@ -1,5 +1,6 @@
-// Host side shared by the two DS16 encoders -- ResidualDS16SW (label_enc.hip, stride 2) and ResidualDS16SW_Clf (rts_fusion.hip, stride 1):
-// one network at two strides, so one plan (pack layout, map sizes, workspace layout) and one driver (argument checks, then the chain
+// Host side shared by the DS16 encoders -- ResidualDS16SW (label_enc.hip, stride 2), ResidualDS16SW_Clf (rts_fusion.hip, stride 1) and the
+// mask trunk of ResidualDS16FeatSWBox (box_enc.hip through label_enc.hip, stride 2): one network at two strides, so one plan (pack
+// layout, map sizes, workspace layout) and one driver (argument checks, then the chain
 // stem -> conv1|downsample -> conv2 + residual -> conv1|downsample -> conv2 + residual -> label_pred|samp_w_pred).  The kernels, their
 // argument structs and the tile choice stay with each source: the driver describes a convolution as a Ds16Conv and hands it to the
 // launcher the source supplies.
@@ -71,6 +72,47 @@ static inline size_t ds16_ws_bytes(int stride, const Ds16Limits& lim, int n, int
     return ds16_plan(stride, lim, n, H, W, c0, c1, c2, f, &p) == PT_OK ? p.ws_floats * sizeof(float) : 0;
 }
 
+// One convolution of the chain as a Ds16Conv: layer k of the plan from map level `level_in` to `level_out`, reading `src`.
+static inline Ds16Conv ds16_layer(const Ds16Plan& p, int stride, const float* pack, int k, int level_in, int level_out, const float* src,
+                                  int src_channels) {
+    const Ds16Layer& L = p.conv[k];
+    Ds16Conv a{};
+    a.in = src; a.in_img = (long)src_channels * p.H[level_in] * p.W[level_in];
+    a.w = pack + L.w_off; a.scale = pack + L.s_off; a.shift = pack + L.b_off;
+    a.Cin = L.Cin; a.Cout = L.Cout;
+    a.Hi = p.H[level_in]; a.Wi = p.W[level_in]; a.Ho = p.H[level_out]; a.Wo = p.W[level_out];
+    a.stride = level_in == level_out ? 1 : stride;
+    a.csplit = L.Cout; a.out0_img = (long)L.Cout * a.Ho * a.Wo;
+    return a;
+}
+
+// The trunk of a checked plan: stem, then the two BasicBlocks (five launches); the result is (n, C2, H[4], W[4]) at base + p.r2.  The
+// pack needs no more than its first `ds16_trunk_pack_floats` floats (the heads' layer comes last).  Used by ds16_encode below and, on
+// its own, by the box label encoder (box_enc.hip), whose heads sit behind a third block.
+template <class Stem, class Conv>
+int ds16_trunk(int stride, const Ds16Plan& p, const float* pack, float* base, Stem stem, Conv conv) {
+    int rc;
+    const int n = p.n, c0 = p.C[0], c1 = p.C[1], c2 = p.C[2];
+    if ((rc = stem(p, pack, base + p.s0))) return rc;
+    const long hw3 = (long)p.H[3] * p.W[3], hw4 = (long)p.H[4] * p.W[4];
+    // block 1: conv1 | downsample as one convolution with 2 C1 outputs (ReLU on the conv1 half), then conv2 + residual + ReLU
+    Ds16Conv a = ds16_layer(p, stride, pack, 0, 2, 3, base + p.s0, c0);
+    a.out0 = base + p.t1; a.relu_n = c1;
+    if ((rc = conv(a, n))) return rc;
+    a = ds16_layer(p, stride, pack, 1, 3, 3, base + p.t1, 2 * c1);
+    a.res = base + p.t1 + c1 * hw3; a.res_img = 2 * c1 * hw3; a.out0 = base + p.r1; a.relu_n = c1;
+    if ((rc = conv(a, n))) return rc;
+    // block 2
+    a = ds16_layer(p, stride, pack, 2, 3, 4, base + p.r1, c1);
+    a.out0 = base + p.t2; a.relu_n = c2;
+    if ((rc = conv(a, n))) return rc;
+    a = ds16_layer(p, stride, pack, 3, 4, 4, base + p.t2, 2 * c2);
+    a.res = base + p.t2 + c2 * hw4; a.res_img = 2 * c2 * hw4; a.out0 = base + p.r2; a.relu_n = c2;
+    return conv(a, n);
+}
+
+static inline size_t ds16_trunk_pack_floats(const Ds16Plan& p) { return p.conv[4].w_off; }
+
 // Checks everything before anything is queued, then runs the six launches.  `stem(plan, pack, out)` launches the source's stem kernel into
 // the workspace, `conv(a, n)` one convolution; both return a PT_* code.  `sample_w_optional`: a null sample_w is allowed and skips that
 // half of the heads (only label_pred's F channels -- the leading rows of the weights, scales and shifts -- are computed).
@@ -86,36 +128,16 @@ int ds16_encode(int stride, const Ds16Limits& lim, bool sample_w_optional, const
         if ((uintptr_t)q % 4) return PT_ERR_UNSUPPORTED;
     if (ws_bytes < p.ws_floats * sizeof(float) || ((uintptr_t)ws % 256) != 0) return PT_ERR_WORKSPACE;
     float* base = (float*)ws;
-    if ((rc = stem(p, pack, base + p.s0))) return rc;
-    auto layer = [&](int k, int level_in, int level_out, const float* src, int src_channels) {
-        const Ds16Layer& L = p.conv[k];
-        Ds16Conv a{};
-        a.in = src; a.in_img = (long)src_channels * p.H[level_in] * p.W[level_in];
-        a.w = pack + L.w_off; a.scale = pack + L.s_off; a.shift = pack + L.b_off;
-        a.Cin = L.Cin; a.Cout = L.Cout;
-        a.Hi = p.H[level_in]; a.Wi = p.W[level_in]; a.Ho = p.H[level_out]; a.Wo = p.W[level_out];
-        a.stride = level_in == level_out ? 1 : stride;
-        a.csplit = L.Cout; a.out0_img = (long)L.Cout * a.Ho * a.Wo;
-        return a;
-    };
-    const long hw3 = (long)p.H[3] * p.W[3], hw4 = (long)p.H[4] * p.W[4];
-    // block 1: conv1 | downsample as one convolution with 2 C1 outputs (ReLU on the conv1 half), then conv2 + residual + ReLU
-    Ds16Conv a = layer(0, 2, 3, base + p.s0, c0);
-    a.out0 = base + p.t1; a.relu_n = c1;
-    if ((rc = conv(a, n))) return rc;
-    a = layer(1, 3, 3, base + p.t1, 2 * c1);
-    a.res = base + p.t1 + c1 * hw3; a.res_img = 2 * c1 * hw3; a.out0 = base + p.r1; a.relu_n = c1;
-    if ((rc = conv(a, n))) return rc;
-    // block 2
-    a = layer(2, 3, 4, base + p.r1, c1);
-    a.out0 = base + p.t2; a.relu_n = c2;
-    if ((rc = conv(a, n))) return rc;
-    a = layer(3, 4, 4, base + p.t2, 2 * c2);
-    a.res = base + p.t2 + c2 * hw4; a.res_img = 2 * c2 * hw4; a.out0 = base + p.r2; a.relu_n = c2;
-    if ((rc = conv(a, n))) return rc;
+    if ((rc = ds16_trunk(stride, p, pack, base, stem, conv))) return rc;
     // heads: label_pred | samp_w_pred as one convolution with 2 F outputs, ReLU on label_pred's half, written to the two results
-    a = layer(4, 4, 4, base + p.r2, c2);
+    const long hw4 = (long)p.H[4] * p.W[4];
+    Ds16Conv a = ds16_layer(p, stride, pack, 4, 4, 4, base + p.r2, c2);
     if (!sample_w) a.Cout = f;
     a.csplit = f; a.out0 = label_enc; a.out0_img = f * hw4; a.out1 = sample_w; a.out1_img = f * hw4; a.relu_n = f;
     return conv(a, n);
 }
+
+// The stride-2 mask trunk fed from boxes instead of masks (label_enc.hip: k_le_stem<true> and k_le_conv), for box_enc.hip.  `plan` checks
+// the sizes against the label encoder's limits and lays the workspace out; `launch` queues the five launches of a checked plan.
+int pt_le_box_trunk_plan(int n, int H, int W, int c0, int c1, int c2, Ds16Plan* p);
+int pt_le_box_trunk_launch(const float* boxes, const float* pack, const Ds16Plan& p, float* ws, hipStream_t st);

@@ -27,6 +27,7 @@
 #include "common.h"
 #include "pt_internal.h"
 #include "ds16_enc.h"
+#include "box_slice.h"
 
 namespace {
 
@@ -35,17 +36,27 @@ constexpr Ds16Limits LE_LIMITS{LE_MAX_C, LE_MAX_DIM, LE_MAX_N};
 constexpr int ST_TH = 4, ST_TW = 32, ST_THREADS = ST_TH * ST_TW;
 constexpr int ST_LR = 4 * ST_TH + 3, ST_LC = 4 * ST_TW + 4;              // LDS tile: origin row 4*py0 - 3, origin column 4*px0 - 4
 
-// grid (ceil(W2/32), ceil(H2/4), n), 128 threads
+// grid (ceil(W2/32), ceil(H2/4), n), 128 threads.  BOX: `mask` holds n boxes (x, y, w, h) instead of n masks and the tile is filled with
+// the binary mask ResidualDS16FeatSWBox.bbox_to_mask writes (box_slice.h; starts clamped at 0); nothing of image size is loaded or stored.
+template <bool BOX>
 __global__ __launch_bounds__(ST_THREADS) void k_le_stem(const float* __restrict__ mask, const float* __restrict__ w,
                                                         const float* __restrict__ scale, const float* __restrict__ shift,
                                                         float* __restrict__ out, int C0, int H, int W, int H1, int W1, int H2, int W2) {
     __shared__ __attribute__((aligned(16))) float tile[ST_LR * ST_LC];
     const int img = blockIdx.z, py0 = blockIdx.y * ST_TH, px0 = blockIdx.x * ST_TW;
-    const float* src = mask + (long)img * H * W;
     const int r0 = 4 * py0 - 3, c0 = 4 * px0 - 4;
-    for (int e = threadIdx.x; e < ST_LR * ST_LC; e += ST_THREADS) {
-        const int r = e / ST_LC, c = e - r * ST_LC, iy = r0 + r, ix = c0 + c;
-        tile[e] = (iy >= 0 && iy < H && ix >= 0 && ix < W) ? src[(long)iy * W + ix] : 0.f;
+    if constexpr (BOX) {
+        const PtBoxRect box = pt_box_rect(mask + 4 * (long)img, H, W, true);         // inside [0, W] x [0, H]
+        for (int e = threadIdx.x; e < ST_LR * ST_LC; e += ST_THREADS) {
+            const int r = e / ST_LC, c = e - r * ST_LC, iy = r0 + r, ix = c0 + c;
+            tile[e] = (iy >= box.y0 && iy < box.y1 && ix >= box.x0 && ix < box.x1) ? 1.f : 0.f;
+        }
+    } else {
+        const float* src = mask + (long)img * H * W;
+        for (int e = threadIdx.x; e < ST_LR * ST_LC; e += ST_THREADS) {
+            const int r = e / ST_LC, c = e - r * ST_LC, iy = r0 + r, ix = c0 + c;
+            tile[e] = (iy >= 0 && iy < H && ix >= 0 && ix < W) ? src[(long)iy * W + ix] : 0.f;
+        }
     }
     __syncthreads();
     const int lx = threadIdx.x % ST_TW, ly = threadIdx.x / ST_TW, py = py0 + ly, px = px0 + lx;
@@ -198,22 +209,44 @@ size_t pt_label_enc_ws_bytes_impl(int n, int H, int W, int c0, int c1, int c2, i
     return ds16_ws_bytes(2, LE_LIMITS, n, H, W, c0, c1, c2, f);
 }
 
+namespace {
+
+template <bool BOX>
+int le_stem(const float* in, const Ds16Plan& p, const float* pk, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(k_le_stem<BOX>, dim3(pt_ceil_div(p.W[2], ST_TW), pt_ceil_div(p.H[2], ST_TH), p.n), dim3(ST_THREADS), 0, st, in,
+                       pk + p.stem.w_off, pk + p.stem.s_off, pk + p.stem.b_off, out, p.C[0], p.H[0], p.W[0], p.H[1], p.W[1], p.H[2], p.W[2]);
+    PT_CHECK_LAUNCH();
+    return PT_OK;
+}
+
+int le_conv_ds16(const Ds16Conv& c, int images, hipStream_t st) {
+    LeConv a{};
+    a.in = c.in; a.in_img = c.in_img;
+    a.w = c.w; a.scale = c.scale; a.shift = c.shift;
+    a.res = c.res; a.res_img = c.res_img;
+    a.out0 = c.out0; a.out0_img = c.out0_img; a.out1 = c.out1; a.out1_img = c.out1_img;
+    a.csplit = c.csplit; a.Cin = c.Cin; a.Cout = c.Cout; a.Hi = c.Hi; a.Wi = c.Wi; a.Ho = c.Ho; a.Wo = c.Wo; a.relu_n = c.relu_n;
+    return le_conv(a, c.stride, images, st);
+}
+
+}  // namespace
+
 int pt_label_enc_impl(const float* masks, const float* pack, float* label_enc, float* sample_w, int n, int H, int W, int c0, int c1,
                       int c2, int f, void* ws, size_t ws_bytes, hipStream_t st) {
-    auto stem = [&](const Ds16Plan& p, const float* pk, float* out) -> int {
-        hipLaunchKernelGGL(k_le_stem, dim3(pt_ceil_div(p.W[2], ST_TW), pt_ceil_div(p.H[2], ST_TH), n), dim3(ST_THREADS), 0, st, masks,
-                           pk + p.stem.w_off, pk + p.stem.s_off, pk + p.stem.b_off, out, c0, H, W, p.H[1], p.W[1], p.H[2], p.W[2]);
-        PT_CHECK_LAUNCH();
-        return PT_OK;
-    };
-    auto conv = [&](const Ds16Conv& c, int images) {
-        LeConv a{};
-        a.in = c.in; a.in_img = c.in_img;
-        a.w = c.w; a.scale = c.scale; a.shift = c.shift;
-        a.res = c.res; a.res_img = c.res_img;
-        a.out0 = c.out0; a.out0_img = c.out0_img; a.out1 = c.out1; a.out1_img = c.out1_img;
-        a.csplit = c.csplit; a.Cin = c.Cin; a.Cout = c.Cout; a.Hi = c.Hi; a.Wi = c.Wi; a.Ho = c.Ho; a.Wo = c.Wo; a.relu_n = c.relu_n;
-        return le_conv(a, c.stride, images, st);
-    };
+    auto stem = [&](const Ds16Plan& p, const float* pk, float* out) { return le_stem<false>(masks, p, pk, out, st); };
+    auto conv = [&](const Ds16Conv& c, int images) { return le_conv_ds16(c, images, st); };
     return ds16_encode(2, LE_LIMITS, false, masks, pack, label_enc, sample_w, n, H, W, c0, c1, c2, f, ws, ws_bytes, stem, conv);
+}
+
+// The mask trunk of ResidualDS16FeatSWBox for box_enc.hip: the plan of the (c0, c1, c2) trunk on n H x W images (the heads' slot of the
+// plan is filled with c2 and not used), and the five launches from the boxes; `ws` holds p.ws_floats floats, the trunk output
+// (n, c2, H[4], W[4]) ends at ws + p.r2.  The caller has checked its arguments.
+int pt_le_box_trunk_plan(int n, int H, int W, int c0, int c1, int c2, Ds16Plan* p) {
+    return ds16_plan(2, LE_LIMITS, n, H, W, c0, c1, c2, c2, p);
+}
+
+int pt_le_box_trunk_launch(const float* boxes, const float* pack, const Ds16Plan& p, float* ws, hipStream_t st) {
+    auto stem = [&](const Ds16Plan& q, const float* pk, float* out) { return le_stem<true>(boxes, q, pk, out, st); };
+    auto conv = [&](const Ds16Conv& c, int images) { return le_conv_ds16(c, images, st); };
+    return ds16_trunk(2, p, pack, ws, stem, conv);
 }

@@ -241,6 +241,19 @@ size_t pt_label_enc_ws_bytes_impl(int n, int H, int W, int c0, int c1, int c2, i
 int pt_label_enc_impl(const float* masks, const float* pack, float* label_enc, float* sample_w, int n, int H, int W, int c0, int c1,
                       int c2, int f, void* ws, size_t ws_bytes, hipStream_t stream);
 
+// box label encoders (box_enc.hip); exported as pt_box_enc_* / pt_box_cat_enc_* / pt_box_slice by api.hip
+int pt_box_slice_impl(int start, int extent, int len, int clamp_start, int* lo, int* hi);
+size_t pt_box_enc_pack_floats_impl(int c0, int c1, int c2, int c3, int f, int feat_dim, int with_sw);
+size_t pt_box_enc_ws_bytes_impl(int n, int H, int W, int h, int w, int c0, int c1, int c2, int c3, int f, int feat_dim);
+int pt_box_enc_impl(const float* boxes, const float* feat, long feat_img, const float* pack, float* label_enc, float* sample_w, int n,
+                    int H, int W, int h, int w, int c0, int c1, int c2, int c3, int f, int feat_dim, int final_relu, void* ws,
+                    size_t ws_bytes, hipStream_t stream);
+size_t pt_box_cat_enc_pack_floats_impl(int nblocks, const int* dims, int feat_dim);
+size_t pt_box_cat_enc_ws_bytes_impl(int n, int H, int W, int h, int w, int nblocks, const int* dims, int feat_dim);
+int pt_box_cat_enc_impl(const float* boxes, const float* feat, long feat_img, const float* pack, float* label_enc, int n, int H, int W,
+                        int h, int w, int nblocks, const int* dims, int feat_dim, int final_relu, void* ws, size_t ws_bytes,
+                        hipStream_t stream);
+
 // RTS instance-score encoder and learners fusion (rts_fusion.hip); exported as pt_score_enc_* / pt_learners_fuse_* by api.hip
 size_t pt_score_enc_pack_floats_impl(int c0, int c1, int c2, int f);
 size_t pt_score_enc_ws_bytes_impl(int n, int H, int W, int c0, int c1, int c2, int f);

@@ -46,6 +46,9 @@ What gets rebound (import path = contract; nothing in the reference tree is edit
   ltr.models.lwl.label_encoder.ResidualDS16SW.forward, ltr.models.rts.label_encoder.ResidualDS16SW.forward
                                                   (mask label encoder; only with install(label_encoder=True))
                                                                                       -> pytracking_amd.label_encoder
+  ltr.models.{lwl,rts}.label_encoder.ResidualDS16FeatSWBox.forward, ...ResidualDS16FeatSWBoxCatMultiBlock.forward
+                                                  (box label encoders of the first frame; only with install(box_encoder=True))
+                                                                                      -> pytracking_amd.box_encoder
   ltr.models.lwl.decoder.LWTLDecoder.forward, ltr.models.rts.decoder.RTSDecoder.forward
                                                   (segmentation decoder, decoder.py:130-160; only with install(decoder=True))
                                                                                       -> pytracking_amd.lwl_decoder
@@ -686,6 +689,24 @@ def _install_label_encoder():
                                             name + ": call outside the gfx950 hot path"))
 
 
+def _install_box_encoder():
+    """`ResidualDS16FeatSWBox.forward` and `ResidualDS16FeatSWBoxCatMultiBlock.forward` of LWL and of RTS (label_encoder.py:108-126 and
+    :188-216, the same code in both packages): the box is rasterised on the device, the mask trunk or the resized mask plane and the
+    blocks over feature + mask encoding run without a concatenated map.  CPU tensors, use_gauss=True, training mode, grad-enabled calls,
+    a `bb` of the wrong rank, modules of another structure and uncovered dims keep the reference's code.  Off unless
+    `install(box_encoder=True)`: the set a default install() rebinds is pinned."""
+    from . import box_encoder as _be
+    for modname in ("ltr.models.lwl.label_encoder", "ltr.models.rts.label_encoder"):
+        for clsname in (_be.BOX, _be.CAT):
+            try:
+                cls = getattr(importlib.import_module(modname), clsname)
+            except Exception:
+                continue
+            name = clsname + ".forward"
+            _rebind(cls, "forward", _dispatcher(cls.forward, name, _be.covered, functools.partial(_be.forward, checked=True),
+                                                name + ": call outside the gfx950 hot path"))
+
+
 def _install_lwl_decoder():
     """`LWTLDecoder.forward` (ltr/models/lwl/decoder.py:130-160) and `RTSDecoder.forward` (ltr/models/rts/decoder.py, the same code): all
     levels (TSE, RRB, CAB, RRB) and the Upsampler in one asynchronous call.  CPU tensors, training mode, grad-enabled calls, multi-object
@@ -931,7 +952,7 @@ def _install_atom_cg():
 
 def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=True, iou_refine=True, preprocessing=True,
             candidate_matching=True, kys=True, iou_feat=False, label_encoder=False, decoder=False, feature_heads=False,
-            rts_fusion=False, seg_readout=False, eco=False, tamos=False):
+            rts_fusion=False, seg_readout=False, eco=False, tamos=False, box_encoder=False):
     """Rebind the boundary symbols.  Call after the reference is importable (`sys.path`) and before networks or
     trackers are constructed.  Idempotent.  If an installer raises, what was rebound so far is undone before the exception
     propagates (an optional reference module that does not import is not a failure: its family is skipped)."""
@@ -953,7 +974,8 @@ def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=T
                                 (candidate_matching, _install_candidate_matching), (kys, _install_kys), (atom_cg, _install_atom_cg),
                                 (iou_feat, _install_iou_feat), (label_encoder, _install_label_encoder),
                                 (decoder, _install_lwl_decoder), (rts_fusion, _install_rts_fusion),
-                                (seg_readout, _install_seg_readout), (eco, _install_eco), (tamos, _install_tamos)):
+                                (seg_readout, _install_seg_readout), (eco, _install_eco), (tamos, _install_tamos),
+                                (box_encoder, _install_box_encoder)):
             if flag:
                 installer()
     except BaseException:

@@ -822,3 +822,109 @@ def eco_series(seed, S, c, Hf, Wh, decay=0.35):
     flip = col[:, :, ::-1, :] * np.array([1.0, -1.0])
     a[:, :, :, 0, :] = 0.5 * (col + flip)
     return a.astype(np.float32)
+
+
+# Box label encoders (ltr/models/lwl/label_encoder.py:58-216, ltr/models/rts/label_encoder.py:106-265), use_gauss = False.
+# ResidualDS16FeatSWBox: dims = (c0, c1, c2, c3, F); the feature map has the trunk's output size (four stride-2 stages of `image`).
+BOX_ENC_DIMS = (16, 32, 64, 128, 16)    # sta_net.py:137-142, rts_net.py:546-553: label_encoder_dims + (num_filters,)
+BOX_ENC_CASES = {
+    "one": dict(n=1, image=(7, 9), dims=(16, 16, 32, 32, 16), feat_dim=16, boxes=[(2, 1, 4, 3)]),       # 1 x 1 map: every tap but the centre is padding
+    "odd": dict(n=3, image=(33, 50), dims=BOX_ENC_DIMS, feat_dim=48,                                      # 3 x 4 map, Cin = 112, per-image indexing
+                boxes=[(10.7, 5.2, 20.9, 15.1), (-6.5, -4.2, 20.3, 18.8), (-3, -2, 80, 60)]),            # inside; left of / above; everything
+    "ragged": dict(n=2, image=(40, 72), dims=(16, 16, 32, 48, 32), feat_dim=80, boxes=[(30, 10, 25, 20), (5.5, 20.5, 40, 12)]),
+    "edge": dict(n=1, image=(70, 260), dims=(16, 32, 64, 80, 16), feat_dim=32, boxes=[(200, 40, 100, 50)]),   # 5 x 17 map; past right / bottom
+    "wrap": dict(n=2, image=(33, 50), dims=BOX_ENC_DIMS, feat_dim=32, boxes=[(5, -30, 20, 10), (-40, 3, 15, 20)]),   # negative stops
+    "nosw": dict(n=2, image=(33, 50), dims=BOX_ENC_DIMS, feat_dim=32, use_sample_w=False, boxes=[(12, 8, 20, 14), (30, 2, 15, 28)]),
+    "bn": dict(n=2, image=(40, 72), dims=BOX_ENC_DIMS, feat_dim=32, use_bn=True, final_relu=False, boxes=[(20, 10, 30, 20), (-5, 15, 40, 40)]),
+    "deployed": dict(n=1, image=(480, 832), dims=BOX_ENC_DIMS, feat_dim=512, boxes=[(301.4, 151.7, 190.2, 222.9)]),
+    "deployed2": dict(n=2, image=(480, 832), dims=BOX_ENC_DIMS, feat_dim=512, boxes=[(301.4, 151.7, 190.2, 222.9), (-20.5, 300.2, 400.6, 250.3)]),
+}
+# ResidualDS16FeatSWBoxCatMultiBlock: dims = the block widths, then F; `feat` = (h, w) of the feature map, any size.
+BOX_CAT_ENC_CASES = {
+    "one": dict(n=1, image=(7, 9), feat=(1, 1), dims=(16, 16), feat_dim=16, boxes=[(4, 3, 4, 3)]),     # the one sample (row 3, column 4) is the box's corner
+    "odd": dict(n=3, image=(33, 50), feat=(3, 4), dims=(64, 64, 16), feat_dim=48,                         # a non-integer resize ratio
+                boxes=[(10.7, 5.2, 20.9, 15.1), (-6.5, -4.2, 20.3, 18.8), (0, 0, 80, 60)]),
+    "ragged": dict(n=2, image=(40, 72), feat=(5, 7), dims=(48, 32), feat_dim=80, boxes=[(30, 10, 25, 20), (5.5, 20.5, 40, 12)]),
+    "edge": dict(n=1, image=(70, 260), feat=(5, 17), dims=(80, 16), feat_dim=32, boxes=[(206, 40, 100, 50)]),     # column 206 is a resize tap
+    "wrap": dict(n=3, image=(33, 50), feat=(5, 7), dims=(32, 16), feat_dim=32,                            # negative stop; negative start; both (empty)
+                 boxes=[(5, -30, 20, 10), (-45, 3, 15, 20), (-10, 4, 25, 10)]),
+    "same": dict(n=2, image=(6, 9), feat=(6, 9), dims=(32, 16), feat_dim=16, boxes=[(2, 1, 4, 3), (-3, 2, 5, 3)]),   # the resize is the identity
+    "blocks1": dict(n=2, image=(40, 72), feat=(6, 10), dims=(32, 16), feat_dim=32, final_relu=False, final_bn=False, boxes=[(20, 10, 30, 20), (3, 15, 40, 20)]),
+    "blocks3": dict(n=2, image=(40, 72), feat=(6, 10), dims=(32, 48, 16, 16), feat_dim=32, boxes=[(20, 10, 30, 20), (3, 15, 40, 20)]),
+    "deployed": dict(n=1, image=(480, 832), feat=(30, 52), dims=(64, 64, 16), feat_dim=512, final_bn=False,    # lwl_boxinit.py:90-95, lwl_box_net.py:169-173
+                     boxes=[(301.4, 151.7, 190.2, 222.9)]),
+}
+_BOX_ENC_DEFAULTS = dict(use_bn=False, use_sample_w=True, final_relu=True)
+_BOX_CAT_ENC_DEFAULTS = dict(use_bn=True, final_relu=True, final_bn=True)
+
+
+def box_enc_case(name):
+    """BOX_ENC_CASES[name] with the defaults filled in and `feat` = the trunk's output size."""
+    c = dict(_BOX_ENC_DEFAULTS, **BOX_ENC_CASES[name])
+    h, w = c["image"]
+    for _ in range(4):
+        h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    c["feat"] = (h, w)
+    return c
+
+
+def box_cat_enc_case(name):
+    return dict(_BOX_CAT_ENC_DEFAULTS, **BOX_CAT_ENC_CASES[name])
+
+
+def _box_enc_layers(rng, sd, use_bn):
+    def conv(name, i, o, bias):
+        sd[name + ".weight"] = (rng.standard_normal((o, i, 3, 3), dtype=np.float32) * np.float32(np.sqrt(2.0 / (9 * i)))).astype(np.float32)
+        if bias:
+            sd[name + ".bias"] = (rng.standard_normal(o, dtype=np.float32) * np.float32(0.1)).astype(np.float32)
+
+    def bn(name, o, on=use_bn):
+        if not on:
+            return
+        sd[name + ".weight"] = rng.uniform(0.5, 1.5, o).astype(np.float32)
+        sd[name + ".bias"] = (rng.standard_normal(o) * 0.1).astype(np.float32)
+        sd[name + ".running_mean"] = (rng.standard_normal(o) * 0.2).astype(np.float32)
+        sd[name + ".running_var"] = rng.uniform(0.5, 2.0, o).astype(np.float32)
+        sd[name + ".num_batches_tracked"] = np.array(100, dtype=np.int64)
+
+    def block(name, i, o):
+        conv(name + ".conv1", i, o, False); bn(name + ".bn1", o)
+        conv(name + ".conv2", o, o, False); bn(name + ".bn2", o)
+        conv(name + ".downsample", i, o, True)
+
+    return conv, bn, block
+
+
+def box_enc_state(seed, dims=BOX_ENC_DIMS, feat_dim=512, use_bn=False, use_sample_w=True):
+    """A state dict (numpy, float32) of a ResidualDS16FeatSWBox(dims, feat_dim, use_bn=..., use_sample_w=...): kaiming (fan-in) weights,
+    non-zero biases, a non-zero samp_w_pred.weight and BatchNorm statistics away from their defaults.  label_pred is a conv_block with
+    its default BatchNorm whatever use_bn says (the class does not pass the flag on)."""
+    rng = np.random.default_rng(seed)
+    c0, c1, c2, c3, f = dims
+    sd = {}
+    conv, bn, block = _box_enc_layers(rng, sd, use_bn)
+    conv("conv_block.0", 1, c0, True); bn("conv_block.1", c0)
+    block("res1", c0, c1); block("res2", c1, c2); block("res3", c2 + feat_dim, c3)
+    conv("label_pred.0", c3, f, True); bn("label_pred.1", f, True)
+    if use_sample_w:
+        conv("samp_w_pred", c3, f, True)
+    return sd
+
+
+def box_cat_enc_state(seed, dims=(64, 64, 16), feat_dim=512, use_bn=True, final_bn=True):
+    """A state dict (numpy, float32) of a ResidualDS16FeatSWBoxCatMultiBlock(dims, feat_dim, use_bn=..., final_bn=...)."""
+    rng = np.random.default_rng(seed)
+    sd = {}
+    conv, bn, block = _box_enc_layers(rng, sd, use_bn)
+    cin = feat_dim + 1
+    for k, c in enumerate(dims[:-1]):
+        block(f"res.{k}", cin, c)
+        cin = c
+    conv("label_pred.0", cin, dims[-1], True); bn("label_pred.1", dims[-1], final_bn)
+    return sd
+
+
+def box_enc_feat(seed, n, feat_dim, h, w):
+    """(n, feat_dim, h, w) float32 target-model features: rectified, roughly unit scale, as the feature head leaves them."""
+    rng = np.random.default_rng(seed)
+    return np.maximum(rng.standard_normal((n, feat_dim, h, w), dtype=np.float32), np.float32(0.0)) * np.float32(0.5)
