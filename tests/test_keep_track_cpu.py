@@ -1,7 +1,11 @@
 """KeepTrack target-candidate matching (pytracking_amd.candidate_matching, tcm.hip) without a GPU: the goldens of the unmodified
 reference (tools/make_golden_keep_track.py) agree with the float64 restatement (tests/tcm_np.py), the weight pack folds the eval
 BatchNorms exactly as the module computes, the C ABI refuses bad arguments before any launch, install() binds and uninstall()
-restores the new names, and KeepTrack's localisation / box refinement methods are DiMP's in code."""
+restores the new names, and KeepTrack's localisation / box refinement methods are DiMP's in code.  On the cases off the deployed shapes
+(tests/tcm_cases.py, run on the device by tests/test_gpu_keep_track_f64.py) the restatement agrees with the reference's own SuperGlue and
+with torch's conv2d in float64, every matcher case is well-conditioned, and a restatement with the mistake a case is there for (side 1
+normalised with side 0's image size, the layer list reversed, H and W swapped, the batch index dropped, one Sinkhorn iteration too few)
+leaves that case's bound."""
 import ast
 import ctypes
 import inspect
@@ -12,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+import tcm_cases as TC
 import tcm_np
 from oracle import ref_harness
 from pytracking_amd import _lib, synth
@@ -249,3 +254,152 @@ def test_uncovered_matcher_confs_and_zero_keypoint_branch_fall_back():
     empty = {"img_coords0": torch.zeros(1, 0, 2), "img_coords1": torch.zeros(1, 3, 2)}
     assert CM.zero_keypoint_branch(empty) and not CM.covered_match(SuperGlue(base).eval(), empty)
     assert not CM.zero_keypoint_branch({"img_coords0": torch.zeros(5, 2), "img_coords1": torch.zeros(3, 2)})
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The cases off the deployed shapes (tests/tcm_cases.py): the float64 anchor is right on them, each has its ref_err, and a restatement
+# with the mistake a case is there for leaves that case's bound.  Every test prints its figures before it asserts (run with -s).
+
+@pytest.mark.parametrize("name", list(TC.PEAK_CASES))
+def test_peak_cases_reach_the_paths_they_are_there_for(name):
+    H, W, ks, th, _, _ = TC.PEAK_CASES[name]
+    maps = TC.peak_map(name)
+    assert maps.dtype == np.float32 and maps.shape[-2:] == (H, W)
+    want = TC.peak_want(name)
+    for c, v in want:
+        idx = c[:, 0] * W + c[:, 1]
+        assert len(set(idx.tolist())) == len(idx) and np.all(v[:-1] >= v[1:])
+        assert all(i0 < i1 for i0, i1, a, b in zip(idx[:-1], idx[1:], v[:-1], v[1:]) if a == b)      # ties in ascending raster order
+    c, v = want[0]
+    idx = c[:, 0] * W + c[:, 1]
+    print(f"\npeaks {name}: {[len(c) for c, _ in want]} hits, {sorted(set((idx // 1024).tolist()))} compaction passes with a hit")
+    if name in ("33x33", "64x64", "64x64_ks1", "40x50_eighths"):           # a hit in every pass: `base` is carried into each
+        assert set((idx // 1024).tolist()) == set(range((H * W + 1023) // 1024))
+    if name == "64x64_ks1":
+        assert len(c) > 1024 and len(c) == int((maps > np.float32(th)).sum())
+    if name == "64x64_ks127":
+        assert [tuple(r) for r in c] == list(TC.TWO_MAXIMA) and v.tolist() == [2.0, 2.0]
+    if name == "1x1":
+        assert len(c) == 1
+    if name == "40x50_eighths":
+        assert len(np.unique(v)) < len(v) / 8                                  # many exact ties
+    if name == "23x23_nonfinite":
+        assert tuple(c[0]) == TC.NONFINITE["+inf"] and np.isinf(v[0]) and np.isfinite(v[1:]).all()
+        ny, nx = TC.NONFINITE["nan"]
+        assert not any(abs(y - ny) <= ks // 2 and abs(x - nx) <= ks // 2 for y, x in c)    # a NaN in the window: no peak there
+        assert np.isnan(maps).sum() == 1 and (maps == -np.inf).sum() == 1
+    if name == "40x50_batch3":
+        assert len(want) == 3 and all(len(c) > 0 for c, _ in want)
+        assert len({tuple(map(tuple, c)) for c, _ in want}) == 3
+
+
+@pytest.mark.parametrize("name", list(TC.DESC_CASES))
+def test_numpy_descriptors_match_conv2d_in_float64(name):
+    B, C, H, W, D, P, form, _ = TC.DESC_CASES[name]
+    i, a = TC.desc_inputs(name), TC.desc_anchor(name)
+    assert i.x.shape == (B, C, H, W) and i.weight.shape == (D, C, 4, 4) and i.coords3.shape == (B, P, 2)
+    assert i.coords.shape == ((B, P, 2) if form == "per_image" else (P, 2)) and i.coords.dtype == (np.int32 if form == "int32" else np.int64)
+    if P > 4:
+        for b in range(B):
+            assert {(0, 0), (0, W), (H, 0), (H, W)} <= set(map(tuple, i.coords3[b]))
+    f64 = TC.conv2d_at_points(i.x, i.weight, i.bias, i.coords3, torch.float64)
+    err = float(np.abs(f64 - a.want).max())
+    print(f"\ndesc {name}: max |numpy - conv2d float64| {err:.3e}, ref_err {a.ref_err:.3e}, bound {TC.bound(a.ref_err):.3e}")
+    assert a.want.shape == (B, D, P) and err <= 1e-9
+    assert 0 < a.ref_err < 1e-5                                                # fp32 rounding of sums of C * 16 terms of order 1
+
+
+@pytest.mark.parametrize("name", list(TC.MATCH))
+def test_matcher_cases_are_well_conditioned(name):
+    """The discrete outputs are compared exactly on the device: every row's and column's maximum is 1e-3 ahead of its runner-up and every
+    match score 1e-3 away from the filter threshold, in float64."""
+    M, N = TC.MATCH[name][1:3]
+    w = TC.match_want(name)
+    rows, cols, thr = tcm_np.margins(w["log_assignment"], w["match_scores0"])
+    print(f"\nmatch {name}: margins rows {rows:.3g}, columns {cols:.3g}, threshold {thr:.3g}")
+    assert w["log_assignment"].shape == (M + 1, N + 1) and min(rows, cols, thr) > 1e-3
+
+
+@needs_ref
+@pytest.mark.parametrize("name", list(TC.MATCH))
+def test_numpy_matcher_matches_the_reference_in_float64(name):
+    w, a = TC.match_want(name), TC.match_anchor(name)
+    r64 = TC.reference_match(name, torch.float64)
+    err = float(np.abs(r64["log_assignment"] - w["log_assignment"]).max())
+    print(f"\nmatch {name}: max |numpy - reference float64| {err:.3e}, ref_err {a.ref_err:.3e}, bound {TC.bound(a.ref_err):.3e}")
+    assert r64["log_assignment"].dtype == np.float64 and err <= 1e-9
+    np.testing.assert_array_equal(r64["matches0"], w["matches0"])
+    np.testing.assert_array_equal(r64["matches1"], w["matches1"])
+    # exp(z) of an agreeing z: relative where the score exceeds 1 (without a Sinkhorn iteration Z is not normalised: `it0` reaches 1e13)
+    np.testing.assert_allclose(r64["match_scores0"], w["match_scores0"], atol=1e-9, rtol=1e-9)
+    np.testing.assert_allclose(r64["match_scores1"], w["match_scores1"], atol=1e-9, rtol=1e-9)
+    assert 0 < a.ref_err < 1e-4                                                # under the flat tolerance of the golden tests
+
+
+def _desc_mutant(name, swap_hw=False, drop_batch=False):
+    """tcm_np.get_descriptors with the map indexed as (W, H) (bounds and row stride), or with every image read as image 0."""
+    i = TC.desc_inputs(name)
+    B, C, H, W = i.x.shape
+    flat = i.x.astype(np.float64).reshape(B, C, H * W)
+    w = i.weight.astype(np.float64)
+    h_, w_ = (W, H) if swap_hw else (H, W)
+    out = np.empty((B, w.shape[0], i.coords3.shape[1]))
+    for b in range(B):
+        for p, (y, x) in enumerate(i.coords3[b]):
+            patch = np.zeros((C, 4, 4))
+            for u in range(4):
+                for v in range(4):
+                    yy, xx = y + u - 2, x + v - 2
+                    if 0 <= yy < h_ and 0 <= xx < w_:
+                        patch[:, u, v] = flat[0 if drop_batch else b, :, yy * w_ + xx]
+            out[b, :, p] = w.reshape(w.shape[0], -1) @ patch.reshape(-1) + i.bias
+    return out
+
+
+def test_desc_mutant_helper_is_the_anchor_without_a_mutation():
+    for name in ("h9_w30", "b2_per_image"):
+        assert np.abs(_desc_mutant(name) - TC.desc_anchor(name).want).max() <= 1e-12
+
+
+@pytest.mark.parametrize("name,mutation", [("h9_w30", "swap_hw"), ("h30_w9", "swap_hw"), ("b2_per_image", "drop_batch"),
+                                           ("b3_shared", "drop_batch")])
+def test_the_descriptor_bound_catches_the_mutant(name, mutation):
+    a = TC.desc_anchor(name)
+    diff = np.abs(_desc_mutant(name, **{mutation: True}) - a.want)
+    print(f"\ndesc {name}, mutant {mutation}: max |mutant - float64| {diff.max():.3e}, bound {TC.bound(a.ref_err):.3e}")
+    assert diff.max() > TC.bound(a.ref_err)
+    if mutation == "drop_batch":                                               # image 0 is right, every later image is not
+        assert diff[0].max() == 0 and all(diff[b].max() > TC.bound(a.ref_err) for b in range(1, diff.shape[0]))
+
+
+@pytest.mark.parametrize("name", ["9x64", "64x9"])
+def test_the_peak_comparison_catches_a_swapped_raster_index(name):
+    H, W = TC.PEAK_CASES[name][:2]
+    c, _ = TC.peak_want(name)[0]
+    idx = c[:, 0] * W + c[:, 1]
+    mutant = np.stack([idx // H, idx % H], 1)                                  # y = i / H, x = i % H
+    assert not np.array_equal(mutant, c)
+
+
+@needs_ref
+@pytest.mark.parametrize("name,mutation", [("sizes", "side0_size"), ("ssc", "reversed"), ("css5", "reversed"), ("it1", "one_fewer")])
+def test_the_matcher_bound_catches_the_mutant(name, mutation):
+    """The float64 anchor with one mistake: side 1 normalised with side 0's image size, the layer list reversed (the weights stay in
+    place), one Sinkhorn iteration too few.  The case made for the mistake leaves its bound and changes its discrete outputs."""
+    sd, layers, iters, data = TC.match_inputs(name)
+    a = TC.match_anchor(name)
+    if mutation == "side0_size":
+        data = dict(data, image_size1=data["image_size0"])
+    elif mutation == "reversed":
+        layers = layers[::-1]
+        assert layers != TC.match_inputs(name)[1]
+    else:
+        iters -= 1
+    Z, m0, m1, ms0, ms1 = tcm_np.match(sd, layers, iters, data)
+    diff = float(np.abs(Z - a.want["log_assignment"]).max())
+    discrete = (not np.array_equal(m0, a.want["matches0"]) or not np.array_equal(m1, a.want["matches1"])
+                or not np.array_equal(ms0 == 0, a.want["match_scores0"] == 0))
+    print(f"\nmatch {name}, mutant {mutation}: max |mutant - float64| {diff:.3e}, bound {TC.bound(a.ref_err):.3e}, "
+          f"discrete outputs differ: {discrete}")
+    assert diff > TC.bound(a.ref_err)
+    assert discrete
