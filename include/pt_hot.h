@@ -54,6 +54,15 @@ int pt_abi_version(void);
  * out[0..9] = usable, tiles, k-step halves per tile, samples per workgroup, mixed pair layout, threads per workgroup, k-steps per wave,
  * channel ranges, dynamic LDS bytes, leftover-quad tile.  Returns 0, or PT_ERR_NULL. */
 int pt_corr_pass_plan(int n, int C, int H, int W, int KH, int KW, int OH, int OW, int* out);
+/* What the correlation launcher dispatches on beyond those ten fields, host only:
+ * out[0..3] = usable, uniform-step 4x4 shift-and-add, quads behind the last full 64-position tile (0..15), and how they run
+ * (0: none, 1: leftover quads on tile 0's wave, 2: a partial tile of its own).  Returns 0, or PT_ERR_NULL. */
+int pt_corr_pass_tail(int n, int C, int H, int W, int KH, int KW, int OH, int OW, int* out);
+/* Launch geometry of the XCD-aligned adjoint pass and the instantiation its dispatcher launches, host only:
+ * out[0..10] = usable, map elements per lane E, compile-time groups per wave UM, groups per wave U, position slices, groups per slice,
+ * 16-channel blocks, channel blocks per XCD (0: fewer blocks than XCDs), residual maps a workgroup holds at most, padded map row,
+ * dynamic LDS bytes.  All 0 when the shape is not covered.  Returns 0, or PT_ERR_NULL. */
+int pt_adj_pass_plan(int n, int C, int H, int W, int KH, int KW, int OH, int OW, int* out);
 size_t pt_apply_filter_ws_bytes(int n, int C, int H, int W, int KH, int KW, int OH, int OW);
 int pt_apply_filter_f32(const float* feat, long feat_stride_n, const float* filt, float* scores,
                         int n, int C, int H, int W, int KH, int KW, int OH, int OW,
@@ -116,6 +125,13 @@ int pt_sd_solve_f32(const pt_sd_params* p, const float* w_in, const float* feat,
                     const float* bb, const float* sample_weight,
                     int n, int C, int H, int W, int K, int num_iter,
                     float* w_iters, float* losses, void* ws, size_t ws_bytes, void* stream);
+
+/* Route pt_sd_solve_f32 takes for exactly these operands -- the solve's own checks, predicate and dispatch helpers, evaluated on the
+ * host, nothing launched: out[0] = 1 XCD-aligned fast route / 0 generic; on the fast route out[1] = residual provider of the adjoint pass
+ * (1 DiMP relu, 2 DiMP bent identity, 3 DiMP-L2, 4 PrDiMP), out[2] = width of the fused gradient reduction (8 | 16 partials),
+ * out[3] = 1 when the last update runs with the loss read-out.  Returns 0 or the status the solve would return for the shape. */
+int pt_sd_solve_route(const pt_sd_params* p, const float* w_in, const float* feat, long feat_stride_n, const float* w_iters,
+                      int n, int C, int H, int W, int K, int want_losses, int* out);
 
 /* S independent sequences in one call (optimizer.py:101-104 `num_sequences`; KYS / multi-object wrappers call the optimiser with
  * S > 1).  Arrays of S pointers (host arrays of device pointers); sample_weight / losses may be NULL as arrays; ws: S workspaces of

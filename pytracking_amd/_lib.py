@@ -102,7 +102,7 @@ HEADS_ROUTES = ("HEADS_NCHW_TOKENS", "HEADS_CONV3_PLAIN", "HEADS_CONV3_ROWSCALE"
 
 EXPORTS = [
     "pt_strerror", "pt_abi_version",
-    "pt_corr_pass_plan", "pt_apply_filter_ws_bytes", "pt_apply_filter_f32",
+    "pt_corr_pass_plan", "pt_corr_pass_tail", "pt_adj_pass_plan", "pt_sd_solve_route", "pt_apply_filter_ws_bytes", "pt_apply_filter_f32",
     "pt_feat_transpose_ws_bytes", "pt_feat_transpose_f32",
     "pt_sd_ws_bytes", "pt_sd_solve_f32",
     "pt_atom_cg_ws_bytes", "pt_atom_cg_f32", "pt_atom_gn_ws_bytes", "pt_atom_gn_f32",
@@ -289,6 +289,12 @@ def lib():
     L.pt_feat_transpose_f32.argtypes = [vp, l, vp, vp] + [i] * 8 + [vp, sz, vp]
     L.pt_sd_ws_bytes.restype = sz
     L.pt_sd_ws_bytes.argtypes = [i] * 5
+    L.pt_corr_pass_tail.restype = i
+    L.pt_corr_pass_tail.argtypes = [i] * 8 + [ctypes.POINTER(ctypes.c_int)]
+    L.pt_adj_pass_plan.restype = i
+    L.pt_adj_pass_plan.argtypes = [i] * 8 + [ctypes.POINTER(ctypes.c_int)]
+    L.pt_sd_solve_route.restype = i
+    L.pt_sd_solve_route.argtypes = [ctypes.POINTER(SdParams), vp, vp, l, vp] + [i] * 6 + [ctypes.POINTER(ctypes.c_int)]
     L.pt_sd_solve_f32.restype = i
     L.pt_sd_solve_f32.argtypes = [ctypes.POINTER(SdParams), vp, vp, l, vp, vp] + [i] * 6 + [vp, vp, vp, sz, vp]
     vpp = ctypes.POINTER(ctypes.c_void_p)

@@ -110,6 +110,27 @@ extern "C" int pt_corr_pass_plan(int n, int C, int H, int W, int KH, int KW, int
     return PT_OK;
 }
 
+// What pt_launch_corr2 dispatches on beyond pt_corr_pass_plan's ten fields: the uniform-step shift-and-add, the quads behind the last
+// full tile, and how they run (0: none, 1: leftover quads on tile 0's wave, 2: a partial 64-position tile of its own).
+extern "C" int pt_corr_pass_tail(int n, int C, int H, int W, int KH, int KW, int OH, int OW, int* out) {
+    if (!out) return PT_ERR_NULL;
+    const PtFast f = pt_fast_plan(n, C, H, W, KH, KW, OH, OW);
+    const int v[4] = {f.ok, f.ok ? f.sa_direct : 0, f.ok ? f.rem : 0, f.ok ? (f.rem == 0 ? 0 : (f.left ? 1 : 2)) : 0};
+    for (int k = 0; k < 4; ++k) out[k] = v[k];
+    return PT_OK;
+}
+
+// The adjoint pass's plan and the instantiation adj2_dispatch launches for it (pt_adj2_um: the dispatcher's own helper).
+extern "C" int pt_adj_pass_plan(int n, int C, int H, int W, int KH, int KW, int OH, int OW, int* out) {
+    if (!out) return PT_ERR_NULL;
+    const PtFast f = pt_fast_plan(n, C, H, W, KH, KW, OH, OW);
+    for (int k = 0; k < 11; ++k) out[k] = 0;
+    if (!f.ok) return PT_OK;
+    const int v[11] = {1, f.E, pt_adj2_um(f), f.U, f.KSPL, f.gper, f.CB, f.bpx, f.ns_max, f.PW, (int)f.adj_lds};
+    for (int k = 0; k < 11; ++k) out[k] = v[k];
+    return PT_OK;
+}
+
 extern "C" size_t pt_apply_filter_ws_bytes(int n, int C, int H, int W, int KH, int KW, int OH, int OW) {
     if (filt_check(n, C, H, W, KH, KW, OH, OW)) return 0;
     PtPlan p = pt_make_plan(n, C, H, W, KH, KW, OH, OW);

@@ -621,7 +621,7 @@ int pt_launch_corr2(const PtFast& p, const float* feat, long stride_n, const flo
     do {                                                                                                         \
         if (lazy) { if constexpr (KF) hipLaunchKernelGGL((k_corr2<NKV, LF, -1, true, NHV, MX>), grid, block, p.corr_lds, st, PT_C2_HOT(a.filt), a); } \
         else if (!a.gpart) hipLaunchKernelGGL((k_corr2<NKV, LF, 0, KF, NHV, MX>), grid, block, p.corr_lds, st, PT_C2_HOT(a.filt), a);             \
-        else if (a.KSPL <= 8) hipLaunchKernelGGL((k_corr2<NKV, LF, 8, KF, NHV, MX>), grid, block, p.corr_lds, st, PT_C2_HOT(a.gpart), a);     \
+        else if (pt_corr2_fuse_width(a.KSPL) == 8) hipLaunchKernelGGL((k_corr2<NKV, LF, 8, KF, NHV, MX>), grid, block, p.corr_lds, st, PT_C2_HOT(a.gpart), a);     \
         else hipLaunchKernelGGL((k_corr2<NKV, LF, 16, KF, NHV, MX>), grid, block, p.corr_lds, st, PT_C2_HOT(a.gpart), a);                     \
     } while (0)
 #define PT_C2H(NKV, LF, KF)              \
@@ -1221,6 +1221,18 @@ static void adj2_fill(const PtFast& p, Adj2Args& a, const float* feat, long stri
     PT_STAMP_SET(a);
 }
 
+// the provider a solve of this kind / score activation runs (pt_launch_adj2_sd; pt_sd_solve_route reports it)
+int pt_adj2_provider(int kind, int score_act) {
+    if (kind == PT_SD_PRDIMP) return V_PRDIMP;
+    if (kind == PT_SD_DIMP_L2) return V_L2;
+    return score_act == PT_ACT_BENTPAR ? V_DIMP_BENT : V_DIMP_RELU;
+}
+// UM of the k_adj2<V, E, UM> instantiation a plan runs (adj2_dispatch; pt_adj_pass_plan reports it)
+int pt_adj2_um(const PtFast& p) {
+    if (p.E != 9) return 16;
+    return p.U <= 12 ? 12 : (p.U <= 16 ? 16 : PT_ADJ_UMAX_WIDE);
+}
+
 // Can the first adjoint pass of this solve do the init stage itself (k_adj2<.., INIT>)?
 bool pt_adj2_init_fusable(const PtFast& p, const SdArgs& sd) {
     if (sd.kind != PT_SD_DIMP && sd.kind != PT_SD_DIMP_L2) return false;
@@ -1235,6 +1247,7 @@ bool pt_adj2_init_fusable(const PtFast& p, const SdArgs& sd) {
 template <int V>
 static int adj2_dispatch(const PtFast& p, const Adj2Args& a, hipStream_t st, bool fuse_init = false) {
     dim3 grid(p.CB * p.KSPL), block(PT_ADJ_WAVES * 64);
+    const int um = pt_adj2_um(p);
     if (p.H > 255 || p.W > 255 || p.U > 31 || p.bpx > 15 || a.t > 127 || p.n > 65535 || p.gper > 65535 || p.OO > 65535 || p.CB > 255 ||
         a.sd.KS > 127 || p.PH > 63 || p.PW > 63 || p.zn > 255 || p.ns_max > 63 || p.KH > 7 || p.KW > 7)
         return PT_ERR_UNSUPPORTED;
@@ -1271,8 +1284,8 @@ static int adj2_dispatch(const PtFast& p, const Adj2Args& a, hipStream_t st, boo
             const size_t lds = p.adj_lds + (size_t)3 * (sd.kind == PT_SD_DIMP ? sd.num_bins : 0) * sizeof(float);
 #define PT_A2_INIT a.feat, a.stride_n, (const float*)sd.spart, sd.bb, lut3, g1, g2, g3, g4, l, il
             if (p.E == 6) hipLaunchKernelGGL((k_adj2<V, 6, 16, true>), grid, block, lds, st, PT_A2_INIT);
-            else if (p.U <= 12) hipLaunchKernelGGL((k_adj2<V, 9, 12, true>), grid, block, lds, st, PT_A2_INIT);
-            else if (p.U <= 16) hipLaunchKernelGGL((k_adj2<V, 9, 16, true>), grid, block, lds, st, PT_A2_INIT);
+            else if (um == 12) hipLaunchKernelGGL((k_adj2<V, 9, 12, true>), grid, block, lds, st, PT_A2_INIT);
+            else if (um == 16) hipLaunchKernelGGL((k_adj2<V, 9, 16, true>), grid, block, lds, st, PT_A2_INIT);
             else hipLaunchKernelGGL((k_adj2<V, 9, PT_ADJ_UMAX_WIDE, true>), grid, block, lds, st, PT_A2_INIT);
 #undef PT_A2_INIT
             return PT_OK;
@@ -1280,8 +1293,8 @@ static int adj2_dispatch(const PtFast& p, const Adj2Args& a, hipStream_t st, boo
     } else if (fuse_init) return PT_ERR_UNSUPPORTED;
 #define PT_A2_HOT a.feat, a.stride_n, pkp, qsp, anp, g1, g2, g3, g4, l, Adj2InitLate{}
     if (p.E == 6) hipLaunchKernelGGL((k_adj2<V, 6, 16>), grid, block, p.adj_lds, st, PT_A2_HOT);
-    else if (p.E == 9 && p.U <= 12) hipLaunchKernelGGL((k_adj2<V, 9, 12>), grid, block, p.adj_lds, st, PT_A2_HOT);
-    else if (p.E == 9 && p.U <= 16) hipLaunchKernelGGL((k_adj2<V, 9, 16>), grid, block, p.adj_lds, st, PT_A2_HOT);
+    else if (p.E == 9 && um == 12) hipLaunchKernelGGL((k_adj2<V, 9, 12>), grid, block, p.adj_lds, st, PT_A2_HOT);
+    else if (p.E == 9 && um == 16) hipLaunchKernelGGL((k_adj2<V, 9, 16>), grid, block, p.adj_lds, st, PT_A2_HOT);
     else if (p.E == 9) hipLaunchKernelGGL((k_adj2<V, 9, PT_ADJ_UMAX_WIDE>), grid, block, p.adj_lds, st, PT_A2_HOT);
     else hipLaunchKernelGGL((k_adj2<V, 16, 16>), grid, block, p.adj_lds, st, PT_A2_HOT);
 #undef PT_A2_HOT
@@ -1310,9 +1323,10 @@ int pt_launch_adj2_sd(const PtFast& p, const float* feat, long stride_n, const S
     a.t = t;
     a.want_loss = want_loss;
     int rc;
-    if (sd.kind == PT_SD_PRDIMP) rc = adj2_dispatch<V_PRDIMP>(p, a, st, fuse_init);
-    else if (sd.kind == PT_SD_DIMP_L2) rc = adj2_dispatch<V_L2>(p, a, st, fuse_init);
-    else if (sd.score_act == PT_ACT_BENTPAR) rc = adj2_dispatch<V_DIMP_BENT>(p, a, st, fuse_init);
+    const int v = pt_adj2_provider(sd.kind, sd.score_act);
+    if (v == V_PRDIMP) rc = adj2_dispatch<V_PRDIMP>(p, a, st, fuse_init);
+    else if (v == V_L2) rc = adj2_dispatch<V_L2>(p, a, st, fuse_init);
+    else if (v == V_DIMP_BENT) rc = adj2_dispatch<V_DIMP_BENT>(p, a, st, fuse_init);
     else rc = adj2_dispatch<V_DIMP_RELU>(p, a, st, fuse_init);
     if (rc) return rc;
     PT_CHECK_LAUNCH();

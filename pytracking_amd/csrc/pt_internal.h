@@ -113,6 +113,14 @@ struct SdArgs;
 int pt_launch_adj2_sd(const PtFast& p, const float* feat, long stride_n, const SdArgs& sd, int t, int want_loss,
                       hipStream_t st, bool fuse_init = false);
 bool pt_adj2_init_fusable(const PtFast& p, const SdArgs& sd);
+// What the two launchers dispatch on beyond the plan, each decided in ONE place that the launcher and the host-only queries
+// (pt_adj_pass_plan, pt_sd_solve_route) both read:
+//   pt_adj2_um           UM of the k_adj2<V, E, UM> instantiation adj2_dispatch launches for this plan
+//   pt_adj2_provider     residual provider V of the solve's adjoint pass: 1 DiMP relu, 2 DiMP bent identity, 3 DiMP-L2, 4 PrDiMP (0: plain pass)
+//   pt_corr2_fuse_width  FUSE of k_corr2's gradient reduction for this many adjoint slices (8 | 16)
+int pt_adj2_um(const PtFast& p);
+int pt_adj2_provider(int kind, int score_act);
+static inline int pt_corr2_fuse_width(int KSPL) { return KSPL <= 8 ? 8 : 16; }
 
 // ---- multi-filter passes (mf_kernels.hip): F <= 16 filters, odd K, C % 16 == 0 -----------------------------
 size_t pt_mf_gpart_floats(int n, int F, int C, int H, int W, int K);     // 0: configuration not covered

@@ -652,6 +652,19 @@ static int sd_solve_fast(const PtFast& f, const pt_sd_params* prm, const float* 
     return PT_OK;
 }
 
+// The shape / parameter checks in front of the route decision (pt_sd_solve_impl; pt_sd_solve_route repeats them through this function).
+static int sd_shape_checks(const pt_sd_params* prm, int n, int C, int H, int W, int K, int num_iter, long feat_stride_n, bool label_map,
+                           bool label_map_refused) {
+    if (n <= 0 || C <= 0 || H <= 0 || W <= 0 || K <= 0 || num_iter < 0) return PT_ERR_SHAPE;
+    if (K * K > 16 || num_iter > PT_SD_MAX_ITER) return PT_ERR_UNSUPPORTED;
+    if (feat_stride_n < (long)C * H * W) return PT_ERR_SHAPE;
+    if (label_map_refused) return PT_ERR_UNSUPPORTED;
+    if (prm->kind == PT_SD_DIMP && !label_map && (!prm->label_lut || !prm->mask_lut || !prm->spatial_lut || prm->num_bins < 1))
+        return PT_ERR_NULL;
+    if (prm->kind < PT_SD_DIMP || prm->kind > PT_SD_PRDIMP) return PT_ERR_UNSUPPORTED;
+    return PT_OK;
+}
+
 // Internal entry shared by pt_sd_solve_f32 and pt_track_frame_f32.
 //   copy_w0  : also materialise iterate 0 in w_iters[0] (public API contract)
 //   w_final  : if non-null the last iterate is written there (may alias w_in) instead of w_iters[T]
@@ -661,13 +674,8 @@ int pt_sd_solve_impl(const pt_sd_params* prm, const float* w_in, const float* fe
                      float* losses, void* ws, size_t ws_bytes, hipStream_t st, bool copy_w0, float* w_final,
                      const PtClsFin* cls, const float* src, pt_frame_pending* pend, bool defer, const PtLabelMap* lmap) {
     if (!prm || !w_in || !feat || !(bb || lmap) || !w_iters || !ws) return PT_ERR_NULL;
-    if (n <= 0 || C <= 0 || H <= 0 || W <= 0 || K <= 0 || num_iter < 0) return PT_ERR_SHAPE;
-    if (K * K > 16 || num_iter > PT_SD_MAX_ITER) return PT_ERR_UNSUPPORTED;
-    if (feat_stride_n < (long)C * H * W) return PT_ERR_SHAPE;
-    if (lmap && (prm->kind != PT_SD_DIMP || !lmap->label || cls || src || defer || pend)) return PT_ERR_UNSUPPORTED;
-    if (prm->kind == PT_SD_DIMP && !lmap && (!prm->label_lut || !prm->mask_lut || !prm->spatial_lut || prm->num_bins < 1))
-        return PT_ERR_NULL;
-    if (prm->kind < PT_SD_DIMP || prm->kind > PT_SD_PRDIMP) return PT_ERR_UNSUPPORTED;
+    const bool lmap_refused = lmap && (prm->kind != PT_SD_DIMP || !lmap->label || cls || src || defer || pend);
+    if (int rc = sd_shape_checks(prm, n, C, H, W, K, num_iter, feat_stride_n, lmap != nullptr, lmap_refused)) return rc;
     const int OH = H + (K + 1) % 2, OW = W + (K + 1) % 2;               // optimizer.py:105
     {
         PtFast f = pt_fast_plan(n, C, H, W, K, K, OH, OW);
@@ -763,6 +771,23 @@ extern "C" int pt_sd_solve_f32(const pt_sd_params* prm, const float* w_in, const
     return pt_sd_solve_impl(prm, w_in, feat, feat_stride_n, bb, sample_weight, n, C, H, W, K, num_iter, w_iters, losses,
                             ws, ws_bytes, (hipStream_t)stream, /*copy_w0=*/true, /*w_final=*/nullptr, /*cls=*/nullptr,
                             /*src=*/nullptr);
+}
+
+// Route pt_sd_solve_f32 takes for these operands, nothing launched: the solve's own checks and predicate (sd_shape_checks,
+// pt_sd_route_fast) and the helpers its two passes dispatch on (pt_adj2_provider, pt_corr2_fuse_width).
+extern "C" int pt_sd_solve_route(const pt_sd_params* prm, const float* w_in, const float* feat, long feat_stride_n, const float* w_iters,
+                                 int n, int C, int H, int W, int K, int want_losses, int* out) {
+    if (!prm || !w_in || !feat || !w_iters || !out) return PT_ERR_NULL;
+    for (int k = 0; k < 4; ++k) out[k] = 0;
+    if (int rc = sd_shape_checks(prm, n, C, H, W, K, 0, feat_stride_n, false, false)) return rc;
+    const int OH = H + (K + 1) % 2, OW = W + (K + 1) % 2;
+    const PtFast f = pt_fast_plan(n, C, H, W, K, K, OH, OW);
+    if (!pt_sd_route_fast(f, feat, feat_stride_n, w_in, w_iters, nullptr, pt_sd_lut_bins(prm), false)) return PT_OK;
+    out[0] = 1;
+    out[1] = pt_adj2_provider(prm->kind, prm->score_act);
+    out[2] = pt_corr2_fuse_width(f.KSPL);
+    out[3] = want_losses ? 1 : 0;                                  // last update: k_fast_final | k_sd_pw with the loss read-out
+    return PT_OK;
 }
 
 // S independent sequences in ONE call (optimizer.py:101-104 `num_sequences`: the reference carries them as a tensor dimension of

@@ -43,6 +43,16 @@ def test_argument_checks_do_not_launch(L):
     assert L.pt_sd_ws_bytes(50, 512, 18, 18, 4) > 0
     assert L.pt_sd_ws_bytes(0, 512, 18, 18, 4) == 0
     assert L.pt_track_frame_ws_bytes(50, 512, 18, 18, 4) > L.pt_sd_ws_bytes(50, 512, 18, 18, 4)
+    # the plan and route queries of the XCD-aligned passes: host only, zeros for a shape the plan does not cover
+    t4, a11, r4 = (ctypes.c_int * 4)(), (ctypes.c_int * 11)(), (ctypes.c_int * 4)()
+    assert L.pt_corr_pass_tail(50, 512, 18, 18, 4, 4, 19, 19, n) == -1 and L.pt_adj_pass_plan(50, 512, 18, 18, 4, 4, 19, 19, n) == -1
+    assert L.pt_corr_pass_tail(50, 512, 18, 18, 4, 4, 19, 19, t4) == 0 and list(t4) == [1, 1, 1, 1]
+    assert L.pt_adj_pass_plan(50, 512, 18, 18, 4, 4, 19, 19, a11) == 0 and list(a11)[:5] == [1, 6, 16, 16, 8] and a11[6:9] == [32, 4, 8]
+    assert L.pt_adj_pass_plan(50, 500, 18, 18, 4, 4, 19, 19, a11) == 0 and list(a11) == [0] * 11
+    p.kind = _lib.PT_SD_PRDIMP
+    assert L.pt_sd_solve_route(ctypes.byref(p), one, one, 512 * 324, one, 50, 512, 18, 18, 4, 0, n) == -1
+    assert L.pt_sd_solve_route(ctypes.byref(p), one, one, 512 * 324, one, 50, 512, 18, 18, 4, 0, r4) == 0 and list(r4) == [1, 4, 8, 0]
+    assert L.pt_sd_solve_route(ctypes.byref(p), one, one, 512 * 324, one, 50, 512, 18, 18, 5, 0, r4) == -3
 
 
 def test_multifilter_and_lwl_argument_checks(L):

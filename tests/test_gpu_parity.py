@@ -63,7 +63,9 @@ def test_apply_filter_two_sequences_and_errors():
 @pytest.mark.parametrize("n,C,H,W,K", [(1, 512, 18, 18, 4), (50, 512, 18, 18, 4), (7, 64, 22, 22, 4),
                                        (3, 20, 9, 7, 3), (2, 33, 5, 6, 2), (5, 256, 18, 18, 1),
                                        # XCD-aligned fast path: trailing-quad trick (rem 1 and 4), no remainder,
-                                       # regular partial tile (22x22: rem 9), every channel count, odd/even K
+                                       # regular partial tile (22x22: rem 9), every channel count, odd/even K.  A sample of
+                                       # its plan space: tests/fast_pass_cases.py holds one case per reachable plan cell of
+                                       # both passes (tests/test_gpu_fast_pass_plans.py, tests/test_fast_pass_plans_cpu.py)
                                        (3, 128, 18, 18, 4), (5, 256, 22, 22, 4), (2, 128, 10, 8, 4),
                                        (2, 128, 16, 16, 4), (3, 256, 12, 12, 3), (2, 128, 20, 20, 4),
                                        (1, 1024, 18, 18, 4), (4, 128, 14, 14, 2), (9, 128, 18, 16, 4),
