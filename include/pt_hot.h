@@ -1197,6 +1197,29 @@ size_t pt_eco_filter_update_ws_bytes(const pt_eco_fu_block* blk, int nb);
 int pt_eco_filter_update_f32(const pt_eco_fu_block* blk, int nb, int num_iter, int fletcher_reeves, int standard_alpha,
                              float direction_forget_factor, float precond_data_param, float precond_reg_param, void* ws, size_t ws_bytes,
                              void* stream);
+/* First-frame joint optimisation of filter and projection matrix (eco.py:152-158): GaussNewtonCG.run (pytracking/libs/optimization.py:
+ * 293-421) on FactorizedConvProblem (pytracking/tracker/eco/optim.py:8-118), one call, all feature blocks, num_gn_iter Gauss-Newton
+ * iterations of num_cg_iter CG iterations each.  Per block: samples (Hf, Wh, n, Cin, 2) UNCOMPRESSED, weights_sqrt (nw = 1 or n) ON THE
+ * DEVICE, yf (Hf, Wh), reg_filter (Rh, Rw), diag_M (c, Hf, Wh) and proj_precond (the problem constructor's preconditioner: inputs, not
+ * recomputed), hf (c, Hf, Wh, 2) and proj (Cin, c) updated IN PLACE.  Residuals: sw_s (x[k,s]^T P h[k] - yf[k]); one correlation of
+ * [conj(flip(h[.., 1 : pad2 + 1, :])), h] with reg_filter at padding (pad1, pad2) = (min(Rh - 1, Hf - 1), min(Rw - 1, Wh - 1)), the left
+ * extension counted in the residual but not in the Jacobian (the reference detaches it); sqrt(projection_reg) P.  Each Gauss-Newton
+ * iteration solves J^T J d = -J^T f0 by run_CG from d = 0: Fletcher-Reeves beta clamped at 0, alpha = rho / ip(p, q), M1 = 1 / diag_M on the
+ * filter and 1 / proj_precond on the projection, p and rho reset, the residual update skipped on the last iteration; ip is ONE scalar per
+ * block, inner_prod_fs of the filter parts plus the dot product of the projection parts, so alpha and beta are per block.  If any block's
+ * rho is exactly 0 at the top of a CG iteration, that Gauss-Newton iteration's CG run ends for every block, the step accumulated so far
+ * (none in the first iteration, where the reference raises) is added and the next Gauss-Newton iteration goes on; a flag in the workspace
+ * turns the remaining launches of the run into no-ops.  Zero Gauss-Newton or CG iterations return PT_OK and touch nothing.
+ * Covered: Cin <= 512, c <= 64, n <= 64, Rh, Rw <= 15, <= PT_ECO_MAX_BLOCKS blocks, num_cg_iter <= 62, num_gn_iter <= 32. */
+typedef struct pt_eco_init_block {
+    const float *samples, *weights_sqrt, *yf, *reg_filter, *diag_M;
+    float *hf, *proj;            /* in/out */
+    int Hf, Wh, Cin, c, n, nw /* 1 or n */, Rh, Rw;
+    float proj_precond;
+} pt_eco_init_block;
+size_t pt_eco_joint_init_ws_bytes(const pt_eco_init_block* blk, int nb);
+int pt_eco_joint_init_f32(const pt_eco_init_block* blk, int nb, int num_gn_iter, int num_cg_iter, float projection_reg, void* ws,
+                          size_t ws_bytes, void* stream);
 int pt_eco_sample_f32(const float* x, const float* proj, const float* window, const float* interp_y, const float* interp_x, int has_shift,
                       float shift_y, float shift_x, float* xf, int S, int Cin, int c, int H, int W, void* stream);
 int pt_eco_shift_f32(const float* xf, float shift_y, float shift_x, float* out, int S, int c, int Hf, int Wh, void* stream);

@@ -9,7 +9,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PT_HOT_LIB", os.path.join(_HERE, "libpt_hot.so"))   # override: experiments only
-SOURCES = ["filter_kernels.hip", "fast_passes.hip", "sd_solver.hip", "mf_kernels.hip", "lwl_solver.hip", "atom_cg.hip", "atom_gn.hip", "tomp.hip", "localize.hip", "iou_refine.hip", "prroi.hip", "patch.hip", "frame_full.hip", "api.hip", "gn_hinge.hip", "tcm.hip", "kys.hip", "iou_feat.hip", "label_enc.hip", "box_enc.hip", "lwl_decoder.hip", "rts_fusion.hip", "seg_readout.hip", "eco.hip"]
+SOURCES = ["filter_kernels.hip", "fast_passes.hip", "sd_solver.hip", "mf_kernels.hip", "lwl_solver.hip", "atom_cg.hip", "atom_gn.hip", "tomp.hip", "localize.hip", "iou_refine.hip", "prroi.hip", "patch.hip", "frame_full.hip", "api.hip", "gn_hinge.hip", "tcm.hip", "kys.hip", "iou_feat.hip", "label_enc.hip", "box_enc.hip", "lwl_decoder.hip", "rts_fusion.hip", "seg_readout.hip", "eco.hip", "eco_init.hip"]
 HEADERS = ["common.h", "pt_internal.h", "rbuild.h", "sd_common.h", "mfma_gemm.h", "conv_tokens.h", "prroi_dev.h", "localize_dev.h", "frame_mid.h", "ds16_enc.h", "box_slice.h", os.path.join("..", "..", "include", "pt_hot.h")]
 # kernarg preload: leading scalar kernel parameters arrive in SGPRs at wave launch (kernels that take them that way only)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-pass-failed", "-mllvm", "-amdgpu-kernarg-preload-count=14"]
@@ -27,6 +27,13 @@ class EcoFuBlock(ctypes.Structure):
     """`pt_eco_fu_block` of include/pt_hot.h."""
     _fields_ = ([(n, ctypes.c_void_p) for n in ("samples", "weights", "yf", "reg_filter", "sample_energy", "new_xf", "x", "p", "r_prev", "state")]
                 + [(n, ctypes.c_int) for n in ("Hf", "Wh", "c", "n", "Rh", "Rw")] + [("learning_rate", ctypes.c_float), ("reg_energy", ctypes.c_float)])
+
+
+class EcoInitBlock(ctypes.Structure):
+    """`pt_eco_init_block` of include/pt_hot.h."""
+    _fields_ = ([(n, ctypes.c_void_p) for n in ("samples", "weights_sqrt", "yf", "reg_filter", "diag_M", "hf", "proj")]
+                + [(n, ctypes.c_int) for n in ("Hf", "Wh", "Cin", "c", "n", "nw", "Rh", "Rw")] + [("proj_precond", ctypes.c_float)])
+
 
 class IouDims(ctypes.Structure):
     """`pt_iou_dims` of include/pt_hot.h."""
@@ -137,7 +144,7 @@ EXPORTS = [
     "pt_seg_readout_ws_bytes", "pt_seg_readout_f32", "pt_seg_state_ws_bytes", "pt_seg_state_f32", "pt_seg_merge_ws_bytes", "pt_seg_merge_f32",
     "pt_sample_mask_patch_f32",
     "pt_eco_sample_f32", "pt_eco_shift_f32", "pt_eco_apply_filter_f32", "pt_eco_localize_ws_bytes", "pt_eco_localize_f32", "pt_eco_insert_f32",
-    "pt_eco_filter_update_ws_bytes", "pt_eco_filter_update_f32",
+    "pt_eco_filter_update_ws_bytes", "pt_eco_filter_update_f32", "pt_eco_joint_init_ws_bytes", "pt_eco_joint_init_f32",
 ]
 
 PT_TCM_MAX_POINTS, PT_TCM_MAX_LAYERS = 64, 32       # include/pt_hot.h
@@ -547,6 +554,10 @@ def lib():
     L.pt_eco_filter_update_ws_bytes.argtypes = [ctypes.POINTER(EcoFuBlock), i]
     L.pt_eco_filter_update_f32.restype = i
     L.pt_eco_filter_update_f32.argtypes = [ctypes.POINTER(EcoFuBlock), i, i, i, i, f, f, f, vp, sz, vp]
+    L.pt_eco_joint_init_ws_bytes.restype = sz
+    L.pt_eco_joint_init_ws_bytes.argtypes = [ctypes.POINTER(EcoInitBlock), i]
+    L.pt_eco_joint_init_f32.restype = i
+    L.pt_eco_joint_init_f32.argtypes = [ctypes.POINTER(EcoInitBlock), i, i, i, f, vp, sz, vp]
     L.pt_mf_corr_tm_plan.restype = i
     L.pt_mf_corr_tm_plan.argtypes = [i] * 5 + [ctypes.POINTER(ctypes.c_int)]
     L.pt_sample_patch_f32.restype = i

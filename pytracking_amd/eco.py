@@ -7,6 +7,10 @@
   insert(samples, xf, ind, shift)                    shift_fs + ECO.update_memory's slot store                   -> pt_eco_insert_f32
   filter_update(filters, samples, ...)               FilterOptim.run (preconditioned CG, all blocks)             -> pt_eco_filter_update_f32
 
+and the first-frame joint optimisation of filter and projection matrix (eco.py:152-158) (eco_init.hip):
+
+  joint_init(filters, projections, samples, ...)     GaussNewtonCG.run on FactorizedConvProblem (all blocks)     -> pt_eco_joint_init_f32
+
 `torch.rfft` / `torch.irfft`, which fourier.py:24,31 and dcf.py:134,139 call, do not exist in the installed torch, so the stock ECO cannot
 run at all.  `cfft2`, `cifft2` and `get_reg_filter` below are written on `torch.fft` from the documented behaviour of the removed functions
 (one-sided, unnormalised forward transform over the last two dimensions, complex numbers as a trailing dimension of 2; normalised inverse
@@ -14,8 +18,8 @@ with `signal_sizes`); install(eco=True) binds them in place of the reference's. 
 
 Every operation has a plain-torch form (`*_torch`, any device, any floating dtype) that states what the kernel computes; the tests run it in
 float64 and in fp32.  The `tracker_*` functions take the reference's ECO object and its TensorLists; `covered_*` say whether a call runs on
-the kernels, install() hands every other call to the reference.  The first-frame joint optimisation has no kernel here and runs the
-reference's code on the rebound Fourier tools.
+the kernels, install() hands every other call to the reference.  `gauss_newton_cg` builds the class install(eco_init=True) binds under
+the name eco.py:9 imported: the reference's GaussNewtonCG whose `run` takes the kernels for ECO's FactorizedConvProblem on the device.
 """
 import ctypes
 import math
@@ -513,3 +517,205 @@ def tracker_filter_run(opt, num_iter, new_xf=None):
                   opt.fletcher_reeves, opt.standard_alpha, opt.direction_forget_factor, prm.precond_data_param, prm.precond_reg_param)
     TL = type(opt.filter)
     opt.p, opt.r_prev, opt.rho = TL([s["p"] for s in st]), TL([s["r_prev"] for s in st]), TL([s["state"][0] for s in st])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# first-frame joint optimisation of filter and projection matrix (GaussNewtonCG.run on FactorizedConvProblem)
+
+def _init_pads(Hf, Wh, Rh, Rw):
+    return min(Rh - 1, Hf - 1), min(Rw - 1, Wh - 1)
+
+
+def _init_reg_fwd(v, reg, left):
+    """The ONE correlation of optim.py:52-69: v complex (c, Hf, Wh) extended to the left by its conjugate flip (`left`) or by zeros (the
+    Jacobian: the reference detaches the extension) -> real (2 c, 1, H1, W1), the real and imaginary parts as a batch."""
+    c, Hf, Wh = v.shape
+    p1, p2 = _init_pads(Hf, Wh, *reg.shape[-2:])
+    ext = v[:, :, 1:p2 + 1].flip((1, 2)).conj().resolve_conj()
+    x = torch.cat((ext if left else torch.zeros_like(ext), v), -1)
+    x = torch.view_as_real(x).permute(0, 3, 1, 2).reshape(2 * c, 1, Hf, Wh + p2)
+    return torch.nn.functional.conv2d(x, reg.reshape(1, 1, *reg.shape[-2:]), padding=(p1, p2))
+
+
+def _init_reg_T(g, reg, c, Hf, Wh):
+    """Its transpose on the non-detached columns -> complex (c, Hf, Wh)."""
+    p1, p2 = _init_pads(Hf, Wh, *reg.shape[-2:])
+    x = torch.nn.functional.conv_transpose2d(g, reg.reshape(1, 1, *reg.shape[-2:]), padding=(p1, p2))[..., p2:]
+    return torch.view_as_complex(x.reshape(c, 2, Hf, Wh).permute(0, 2, 3, 1).contiguous())
+
+
+def joint_init_torch(filters, projections, samples, weights_sqrt, yf, reg_filters, diag_M, proj_precond, num_cg_iter, num_gn_iter, projection_reg):
+    """GaussNewtonCG.run(num_cg_iter, num_gn_iter) on FactorizedConvProblem with the Gauss-Newton operator written out (what the two autograd
+    passes of the reference compute; definition in include/pt_hot.h), any device, any floating dtype.  `filters` (1, c, Hf, Wh, 2) and
+    `projections` (Cin, c) are updated IN PLACE."""
+    nb = len(filters)
+    if num_cg_iter == 0 or num_gn_iter == 0:
+        return filters, projections
+    cplx = lambda t: torch.view_as_complex(t.contiguous())      # noqa: E731
+    X = [cplx(s) for s in samples]                                # (Hf, Wh, n, Cin)
+    sw = [w.reshape(-1) for w in weights_sqrt]
+    y = [t.reshape(f.shape[2:4]) for t, f in zip(yf, filters)]
+    dM = [d.reshape(f.shape[1:4]) for d, f in zip(diag_M, filters)]
+    root = math.sqrt(projection_reg)
+
+    def fwd(b, h, P, dh, dP, left):
+        """J (dh, dP) at (h, P); with dP None the residual's own products: (data, reg, proj)"""
+        m = dh.permute(1, 2, 0) @ P.t().to(h.dtype)
+        if dP is not None:
+            m = m + h.permute(1, 2, 0) @ dP.t().to(h.dtype)
+        return (X[b] @ m.unsqueeze(-1)).squeeze(-1) * sw[b], _init_reg_fwd(dh, reg_filters[b], left), root * (P if dP is None else dP)
+
+    def transposed(b, h, P, g_data, g_reg, g_proj):
+        v = ((g_data * sw[b]).unsqueeze(-2) @ X[b].conj()).squeeze(-2)                   # (Hf, Wh, Cin)
+        gh = (v @ P.to(h.dtype)).permute(2, 0, 1) + _init_reg_T(g_reg, reg_filters[b], *h.shape)
+        return gh, torch.einsum("hwi,chw->ic", v, h.conj()).real + root * g_proj
+
+    def ip(a, b):
+        d = a[0].real * b[0].real + a[0].imag * b[0].imag
+        return 2 * d.sum() - d[..., 0].sum() + (a[1] * b[1]).sum()
+
+    for _ in range(num_gn_iter):
+        hs, Ps = [cplx(f[0]).clone() for f in filters], [p.clone() for p in projections]
+        r = []
+        for b in range(nb):
+            data, reg, proj = fwd(b, hs[b], Ps[b], hs[b], None, True)
+            gh, gP = transposed(b, hs[b], Ps[b], data - sw[b] * y[b].unsqueeze(-1), reg, proj)
+            r.append((-gh, -gP))
+        p, rho, dx = None, None, None
+        for ii in range(num_cg_iter):
+            z = [(rh / d, rP / pc) for (rh, rP), d, pc in zip(r, dM, proj_precond)]
+            rho1, rho = rho, [ip(rr, zz) for rr, zz in zip(r, z)]
+            if any(bool(v == 0) for v in rho):
+                break
+            if p is None:
+                p = z
+            else:
+                beta = [(n / o).clamp(0) for n, o in zip(rho, rho1)]
+                p = [(zh + ph * bt, zP + pP * bt) for (zh, zP), (ph, pP), bt in zip(z, p, beta)]
+            q = [transposed(b, hs[b], Ps[b], *fwd(b, hs[b], Ps[b], p[b][0], p[b][1], False)) for b in range(nb)]
+            alpha = [rh / ip(pp, qq) for rh, pp, qq in zip(rho, p, q)]
+            step = [(ph * al, pP * al) for (ph, pP), al in zip(p, alpha)]
+            dx = step if dx is None else [(dh + sh, dP + sP) for (dh, dP), (sh, sP) in zip(dx, step)]
+            if ii < num_cg_iter - 1:
+                r = [(rh - qh * al, rP - qP * al) for (rh, rP), (qh, qP), al in zip(r, q, alpha)]
+        if dx is not None:
+            for f, P, (dh, dP) in zip(filters, projections, dx):
+                f += torch.view_as_real(dh).unsqueeze(0)
+                P += dP
+    return filters, projections
+
+
+INIT_MAX_CIN, INIT_MAX_SAMPLES, INIT_MAX_CG, INIT_MAX_GN = 512, 64, 62, 32
+
+
+def covered_joint_init(filters, projections, samples, weights_sqrt, yf, reg_filters, diag_M, proj_precond, num_cg_iter, num_gn_iter) -> bool:
+    lists = [filters, projections, samples, weights_sqrt, yf, reg_filters, diag_M, proj_precond]
+    if not 1 <= len(filters) <= _lib.PT_ECO_MAX_BLOCKS or any(len(v) != len(filters) for v in lists):
+        return False
+    if not (isinstance(num_cg_iter, int) and isinstance(num_gn_iter, int) and 0 <= num_cg_iter <= INIT_MAX_CG and 0 <= num_gn_iter <= INIT_MAX_GN):
+        return False
+    for f, P, s, w, y, r, d in zip(filters, projections, samples, weights_sqrt, yf, reg_filters, diag_M):
+        if not (covered_series(f) and f.shape[0] == 1 and _dev_f32(P, 2)):
+            return False
+        _, c, Hf, Wh, _ = f.shape
+        if not (_dev_f32(s, 5) and tuple(s.shape[:2]) == (Hf, Wh) and s.shape[-1] == 2 and s.shape[3] == P.shape[0] and P.shape[1] == c):
+            return False
+        n, Cin = s.shape[2], s.shape[3]
+        if not (c <= 64 and 1 <= Cin <= INIT_MAX_CIN and 1 <= n <= INIT_MAX_SAMPLES and Hf * Wh <= 1 << 20):
+            return False
+        if not (_dev_f32(w) and w.numel() in (1, n) and _dev_f32(y) and y.numel() == Hf * Wh and _dev_f32(d) and d.numel() == c * Hf * Wh):
+            return False
+        if not (_dev_f32(r) and r.dim() in (2, 4) and r.numel() == r.shape[-2] * r.shape[-1] and max(r.shape[-2:]) <= 15):
+            return False
+        if not (_no_grad_needed(f, P, s, w, y, r, d) and len({t.device for t in (f, P, s, w, y, r, d)}) == 1):
+            return False
+    return True
+
+
+@device_guarded
+def joint_init(filters, projections, samples, weights_sqrt, yf, reg_filters, diag_M, proj_precond, num_cg_iter, num_gn_iter, projection_reg):
+    """GaussNewtonCG.run(num_cg_iter, num_gn_iter) on FactorizedConvProblem for all blocks in one call: `filters` (1, c, Hf, Wh, 2) and
+    `projections` (Cin, c) are updated IN PLACE (a strided one -- the tracker's projection matrix is a clone of a column slice and keeps
+    its strides -- through a dense copy that is written back).  samples (Hf, Wh, n, Cin, 2) uncompressed, weights_sqrt 1 or n entries, yf (Hf, Wh)-shaped,
+    reg_filters (Rh, Rw)-shaped, diag_M (c, Hf, Wh)-shaped and proj_precond (a float per block): the problem constructor's preconditioner.
+    Definition in include/pt_hot.h."""
+    _require_device(*filters)
+    if not covered_joint_init(filters, projections, samples, weights_sqrt, yf, reg_filters, diag_M, proj_precond, num_cg_iter, num_gn_iter):
+        raise NotImplementedError(f"joint init: device fp32 filters (1, c, Hf, Wh, 2) and projections (Cin, c), c <= 64, Cin <= "
+                                  f"{INIT_MAX_CIN}, n <= {INIT_MAX_SAMPLES}, reg filter <= 15 x 15, <= {INIT_MAX_CG} CG x {INIT_MAX_GN} GN iterations")
+    nb = len(filters)
+    keep, arr = [], (_lib.EcoInitBlock * nb)()
+    dense = [(t, t if t.is_contiguous() else t.contiguous()) for t in list(filters) + list(projections)]
+    for b, ((_, f), (_, P)) in enumerate(zip(dense[:nb], dense[nb:])):
+        _, c, Hf, Wh, _ = f.shape
+        ts = [samples[b].contiguous(), weights_sqrt[b].contiguous(), yf[b].contiguous(), reg_filters[b].contiguous(), diag_M[b].contiguous()]
+        keep += ts
+        arr[b] = _lib.EcoInitBlock(*[t.data_ptr() for t in ts], f.data_ptr(), P.data_ptr(), Hf, Wh, P.shape[0], c, ts[0].shape[2], ts[1].numel(),
+                                   ts[3].shape[-2], ts[3].shape[-1], float(proj_precond[b]))
+    L = _lib.lib()
+    ws = workspace(L.pt_eco_joint_init_ws_bytes(arr, nb), filters[0].device)
+    rc = L.pt_eco_joint_init_f32(arr, nb, int(num_gn_iter), int(num_cg_iter), float(projection_reg), _ptr(ws), ws.numel(), _stream())
+    _lib.check(rc, "pt_eco_joint_init_f32")
+    for t, d in dense:
+        if d is not t:
+            t.copy_(d)
+    return filters, projections
+
+
+def _joint_run_args(opt):
+    """joint_init's arguments from a reference GaussNewtonCG object on a FactorizedConvProblem (optim.py:9-31); None when the object is
+    not of that kind."""
+    prob, x = opt.problem, list(opt.x)
+    nb = len(x) // 2
+    if len(x) != 2 * nb or nb == 0 or getattr(prob, "sample_weights_sqrt", None) is None or len(prob.diag_M) != 2 * nb:
+        return None
+    if not all(isinstance(t, torch.Tensor) and t.dim() == 5 and t.shape[2:4] == (1, 1) for t in prob.yf):
+        return None
+    return dict(filters=x[:nb], projections=x[nb:], samples=list(prob.training_samples), weights_sqrt=list(prob.sample_weights_sqrt),
+                yf=[t[..., 0] for t in prob.yf], reg_filters=list(prob.reg_filter), diag_M=list(prob.diag_M[:nb]),
+                proj_precond=list(prob.diag_M[nb:]))
+
+
+def covered_joint_run(opt, num_cg_iter, num_gn_iter=None) -> bool:
+    """A `run(num_cg_iter, num_gn_iter)` of a GaussNewtonCG built by `gauss_newton_cg` that the kernels take: integer iteration counts of
+    at least 1 (zero iterations and lists keep the reference's own behaviour) on an object whose constructor found the kernel route."""
+    if not (getattr(opt, "_amd_route", False) and isinstance(num_cg_iter, int) and isinstance(num_gn_iter, int)):
+        return False
+    if num_cg_iter < 1 or num_gn_iter < 1:
+        return False
+    a = _joint_run_args(opt)
+    return a is not None and covered_joint_init(**a, num_cg_iter=num_cg_iter, num_gn_iter=num_gn_iter)
+
+
+def tracker_joint_run(opt, num_cg_iter, num_gn_iter=None):
+    """GaussNewtonCG.run (optimization.py:328-374) of a reference object: the tracker's `filter` and `projection_matrix` tensors are updated in
+    place, as `self.x += delta_x` does; `losses` and `residuals` stay the empty tensors of the constructor (debug is off)."""
+    a = _joint_run_args(opt)
+    a["proj_precond"] = [float(v) for v in a["proj_precond"]]
+    joint_init(**a, num_cg_iter=num_cg_iter, num_gn_iter=num_gn_iter, projection_reg=float(opt.problem.params.projection_reg))
+    return opt.losses, opt.residuals
+
+
+def gauss_newton_cg(ref_cls, problem_cls, on_run=None):
+    """The class for the name `pytracking.tracker.eco.eco.GaussNewtonCG` (eco.py:9): a subclass of the reference's `ref_cls` whose
+    constructor notes whether the kernels cover the object -- a `problem_cls` (eco.optim.FactorizedConvProblem) on device fp32 tensors,
+    debug / analyze / plotting off, the CG settings the tracker uses -- and whose `run` then goes to `tracker_joint_run`; every other object
+    and call (a list-valued num_cg_iter, CPU tensors, zero iterations) runs the reference's `run`.  `on_run(fast)` is told which."""
+    class GaussNewtonCG(ref_cls):
+        __doc__ = ref_cls.__doc__
+
+        def __init__(self, problem, variable, *args, **kw):
+            super().__init__(problem, variable, *args, **kw)
+            self._amd_route = bool(isinstance(problem, problem_cls) and not self.debug and self.fletcher_reeves and self.standard_alpha
+                                   and self.direction_forget_factor == 0 and self.cg_eps == 0
+                                   and all(isinstance(t, torch.Tensor) and _dev_f32(t) for t in variable))
+
+        def run(self, num_cg_iter, num_gn_iter=None):
+            fast = covered_joint_run(self, num_cg_iter, num_gn_iter)
+            if on_run is not None:
+                on_run(fast)
+            if fast:
+                return tracker_joint_run(self, num_cg_iter, num_gn_iter)
+            return super().run(num_cg_iter, num_gn_iter)
+
+    return GaussNewtonCG

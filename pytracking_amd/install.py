@@ -67,6 +67,9 @@ What gets rebound (import path = contract; nothing in the reference tree is edit
   localize_target / update_memory, pytracking.tracker.eco.optim.FilterOptim.run
                                              (ECO's per-frame Fourier-domain path and filter update; only with install(eco=True))
                                                                                       -> pytracking_amd.eco
+  pytracking.tracker.eco.eco.GaussNewtonCG   (the name eco.py:9 imported: ECO's first-frame joint Gauss-Newton optimisation of filter and
+                                             projection matrix; only with install(eco_init=True), meant to go with eco=True)
+                                                                                      -> pytracking_amd.eco
   ltr.models.transformer.filter_predictor.GOTFilterPredictor
                                              (TaMOs multi-object filter predictor, inference; only with install(tamos=True))
                                                                                       -> pytracking_amd.tamos
@@ -778,7 +781,7 @@ def _install_eco():
     `preprocess_sample`, `extract_fourier_sample`, `apply_filter`, `localize_target`, `update_memory` are dispatchers: CPU tensors,
     grad-enabled calls, other dtypes, debug >= 3, the 'transcale' fusion, a score grid equal to or smaller than the series and uncovered
     shapes keep the reference's code; so does `FilterOptim.run` (the filter update: all blocks, the CG state carried on the device).  The first-frame joint Gauss-Newton (whose problem class `_install_atom_cg`'s
-    dispatcher declines) and `symmetrize_filter` stay the reference's.  Off unless `install(eco=True)`: the set a default install() rebinds
+    dispatcher declines; `_install_eco_init` has its kernels) and `symmetrize_filter` stay the reference's.  Off unless `install(eco=True)`: the set a default install() rebinds
     is pinned."""
     from . import eco as _eco
     try:
@@ -812,6 +815,28 @@ def _install_eco():
     ocls = importlib.import_module("pytracking.tracker.eco.optim").FilterOptim
     _rebind(ocls, "run", _dispatcher(ocls.run, "FilterOptim.run", _eco.covered_filter_run, _eco.tracker_filter_run,
                                      "FilterOptim.run: call outside the gfx950 hot path"))
+
+
+def _install_eco_init():
+    """ECO's first-frame joint optimisation (eco.py:152-158).  Exactly one name is rebound: `pytracking.tracker.eco.eco.GaussNewtonCG`, which
+    eco.py:9 imported by value, to a subclass of the reference's class whose `run` takes the kernels (pytracking_amd.eco.joint_init) for an
+    `eco.optim.FactorizedConvProblem` on device fp32 tensors with debug off and integer iteration counts; every other object or call runs
+    the reference's `run` (or raises under strict).  `pytracking.libs.optimization.GaussNewtonCG` is not touched: ATOM's dispatcher goes on
+    declining ECO's problem.  Counters: `ECO.GaussNewtonCG.run.fast` / `.reference`.  Off unless `install(eco_init=True)`."""
+    from . import eco as _eco
+    try:
+        emod = importlib.import_module("pytracking.tracker.eco.eco")
+        problem_cls = importlib.import_module("pytracking.tracker.eco.optim").FactorizedConvProblem
+    except Exception:
+        return
+    bound = emod.GaussNewtonCG
+    ref = getattr(bound, "_pt_reference", bound)              # under a default install() the name may hold ATOM's choosing class
+
+    def on_run(fast):
+        if not _hit("ECO.GaussNewtonCG.run", fast):
+            _outside("ECO.GaussNewtonCG.run: call outside the gfx950 hot path")
+
+    _rebind(emod, "GaussNewtonCG", _eco.gauss_newton_cg(ref, problem_cls, on_run))
 
 
 def _install_gn_hinge():
@@ -952,7 +977,7 @@ def _install_atom_cg():
 
 def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=True, iou_refine=True, preprocessing=True,
             candidate_matching=True, kys=True, iou_feat=False, label_encoder=False, decoder=False, feature_heads=False,
-            rts_fusion=False, seg_readout=False, eco=False, tamos=False, box_encoder=False):
+            rts_fusion=False, seg_readout=False, eco=False, tamos=False, box_encoder=False, eco_init=False):
     """Rebind the boundary symbols.  Call after the reference is importable (`sys.path`) and before networks or
     trackers are constructed.  Idempotent.  If an installer raises, what was rebound so far is undone before the exception
     propagates (an optional reference module that does not import is not a failure: its family is skipped)."""
@@ -975,7 +1000,7 @@ def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=T
                                 (iou_feat, _install_iou_feat), (label_encoder, _install_label_encoder),
                                 (decoder, _install_lwl_decoder), (rts_fusion, _install_rts_fusion),
                                 (seg_readout, _install_seg_readout), (eco, _install_eco), (tamos, _install_tamos),
-                                (box_encoder, _install_box_encoder)):
+                                (box_encoder, _install_box_encoder), (eco_init, _install_eco_init)):
             if flag:
                 installer()
     except BaseException:
