@@ -5,12 +5,13 @@ resnet.py:15-53 for the block; blocks.py:4-20 for conv_block), for the tests tha
 what the kernels compute from the pack (include/pt_hot.h); and the float64 anchor of a case.  Test infrastructure only."""
 import copy
 import os
-from collections import OrderedDict, namedtuple
+from collections import OrderedDict
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
+import f64_bound
 from pytracking_amd import synth
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -19,9 +20,8 @@ KINDS = (BOX, CAT)
 CASES = {BOX: tuple(synth.BOX_ENC_CASES), CAT: tuple(synth.BOX_CAT_ENC_CASES)}
 ALL = tuple((kind, name) for kind in KINDS for name in CASES[kind])
 STORED_STATE_FLOATS = 150_000          # a golden holds the state dict up to this size, beyond it the seed and a float64 checksum
-THREADS = 8                            # of the fp32 CPU run whose distance from float64 is ref_err (tests/fused_f64.py)
-Anchor = namedtuple("Anchor", "want ref_err ref_errs")
-_CACHE, _ANCHORS = {}, {}
+THREADS = f64_bound.THREADS            # of the fp32 CPU run whose distance from float64 is ref_err
+_CACHE = {}
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -212,37 +212,16 @@ def run(kind, net, args, c):
     return OrderedDict((q, out[k].reshape(-1, *out[k].shape[-3:])) for k, q in enumerate(outputs(kind, c)))
 
 
-def anchor_of(kind, net, c, boxes, feat):
-    """Anchor of the fp32 CPU stand-in `net`: `want` = the same module in float64, ref_err = the fp32 run's distance from it with the
-    threads pinned (the CPU convolutions block their sums by the thread count)."""
-    want = run(kind, copy.deepcopy(net).double(), call_args(kind, c, boxes, feat, dtype=torch.float64), c)
-    threads = torch.get_num_threads()
-    try:
-        torch.set_num_threads(THREADS)
-        f32 = run(kind, net, call_args(kind, c, boxes, feat), c)
-    finally:
-        torch.set_num_threads(threads)
-    errs = OrderedDict((q, float((f32[q].double() - t).abs().max())) for q, t in want.items())
-    want = OrderedDict((q, t.numpy()) for q, t in want.items())
-    for v in want.values():
-        v.setflags(write=False)
-    return Anchor(want, max(errs.values()), errs)
-
-
 def anchor(kind, name):
-    if (kind, name) not in _ANCHORS:
+    """Anchor (tests/f64_bound.py) of the fp32 CPU stand-in: `want` = the same module in float64, ref_err = the fp32 run's distance from
+    it with the threads pinned (the CPU convolutions block their sums by the thread count)."""
+    def in_dtype(dtype):
         _, c, _, boxes, feat = case(kind, name)
-        _ANCHORS[(kind, name)] = anchor_of(kind, module(kind, name), c, boxes, feat)
-    return _ANCHORS[(kind, name)]
-
-
-def ulp_of_range(want):
-    """One fp32 ulp at the largest magnitude of the outputs."""
-    return float(np.spacing(np.float32(max(float(np.abs(w).max()) for w in want.values()))))
-
-
-def errors(want, got):
-    return OrderedDict((q, float(np.abs(np.asarray(got[q], dtype=np.float64).reshape(w.shape) - w).max())) for q, w in want.items())
+        net = module(kind, name)
+        if dtype == np.float32:
+            return run(kind, net, call_args(kind, c, boxes, feat), c)
+        return run(kind, copy.deepcopy(net).double(), call_args(kind, c, boxes, feat, dtype=torch.float64), c)
+    return f64_bound.anchor(("box_enc", kind, name), in_dtype, threads=THREADS)
 
 
 def shift_visible(kind, name):

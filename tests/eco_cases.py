@@ -14,10 +14,11 @@ from collections import OrderedDict
 
 import numpy as np
 
+import f64_bound
 from pytracking_amd import synth
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-EPS = 2.0 ** -23
+EPS = f64_bound.ULP            # one fp32 ulp of 1, under the name tools/make_golden_eco_init.py and tests/test_eco_cpu.py use
 SAMPLE_ENTRIES = 256          # entries of a large output a golden keeps (seeded positions)
 
 
@@ -198,13 +199,6 @@ def insert_np(mem, xf, ind, shift=None):
     out = np.array(mem, dtype=np.float64)
     out[:, :, ind] = to_r(z)[0].transpose(1, 2, 0, 3)
     return out
-
-
-def bound(ref_fp32_err, want):
-    """The project's bound of an fp32 output against float64 (tests/fused_f64.py): FACTOR x the larger of the reference's own fp32 error
-    on the case and one fp32 ulp of the largest value."""
-    import fused_f64
-    return fused_f64.FACTOR * max(float(ref_fp32_err), EPS * float(np.abs(want).max()))
 
 
 def sample_positions(seed, size):

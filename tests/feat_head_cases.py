@@ -2,18 +2,18 @@
 cases of the LWL / RTS feature heads (synth.FEAT_HEAD_CASES) with their seeded inputs and weights, the plain-torch stand-in of the head --
 `F.conv2d(stride, padding=1)` followed by the expression of InstanceL2Norm (ltr/models/layers/normalization.py:15-18) -- for the tests that
 must not read the reference tree, and its float64 anchor: for a case the stand-in runs once in float64 on the CPU (`want`) and once in
-fp32 on the CPU with fused_f64.THREADS threads; `ref_err` is the largest |fp32 - float64|, what fp32 arithmetic costs on this very case in
-an order of summation nobody tuned.  A device output is held to FACTOR x ref_err of `want`.  FACTOR starts from fused_f64.FACTOR;
+fp32 on the CPU with f64_bound.THREADS threads; `ref_err` is the largest |fp32 - float64|, what fp32 arithmetic costs on this very case in
+an order of summation nobody tuned.  A device output is held to the bound of tests/f64_bound.py, FACTOR x ref_err of `want`;
 tests/test_feat_head_cpu.py fails if it is raised until a head with 10-bit weights or with a shifted tap origin passes.  Test
 infrastructure only."""
 import os
-from collections import namedtuple
+from collections import OrderedDict
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-import fused_f64 as F64
+import f64_bound
 from pytracking_amd import synth
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -21,13 +21,8 @@ CASES = tuple(synth.FEAT_HEAD_CASES)
 SCALE, EPS = synth.FEAT_HEAD_SCALE, 1e-5
 SEED = 2300                                   # case k: inputs and weights from SEED + k
 X_STORED_MAX = 4096                           # a golden stores its input up to this many values; larger ones are regenerated from the seed
-FACTOR = F64.FACTOR
-Anchor = namedtuple("Anchor", "want ref_err")  # float64 numpy (read-only), float
+FACTOR = f64_bound.FACTOR
 _CACHE = {}
-
-
-def bound(ref_err):
-    return FACTOR * ref_err
 
 
 def out_hw(H, W, stride):
@@ -50,20 +45,11 @@ def standin(x, w, stride, scale=SCALE, eps=EPS, origin=-1):
 
 
 def anchor(key, x, w, stride, scale=SCALE, eps=EPS):
-    """Anchor of the stand-in on the CPU tensors (x, w), computed once per session under `key`."""
-    if key not in _CACHE:
-        want = standin(x.double(), w.double(), stride, scale, eps)
-        threads = torch.get_num_threads()
-        try:
-            torch.set_num_threads(F64.THREADS)
-            f32 = standin(x, w, stride, scale, eps)
-        finally:
-            torch.set_num_threads(threads)
-        err = float((f32.double() - want).abs().max())
-        want = want.numpy()
-        want.setflags(write=False)
-        _CACHE[key] = Anchor(want, err)
-    return _CACHE[key]
+    """Anchor of the stand-in on the CPU tensors (x, w), computed once per session under `key`; `want` is the one output's array."""
+    def run(dtype):
+        return OrderedDict(y=standin(x, w, stride, scale, eps) if dtype == np.float32 else standin(x.double(), w.double(), stride, scale, eps))
+    a = f64_bound.anchor(("feat_head", key), run, threads=f64_bound.THREADS)
+    return a._replace(want=a.want["y"])
 
 
 def small(name, stride=2):
@@ -85,12 +71,3 @@ def deployed(n, stride, seed):
 
 def golden(name):
     return dict(np.load(os.path.join(GOLDEN, f"feat_head_{name}.npz")))
-
-
-def max_err(want, got):
-    return float(np.abs(got.detach().double().cpu().numpy().reshape(want.shape) - want).max())
-
-
-def report(tag, err, ref_err):
-    """The line every test prints before it asserts."""
-    return f"\n{tag}: max |out - float64| {err:.3e} ({err / ref_err:.2f}x)  ref_err {ref_err:.3e}, bound {bound(ref_err):.3e}"

@@ -4,34 +4,25 @@ tests/test_gpu_fused_f64.py.  For a module instance and its inputs the plain-tor
 tests/label_enc_cases.py, tests/lwl_decoder_cases.py) runs once in float64 on the CPU (`want`, per output tensor) and once in fp32 on the
 CPU; `ref_err` is the largest |fp32 - float64| over all outputs of the case: what fp32 arithmetic costs on this very case in an order of
 summation nobody tuned.  A device output is held to bound(ref_err) = FACTOR * ref_err of `want`, as tests/test_gpu_kys.py holds the cost
-volume to 4 x its golden's ref_fp32_err.  FACTOR is defined here and nowhere else; tests/test_fused_bounds_cpu.py fails if it is raised
-until a doubled BatchNorm eps or a convolution with 10-bit weights passes.  Reads nothing outside the repository.  Test infrastructure
+volume to 4 x its golden's ref_fp32_err.  The anchor, FACTOR and the bound are those of tests/f64_bound.py; tests/test_fused_bounds_cpu.py
+fails if FACTOR is raised until a doubled BatchNorm eps or a convolution with 10-bit weights passes.  Reads nothing outside the repository.  Test infrastructure
 only."""
 import copy
-from collections import OrderedDict, namedtuple
+from collections import OrderedDict
 
 import numpy as np
 import torch
 
+import f64_bound
 import iou_feat_cases as IC
 import label_enc_cases as LC
 import lwl_decoder_cases as DC
+from f64_bound import FACTOR, THREADS, bound, errors, report  # noqa: F401  (tests/f64_bound.py's, re-exported to the users of this module)
 
-FACTOR = 4
-# The CPU convolutions block their sums by the number of threads, so the fp32 run's rounding -- ref_err -- moves by tens of per cent with
-# it.  The goldens' ref_fp32_err were written with 8 threads; the fp32 run is pinned to that so that ref_err does not follow the ambient
-# thread count (a CPU with another vector width may still round differently: tests/test_fused_bounds_cpu.py compares with the goldens).
-THREADS = 8
 KINDS = ("iou_feat", "label_enc", "lwl_decoder")
 SMALL = {"iou_feat": IC.SMALL, "label_enc": tuple(c for c in LC.CASES if c != "deployed"),
          "lwl_decoder": tuple(c for c in DC.CASES if c != "deployed")}
 DEPLOYED = {"iou_feat": IC.DEPLOYED, "label_enc": ("deployed",), "lwl_decoder": ("deployed",)}
-Anchor = namedtuple("Anchor", "want ref_err ref_errs")        # {output: float64 numpy, read-only}, float, {output: float}
-_CACHE = {}
-
-
-def bound(ref_err):
-    return FACTOR * ref_err
 
 
 def convert(args, device=None, dtype=None):
@@ -61,21 +52,11 @@ def standin(kind, net, args):
 
 def anchor(kind, key, net, args):
     """Anchor of the fp32 CPU stand-in `net` on the CPU arguments `args`, computed once per session under (kind, key)."""
-    if (kind, key) not in _CACHE:
-        f64 = standin(kind, copy.deepcopy(net).double(), convert(args, dtype=torch.float64))
-        threads = torch.get_num_threads()
-        try:
-            torch.set_num_threads(THREADS)
-            f32 = standin(kind, net, args)
-        finally:
-            torch.set_num_threads(threads)
-        want, errs = OrderedDict(), OrderedDict()
-        for q, t in f64.items():
-            want[q] = t.numpy()
-            want[q].setflags(write=False)
-            errs[q] = float((f32[q].double() - t).abs().max())
-        _CACHE[(kind, key)] = Anchor(want, max(errs.values()), errs)
-    return _CACHE[(kind, key)]
+    def run(dtype):
+        if dtype == np.float32:
+            return standin(kind, net, args)
+        return standin(kind, copy.deepcopy(net).double(), convert(args, dtype=torch.float64))
+    return f64_bound.anchor(("fused", kind, key), run, threads=THREADS)
 
 
 def committed_case(kind, name):
@@ -94,14 +75,3 @@ def committed_case(kind, name):
 def committed(kind, name):
     net, args, _ = committed_case(kind, name)
     return anchor(kind, ("committed", name), net, args)
-
-
-def errors(want, got):
-    """{output: max |got - want|} for device or CPU tensors `got` against an Anchor's `want`."""
-    return OrderedDict((q, float(np.abs(got[q].detach().double().cpu().numpy().reshape(w.shape) - w).max())) for q, w in want.items())
-
-
-def report(tag, errs, ref_err):
-    """The line every test prints before it asserts: per output the measured error and its ratio to ref_err."""
-    return (f"\n{tag}: max |out - float64| " + "  ".join(f"{q} {e:.3e} ({e / ref_err:.2f}x)" for q, e in errs.items())
-            + f"  ref_err {ref_err:.3e}, bound {bound(ref_err):.3e}")

@@ -3,16 +3,16 @@ the golden cases (synth.SCORE_ENC_CASES, synth.LEARNERS_FUSE_CASES, chain_deploy
 with the layer structure of ResidualDS16SW_Clf (ltr/models/rts/label_encoder.py:57-103; resnet.py:15-53 for the block) and LearnersFusion
 (ltr/models/rts/learners_fusion.py) under the reference's attribute names for the tests that must not read the reference tree, the float64
 restatement of the folded-pack arithmetic and of the resize rule the kernels implement (include/pt_hot.h), and the float64 anchor of a case
-(bound = fused_f64.FACTOR x the fp32 CPU stand-in's own distance from float64).  Test infrastructure only."""
+(tests/f64_bound.py: bound = FACTOR x the fp32 CPU stand-in's own distance from float64).  Test infrastructure only."""
 import copy
 import os
-from collections import OrderedDict, namedtuple
+from collections import OrderedDict
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-import fused_f64
+import f64_bound
 from pytracking_amd import synth
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -21,8 +21,7 @@ FUSE_CASES = tuple(synth.LEARNERS_FUSE_CASES)
 FUSION_TYPES = tuple(synth.FUSION_TYPES)
 CHAIN = "chain_deployed"
 ENC_STATE_SEED, ENC_INPUT_SEED, FUSE_STATE_SEED, FUSE_INPUT_SEED, CHAIN_SEED = 2600, 2700, 2800, 2900, 2990
-Anchor = namedtuple("Anchor", "want ref_err ref_errs")        # {output: float64 numpy, read-only}, float, {output: float}
-_CACHE, _ANCHORS = {}, {}
+_CACHE = {}
 
 
 class BasicBlock(torch.nn.Module):
@@ -224,24 +223,12 @@ def fuse_from_pack(kind, pack, seg, clf):
 # ---- the float64 anchor -----------------------------------------------------------------------------------------------------------------
 def anchor(key, run, nets, args):
     """Anchor of one case, once per session: run(nets, args) -> OrderedDict {output: tensor} is called with float64 copies of the fp32 CPU
-    stand-ins `nets` and inputs `args`, and with the fp32 ones under fused_f64.THREADS threads (the count the goldens' ref_fp32_err were
+    stand-ins `nets` and inputs `args`, and with the fp32 ones under f64_bound.THREADS threads (the count the goldens' ref_fp32_err were
     written with); ref_err = the largest |fp32 - float64| over all outputs."""
-    if key not in _ANCHORS:
+    def in_dtype(dtype):
         with torch.no_grad():
-            f64 = run([copy.deepcopy(m).double() for m in nets], [a.double() for a in args])
-            threads = torch.get_num_threads()
-            try:
-                torch.set_num_threads(fused_f64.THREADS)
-                f32 = run(nets, args)
-            finally:
-                torch.set_num_threads(threads)
-        want, errs = OrderedDict(), OrderedDict()
-        for q, t in f64.items():
-            want[q] = t.numpy()
-            want[q].setflags(write=False)
-            errs[q] = float((f32[q].double() - t).abs().max())
-        _ANCHORS[key] = Anchor(want, max(errs.values()), errs)
-    return _ANCHORS[key]
+            return run(nets, args) if dtype == np.float32 else run([copy.deepcopy(m).double() for m in nets], [a.double() for a in args])
+    return f64_bound.anchor(("rts_fusion",) + key, in_dtype, threads=f64_bound.THREADS)
 
 
 def run_enc(nets, args):

@@ -6,21 +6,18 @@ classifier's scores, whose D-term dot products carry ten times the predictor's e
 numpy's BLAS blocks its sums by the thread count, so ref_err moves with the machine: tamos_cases.REF_ERR carries the values measured where
 the table was written, the CPU test holds the recomputed value to [0.5, 2] x the committed one, and the GPU test uses the committed one.
 
-F starts from the fused modules' FACTOR (tests/fused_f64.py).  After the MI355X run every ratio is in profiles/tamos_f64.txt; where the
-worst is at most FACTOR / 2, F stays FACTOR, otherwise ceil(2 x worst), and never above F_MAX = 8: the weakest seeded defect of
+The anchor, the bound and the report are those of tests/f64_bound.py; F starts from its FACTOR.  After the MI355X run every ratio is in
+profiles/tamos_f64.txt; where the worst is at most FACTOR / 2, F stays FACTOR, otherwise ceil(2 x worst), and never above F_MAX = 8: the weakest seeded defect of
 tests/test_tamos_cpu.py, a LayerNorm eps of 2e-5, sits at 8 - 13 x ref_err and has to fail.
 
 `python tests/tamos_f64.py` prints the ROUTES_TEXT and REF_ERR tables of tests/tamos_cases.py from the built library and this CPU.
 Reads nothing outside the repository.  Test infrastructure only."""
-import math
 import os
 import sys
-from collections import OrderedDict, namedtuple
-
-import numpy as np
+from collections import OrderedDict
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from fused_f64 import FACTOR                   # noqa: E402
+import f64_bound                               # noqa: E402
 import tamos_cases as TC                       # noqa: E402
 import tamos_np as TN                          # noqa: E402
 
@@ -28,17 +25,14 @@ F_MAX = 8
 # The largest max |MI355X - float64| / ref_err over every output of every case (profiles/tamos_f64.txt: the filters of mask9_gth0; three more
 # outputs at 2.8 - 2.9, all on D >= 256).  Above FACTOR / 2 = 2, so F is twice it, rounded up.
 WORST_MEASURED = 3.13
-F = FACTOR if WORST_MEASURED <= FACTOR / 2 else math.ceil(2 * WORST_MEASURED)
-assert FACTOR <= F <= F_MAX
+F = f64_bound.raised_factor(WORST_MEASURED, F_MAX)
 REF_ERR_BAND = (0.5, 2.0)
 
 PREDICTOR = ("cls_filter", "bbreg_filter", "cls_enc", "bbreg_enc", "filter", "enc")
-Anchor = namedtuple("Anchor", "want f32 ref_err ref_errs")
-_CACHE = {}
 
 
 def bound(ref_err):
-    return F * ref_err
+    return f64_bound.bound(ref_err, F)
 
 
 def group(output):
@@ -60,52 +54,8 @@ def outputs(name, dtype, defect=None):
     return OrderedDict((("filter", w), ("enc", enc), ("scores", TN.classifier_scores(p, enc, w))))
 
 
-def want(name):
-    if ("want", name) not in _CACHE:
-        out = outputs(name, np.float64)
-        for v in out.values():
-            assert v.dtype == np.float64
-            v.setflags(write=False)
-        _CACHE[("want", name)] = out
-    return _CACHE[("want", name)]
-
-
-def errors_np(w, got):
-    return OrderedDict((q, float(np.abs(np.asarray(got[q], dtype=np.float64).reshape(v.shape) - v).max())) for q, v in w.items())
-
-
-def by_group(errs):
-    out = OrderedDict()
-    for q, e in errs.items():
-        out[group(q)] = max(out.get(group(q), 0.0), e)
-    return out
-
-
 def anchor(name):
-    if ("anchor", name) not in _CACHE:
-        w = want(name)
-        f32 = outputs(name, np.float32)
-        assert all(v.dtype == np.float32 for v in f32.values()), {q: v.dtype for q, v in f32.items()}
-        errs = errors_np(w, f32)
-        _CACHE[("anchor", name)] = Anchor(w, f32, by_group(errs), errs)
-    return _CACHE[("anchor", name)]
-
-
-def within(errs, ref_err):
-    return all(e <= bound(ref_err[group(q)]) for q, e in errs.items())
-
-
-def errors(w, got):
-    return errors_np(w, {q: got[q].detach().double().cpu().numpy() for q in w})
-
-
-def ratios(errs, ref_err):
-    return OrderedDict((q, e / ref_err[group(q)]) for q, e in errs.items())
-
-
-def report(tag, errs, ref_err):
-    return (f"\n{tag}: max |out - float64| " + "  ".join(f"{q} {e:.3e} ({e / ref_err[group(q)]:.2f}x)" for q, e in errs.items())
-            + "  ref_err " + " ".join(f"{g} {r:.3e}" for g, r in ref_err.items()) + f", bound {F} x ref_err")
+    return f64_bound.anchor(("tamos", name), lambda dtype: outputs(name, dtype), group)
 
 
 def _main():

@@ -5,21 +5,20 @@ built like tests/tamos_f64.py.  For a case the numpy restatement (tests/tamos_he
 numpy's BLAS blocks its sums by the thread count, so ref_err moves with the machine: tamos_heads_cases.REF_ERR carries the values measured
 where the table was written, the CPU test holds the recomputed value to [0.5, 2] x the committed one, and the GPU test uses the committed one.
 
-F starts from the fused modules' FACTOR (tests/fused_f64.py).  After the MI355X run every ratio is in profiles/tamos_heads_f64.txt; where the
-worst is at most FACTOR / 2, F stays FACTOR, otherwise ceil(2 x worst), and never above F_MAX: the weakest seeded defect of
+The anchor, the bound and the report are those of tests/f64_bound.py; F starts from its FACTOR.  After the MI355X run every ratio is in
+profiles/tamos_heads_f64.txt; where the worst is at most FACTOR / 2, F stays FACTOR, otherwise ceil(2 x worst), and never above F_MAX: the weakest seeded defect of
 tests/test_tamos_heads_cpu.py has to fail (see F_MAX below).
 
 `python tests/tamos_heads_f64.py` prints the ROUTES_TEXT and REF_ERR tables of tests/tamos_heads_cases.py from the built library and this CPU.
 Reads nothing outside the repository.  Test infrastructure only."""
-import math
 import os
 import sys
-from collections import OrderedDict, namedtuple
+from collections import OrderedDict
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from fused_f64 import FACTOR                   # noqa: E402
+import f64_bound                               # noqa: E402
 import tamos_heads_cases as HC                 # noqa: E402
 import tamos_heads_np as HN                    # noqa: E402
 
@@ -29,18 +28,10 @@ F_MAX = 8
 # The largest max |MI355X - float64| / ref_err over every output of every case (profiles/tamos_heads_f64.txt: feat2 of fpn_x2; the FPN's
 # high-resolution map sits at 3.4 - 4.0 everywhere, the regressor at 1.3 - 2.5).  Above FACTOR / 2 = 2, so F is twice it, rounded up.
 WORST_MEASURED = 3.96
-F = FACTOR if WORST_MEASURED <= FACTOR / 2 else math.ceil(2 * WORST_MEASURED)
-assert FACTOR <= F <= F_MAX
+F = f64_bound.raised_factor(WORST_MEASURED, F_MAX)
 REF_ERR_BAND = (0.5, 2.0)
 # defect -> the small cases on which it has to exceed F_MAX x ref_err
 DEFECT_CASES = {"gn_eps": HC.SMALL_REG, "halo": HC.SMALL_REG, "stats_nobias": HC.SMALL_REG, "nearest_round": HC.SMALL_FPN}
-
-Anchor = namedtuple("Anchor", "want f32 ref_err")
-_CACHE = {}
-
-
-def bound(ref_err):
-    return F * ref_err
 
 
 def outputs(name, dtype, defect=None):
@@ -58,40 +49,8 @@ def outputs(name, dtype, defect=None):
     return OrderedDict(feat2=f2, ltrb=HN.regressor({k: v.astype(dtype) for k, v in rp.items()}, f2, filt.astype(dtype), defect))
 
 
-def want(name):
-    if ("want", name) not in _CACHE:
-        out = outputs(name, np.float64)
-        for v in out.values():
-            assert v.dtype == np.float64
-            v.setflags(write=False)
-        _CACHE[("want", name)] = out
-    return _CACHE[("want", name)]
-
-
-def errors_np(w, got):
-    return OrderedDict((q, float(np.abs(np.asarray(got[q], dtype=np.float64).reshape(v.shape) - v).max())) for q, v in w.items())
-
-
 def anchor(name):
-    if ("anchor", name) not in _CACHE:
-        w = want(name)
-        f32 = outputs(name, np.float32)
-        assert all(v.dtype == np.float32 for v in f32.values())
-        _CACHE[("anchor", name)] = Anchor(w, f32, max(errors_np(w, f32).values()))
-    return _CACHE[("anchor", name)]
-
-
-def errors(w, got):
-    return errors_np(w, {q: got[q].detach().double().cpu().numpy() for q in w})
-
-
-def within(errs, ref_err):
-    return all(e <= bound(ref_err) for e in errs.values())
-
-
-def report(tag, errs, ref_err):
-    return (f"\n{tag}: max |out - float64| " + "  ".join(f"{q} {e:.3e} ({e / ref_err:.2f}x)" for q, e in errs.items())
-            + f"  ref_err {ref_err:.3e}, bound {F} x ref_err")
+    return f64_bound.anchor(("tamos_heads", name), lambda dtype: outputs(name, dtype))
 
 
 def _main():
@@ -109,7 +68,7 @@ def _main():
     print("}")
     for defect, cases in DEFECT_CASES.items():
         for name in cases:
-            e = max(errors_np(want(name), outputs(name, np.float32, defect)).values())
+            e = max(f64_bound.errors(anchor(name).want, outputs(name, np.float32, defect)).values())
             print(f"defect {defect:14s} {name:22s} {e:.3e} = {e / anchor(name).ref_err:7.1f} x ref_err", flush=True)
 
 

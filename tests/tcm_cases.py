@@ -4,17 +4,17 @@ of k_tcm_peaks, more than 1024 hits, non-square maps, other window sizes, ties a
 point counts around the 16-point pass and both coordinate forms; matcher runs with unequal image sizes, other layer lists, zero and one
 Sinkhorn iteration and token counts around the 16-token tile of k_tcm_linear.
 
-The anchor of every case is the float64 restatement tests/tcm_np.py (`want`).  ref_err is the convention of tests/fused_f64.py: the same
-operation in fp32 on the CPU (torch.nn.functional.conv2d read at the points; the reference's own SuperGlue), pinned to fused_f64.THREADS
-threads, ref_err = max |fp32 - float64| over the descriptor tensor / over log_assignment; a device output is held to fused_f64.bound(ref_err).
+The anchor of every case is the float64 restatement tests/tcm_np.py (`want`).  ref_err is that of tests/f64_bound.py: the same
+operation in fp32 on the CPU (torch.nn.functional.conv2d read at the points; the reference's own SuperGlue), pinned to f64_bound.THREADS
+threads, ref_err = max |fp32 - float64| over the descriptor tensor / over log_assignment; a device output is held to f64_bound.bound(ref_err).
 Reads nothing outside the repository (the matcher's ref_err needs the reference through oracle.ref_harness).  Test infrastructure only."""
 from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
 
+import f64_bound
 import tcm_np
-from fused_f64 import THREADS, bound  # noqa: F401  (bound is re-exported to the tests)
 from pytracking_amd import synth
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -97,7 +97,6 @@ DESC_CASES = OrderedDict([
     ("c16", (1, 16, 22, 22, 64, 33, "shared", 2210)),          # a single K slice
 ])
 DescInputs = namedtuple("DescInputs", "x weight bias coords coords3")   # coords as the caller passes them; coords3 (B, P, 2) int64
-Anchor = namedtuple("Anchor", "want ref_err")
 _CACHE = {}
 
 
@@ -129,24 +128,15 @@ def conv2d_at_points(x, weight, bias, coords3, dtype):
     return torch.stack([full[b][:, c[b, :, 0], c[b, :, 1]] for b in range(full.shape[0])]).numpy()
 
 
-def _pinned(fn):
-    threads = torch.get_num_threads()
-    try:
-        torch.set_num_threads(THREADS)
-        return fn()
-    finally:
-        torch.set_num_threads(threads)
-
-
 def desc_anchor(name):
-    """Anchor(want (B, D, P) float64 read-only, ref_err), once per session."""
-    if ("desc", name) not in _CACHE:
+    """Anchor (tests/f64_bound.py) with want (B, D, P) float64 read-only, once per session."""
+    def run(dtype):
         i = desc_inputs(name)
-        want = tcm_np.get_descriptors(i.x, i.weight, i.bias, i.coords3)
-        want.setflags(write=False)
-        f32 = _pinned(lambda: conv2d_at_points(i.x, i.weight, i.bias, i.coords3, torch.float32))
-        _CACHE[("desc", name)] = Anchor(want, float(np.abs(f32.astype(np.float64) - want).max()))
-    return _CACHE[("desc", name)]
+        if dtype == np.float32:
+            return OrderedDict(desc=conv2d_at_points(i.x, i.weight, i.bias, i.coords3, torch.float32))
+        return OrderedDict(desc=tcm_np.get_descriptors(i.x, i.weight, i.bias, i.coords3))
+    a = f64_bound.anchor(("tcm_desc", name), run, threads=f64_bound.THREADS)
+    return a._replace(want=a.want["desc"])
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -221,15 +211,9 @@ def reference_match(name, dtype):
 
 
 def match_anchor(name):
-    """Anchor(want, ref_err = max |reference fp32 log_assignment - float64|), once per session.  Needs the reference."""
-    if ("match_anchor", name) not in _CACHE:
-        want = match_want(name)
-        f32 = _pinned(lambda: reference_match(name, torch.float32))
-        _CACHE[("match_anchor", name)] = Anchor(want, float(np.abs(f32["log_assignment"].astype(np.float64) - want["log_assignment"]).max()))
-    return _CACHE[("match_anchor", name)]
-
-
-def report(tag, errs, ref_err):
-    """The line a test prints before it asserts: per output the measured error and its ratio to ref_err."""
-    return (f"\n{tag}: max |out - float64| " + "  ".join(f"{q} {e:.3e} ({e / ref_err:.2f}x)" for q, e in errs.items())
-            + f"  ref_err {ref_err:.3e}, bound {bound(ref_err):.3e}")
+    """Anchor (tests/f64_bound.py) with want = match_want(name) and ref_err = max |reference fp32 log_assignment - float64|, once per
+    session.  Needs the reference."""
+    def run(dtype):
+        out = match_want(name) if dtype == np.float64 else reference_match(name, torch.float32)
+        return OrderedDict(log_assignment=out["log_assignment"])
+    return f64_bound.anchor(("tcm_match", name), run, threads=f64_bound.THREADS)._replace(want=match_want(name))

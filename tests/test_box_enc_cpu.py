@@ -15,7 +15,7 @@ import pytest
 import torch
 
 import box_enc_cases as BC
-import fused_f64 as F64
+import f64_bound
 from oracle import ref_harness
 from pytracking_amd import _lib, box_encoder as BE, synth
 
@@ -287,10 +287,10 @@ def test_bound_rejects_perturbed_standins(kind, name):
     the box moved by a pixel all fail, on every case whose input can show a moved box (box_enc_cases.shift_visible)."""
     _, c, _, boxes, feat = BC.case(kind, name)
     a = BC.anchor(kind, name)
-    bound = F64.FACTOR * max(a.ref_err, BC.ulp_of_range(a.want))
+    bound = f64_bound.bound(a.ref_err, floor=f64_bound.spacing_of_max(a.want))
     for what in ("eps", "weights", "box"):
         out = BC.run(kind, _perturbed(kind, name, what), BC.call_args(kind, c, boxes, feat, dtype=torch.float64), c)
-        err = max(BC.errors(a.want, {q: t.numpy() for q, t in out.items()}).values())
+        err = max(f64_bound.errors(a.want, {q: t.numpy() for q, t in out.items()}).values())
         print(f"\n{kind}_{name} {what}: max |perturbed - float64| = {err:.3e} ({err / bound:.1f} x the bound {bound:.3e})")
         assert err > bound, (what, err, bound)
 

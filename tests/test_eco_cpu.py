@@ -16,6 +16,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
+import f64_bound  # noqa: E402
 import eco_cases as EC  # noqa: E402
 import eco_shim  # noqa: E402
 from oracle import ref_harness  # noqa: E402
@@ -82,7 +83,7 @@ def check_case(g, key, seed, want, got32, shifted=False):
     assert abs(np.abs(want).max() - float(g[key + "/max_abs"])) <= tol
     assert np.abs(at_positions(got32, seed) - g[key + "/out"]).max() <= 1e-4, key
     err = float(np.abs(got32.astype(np.float64) - want).max())
-    assert err <= EC.bound(g[key + "/ref_fp32_err"], want), (key, err, float(g[key + "/ref_fp32_err"]))
+    assert err <= f64_bound.bound(g[key + "/ref_fp32_err"], floor=f64_bound.ulp_of_max(want)), (key, err, float(g[key + "/ref_fp32_err"]))
 
 
 @pytest.mark.parametrize("case", list(EC.SAMPLE_CASES))

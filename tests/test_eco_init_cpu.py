@@ -12,6 +12,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
+import f64_bound  # noqa: E402
 import eco_cases as EC  # noqa: E402
 import eco_init_cases as IC  # noqa: E402
 from oracle import ref_harness  # noqa: E402
@@ -87,7 +88,7 @@ def test_torch_form(g_init, case):
         assert np.abs(got - w).max() <= 1e-10 * max(np.abs(w).max(), 1e-30), key
     for key, got, w in zip(IC.keys(case), torch_run(case, torch.float32), want):
         ref_err = g_init[key + "/ref_fp32_err"] if key + "/ref_fp32_err" in g_init else 0.0
-        bound = EC.bound(ref_err, w)
+        bound = f64_bound.bound(ref_err, floor=f64_bound.ulp_of_max(w))
         err = np.abs(got - w).max()
         print(f"\n{key}: torch fp32 {err:.3e}, bound {bound:.3e}")
         assert err <= bound, (key, err, bound)

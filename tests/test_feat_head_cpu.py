@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import f64_bound
 import feat_head_cases as FC
 from oracle import ref_harness
 from pytracking_amd import _lib, features as FM, synth
@@ -100,11 +101,11 @@ def test_goldens_reproduce_from_the_stand_in(name):
         assert np.array_equal(g["x"], x.numpy())
     recorded = float(g["ref_fp32_err"])
     dist = float(np.abs(g["out"].astype(np.float64) - a.want).max())
-    here = FC.max_err(a.want, FC.standin(x, w, 2))
+    here = f64_bound.errors(a.want, FC.standin(x, w, 2))[""]
     print(f"\nfeat_head_{name}: golden ref_fp32_err {recorded:.6e}, max |golden - float64| {dist:.6e}, this host's fp32 stand-in {here:.3e}, "
           f"ref_err {a.ref_err:.3e}, max |v| {np.abs(a.want).max():.3f}")
     assert abs(dist / recorded - 1) <= 1e-6
-    assert 0.25 * recorded <= a.ref_err <= 4 * recorded and here <= FC.bound(a.ref_err)
+    assert 0.25 * recorded <= a.ref_err <= 4 * recorded and here <= f64_bound.bound(a.ref_err)
     assert float(np.abs(FC.standin(x, w, 2).numpy() - g["out"]).max()) <= 1e-6
 
 
@@ -213,16 +214,14 @@ def _ten_bit(w):
 
 
 def test_factor_is_the_projects_or_the_tomp_tests():
-    """F starts from fused_f64.FACTOR = 4 and may be raised once, to the 6 of the ToMP route tests; no further."""
+    """F starts from f64_bound.FACTOR = 4 and may be raised once, to the 6 of the ToMP route tests; no further."""
     assert FC.FACTOR in (4, 6)
 
 
 @pytest.mark.parametrize("name", FC.CASES)
 def test_the_fp32_stand_in_is_inside_the_bound(name):
     x, w, a = FC.small(name)
-    err = FC.max_err(a.want, FC.standin(x, w, 2))
-    print(FC.report(f"feat_head_{name}, fp32 CPU", err, a.ref_err))
-    assert err <= FC.bound(a.ref_err)
+    f64_bound.held(f"feat_head_{name}, fp32 CPU", FC.standin(x, w, 2), a.want, a.ref_err)
 
 
 @pytest.mark.parametrize("which", ["weights", "origin"])
@@ -234,7 +233,7 @@ def test_the_bound_catches_the_mutant(name, which):
         got = FC.standin(x.double(), _ten_bit(w).double(), 2)
     else:
         got = FC.standin(x.double(), w.double(), 2, origin=0)
-    err = FC.max_err(a.want, got)
-    print(FC.report(f"feat_head_{name}, mutant {which}", err, a.ref_err) + f"  (under the flat 1e-4: {err <= 1e-4})")
-    assert err > FC.bound(a.ref_err)
+    err = f64_bound.errors(a.want, got)[""]
+    print(f64_bound.report(f"feat_head_{name}, mutant {which}", {"": err}, a.ref_err) + f"  (under the flat 1e-4: {err <= 1e-4})")
+    assert err > f64_bound.bound(a.ref_err)
     assert err > 6 * a.ref_err                                   # also at the one value FACTOR may be raised to

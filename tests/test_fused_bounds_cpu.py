@@ -1,4 +1,4 @@
-"""The bound of tests/fused_f64.py without a GPU: ref_err of every committed case is the number its golden recorded, and FACTOR x ref_err
+"""The bound of tests/f64_bound.py on the anchors of tests/fused_f64.py without a GPU: ref_err of every committed case is the number its golden recorded, and FACTOR x ref_err
 catches what the flat 1e-4 of the golden tests lets through.  Two mutants of the stand-in, evaluated in float64 so that nothing but the
 mutation separates them from `want`: every BatchNorm eps doubled (errors of 2e-6 to 9e-5, all under 1e-4), and the weights of one
 mid-network convolution cut to a 10-bit mantissa.  Each must leave the bound on every committed small case while the unmutated fp32 run

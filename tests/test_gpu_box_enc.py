@@ -1,7 +1,7 @@
 """Box label encoders on the MI355X (box_enc.hip through pytracking_amd.box_encoder): every case of synth.BOX_ENC_CASES and
 synth.BOX_CAT_ENC_CASES, every output, within FACTOR x max(ref_err, one fp32 ulp of the output's range) of the float64 stand-in
 (tests/box_enc_cases.py; ref_err = the fp32 CPU stand-in's own distance from float64 on that case, 8 threads; FACTOR is the project's,
-tests/fused_f64.py) and within the golden's distance (the CPU bound of tests/test_box_enc_cpu.py plus the float64 bound); bit-identical
+tests/f64_bound.py) and within the golden's distance (the CPU bound of tests/test_box_enc_cpu.py plus the float64 bound); bit-identical
 repeats, graph capture, feature views, box dtypes, the weight cache, and install(box_encoder=True) on the reference's four classes.
 tests/test_box_enc_cpu.py shows that the float64 bound rejects a doubled BatchNorm eps, 10-bit weights and a box moved by a pixel.
 
@@ -12,19 +12,19 @@ import pytest
 import torch
 
 import box_enc_cases as BC
-import fused_f64 as F64
+import f64_bound
+from f64_bound import needs_bundle
 from oracle import ref_harness
 from pytracking_amd import box_encoder as BE
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-needs_bundle = pytest.mark.skipif(not ref_harness.available(), reason="no reference tree / bundle (oracle/_ref)")
 _RUNS = {}
 
 
 def _bound(a):
-    return F64.FACTOR * max(a.ref_err, BC.ulp_of_range(a.want))
+    return f64_bound.bound(a.ref_err, floor=f64_bound.spacing_of_max(a.want))
 
 
 def _layers_crossed(kind, c):
@@ -61,11 +61,8 @@ def test_matches_float64_and_golden(kind, name):
         assert out.shape == (n, 1, F, h, w)
     got = {q: t.cpu().numpy() for q, t in _named(kind, c, out).items()}
     a = BC.anchor(kind, name)
-    errs = BC.errors(a.want, got)
     bound = _bound(a)
-    print(f"\n{kind}_{name}: max |gpu - float64| " + "  ".join(f"{q} {e:.3e} ({e / max(a.ref_err, 1e-30):.2f}x)" for q, e in errs.items())
-          + f"  ref_err {a.ref_err:.3e}, bound {bound:.3e}")
-    assert max(errs.values()) <= bound
+    f64_bound.held(f"{kind}_{name}", got, a.want, a.ref_err, floor=f64_bound.spacing_of_max(a.want))
     gerr = max(float(np.abs(got[q] - g[q]).max()) for q in got)
     gbound = float(g["ref_fp32_err"]) + _layers_crossed(kind, c) * float(g["max_abs"]) * 2.0 ** -24 + 1e-12 + bound
     print(f"{kind}_{name}: max |gpu - reference fp32 golden| = {gerr:.3e} (bound {gbound:.3e})")
@@ -204,7 +201,7 @@ def test_install_dispatches_the_references_classes(amd, pkg, kind, name):
     err = max(float((got[q] - stock[q]).abs().max()) for q in got)
     print(f"\ninstall(box_encoder=True), {pkg} {cname}: max |fused - stock on device| = {err:.3e} (bound 2 x {_bound(a):.3e})")
     assert err <= 2 * _bound(a)                                         # both sides within the bound of float64
-    assert max(BC.errors(a.want, {q: t.cpu().numpy() for q, t in got.items()}).values()) <= _bound(a)
+    assert max(f64_bound.errors(a.want, {q: t.cpu().numpy() for q, t in got.items()}).values()) <= _bound(a)
     net.train()
     with torch.no_grad():
         net(*args)

@@ -9,16 +9,13 @@ import pytest
 import torch
 
 import corr_tm_cases as CT
+from f64_bound import dev
 from pytracking_amd import _lib, iou_feat as IF
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 ATOL = 1e-4
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _where(name, n, t3, t4, got, ref):
@@ -46,10 +43,10 @@ def test_full_maps_match_float64(name):
     ref, f32_err = CT.reference(name)
     net = CT.module(name, DEV)
     with torch.no_grad():
-        dev = [_dev(f) for f in feats]
-        assert IF.covered(net, dev)
-        c3, c4 = IF.get_iou_feat(net, dev)
-        d3, d4 = IF.get_iou_feat(net, dev)
+        fd = [dev(f) for f in feats]
+        assert IF.covered(net, fd)
+        c3, c4 = IF.get_iou_feat(net, fd)
+        d3, d4 = IF.get_iou_feat(net, fd)
     assert c3.shape == (n, t3[2], t3[3], t3[4]) and c4.shape == (n, t4[2], t4[3], t4[4])
     got = [c3.cpu().numpy().astype(np.float64), c4.cpu().numpy().astype(np.float64)]
     err, msg = _where(name, n, t3, t4, got, ref)
@@ -74,9 +71,9 @@ def test_one_hot_maps_against_power_of_two_taps_are_exact(route):
     assert all(float(r.max()) < 2 ** 24 and np.array_equal(r, np.round(r)) for r in ref) and float(ref[0].max()) >= 256
     net = CT.structured_module(t3, t4).to(DEV)
     with torch.no_grad():
-        dev = [_dev(f) for f in feats]
-        assert IF.covered(net, dev)
-        got = [c.cpu().numpy().astype(np.float64) for c in IF.get_iou_feat(net, dev)]
+        fd = [dev(f) for f in feats]
+        assert IF.covered(net, fd)
+        got = [c.cpu().numpy().astype(np.float64) for c in IF.get_iou_feat(net, fd)]
     err, msg = _where(route, n, t3, t4, got, ref)
     print(f"\ncorr_tm structured {route}: max |gpu - float64| = {err:.3e} (exact expected)\n{msg}")
     assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1]), msg

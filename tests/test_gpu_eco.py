@@ -2,13 +2,14 @@
 localisation and memory insert against the float64 restatements of tests/eco_cases.py, the closed per-frame loop (eager and as captured
 graphs) and the unmodified reference ECO through install(eco=True).
 
-Bounds are the project's (tests/fused_f64.py): an fp32 output lies within FACTOR x max(ref_fp32_err, 2^-23 max |want|) of float64, where
+Bounds are the project's (tests/f64_bound.py): an fp32 output lies within FACTOR x max(ref_fp32_err, 2^-23 max |want|) of float64, where
 ref_fp32_err is the error of the unmodified reference's own fp32 run recorded in the golden (tests/golden/eco_*.npz, written by
 tools/make_golden_eco.py from the reference on the torch.rfft / torch.irfft shim that tests/test_eco_cpu.py verifies), and within 1e-4 of
 the golden; arg-max positions, scale indices and slots are compared exactly.  Where there is no golden (a score grid equal to the series,
 which the reference evaluates on 2 Wh - 2 columns; the closed loop; the tracker run) ref_fp32_err is the error of pytracking_amd.eco's
 torch form in fp32 on the same inputs.  Every test prints its measured ratio before it asserts (run with -s); when ECO_F64_OUT names a
 file the ratios are written there as a table (profiles/eco_f64.txt is the table of such a run)."""
+import functools
 import os
 import sys
 from collections import OrderedDict
@@ -21,46 +22,17 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
 import eco_cases as EC  # noqa: E402
-import fused_f64  # noqa: E402
+import f64_bound  # noqa: E402
+from f64_bound import host, needs_bundle  # noqa: E402
 from oracle import ref_harness  # noqa: E402
 from pytracking_amd import eco  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-TABLE = os.environ.get("ECO_F64_OUT")
-needs_bundle = pytest.mark.skipif(not ref_harness.available(), reason="no reference tree / bundle (oracle/_ref)")
-_ROWS = OrderedDict()
-
-
-def dev(a, dtype=torch.float32):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(device=DEV, dtype=dtype)
-
-
-def host(t):
-    return t.detach().double().cpu().numpy()
-
-
-@pytest.fixture(scope="module", autouse=True)
-def table():
-    yield
-    if TABLE and _ROWS:
-        with open(TABLE, "w") as fh:
-            fh.write("ECO Fourier-domain path on gfx950: max |out - float64| per case, as a multiple of max(ref_fp32_err, 2^-23 max |want|)\n"
-                     f"(bound: {fused_f64.FACTOR}); ref_fp32_err: the unmodified reference's own fp32 error (golden) or, marked *, the torch form's\n")
-            fh.write(f"{'case':58s} {'err':>10s} {'ref_err':>10s} {'ulp*max':>10s} {'ratio':>7s}\n")
-            for k, (err, ref, ulp, ratio) in _ROWS.items():
-                fh.write(f"{k:58s} {err:10.3e} {ref:10.3e} {ulp:10.3e} {ratio:7.2f}\n")
-
-
-def held(tag, got, want, ref_err, own=False):
-    """Print, record and assert the float64 bound of one output."""
-    err = float(np.abs(got - want).max())
-    ulp = EC.EPS * float(np.abs(want).max())
-    unit = max(float(ref_err), ulp)
-    ratio = err / unit if unit > 0 else 0.0
-    _ROWS[tag + ("*" if own else "")] = (err, float(ref_err), ulp, ratio)
-    print(f"\n{tag}: max |out - float64| {err:.3e} = {ratio:.2f} x max(ref_fp32_err {float(ref_err):.3e}, ulp {ulp:.3e}); bound {fused_f64.FACTOR} x")
-    assert err <= fused_f64.FACTOR * unit, (tag, err, unit)
+TABLE = f64_bound.Table("ECO_F64_OUT",
+                        "ECO Fourier-domain path on gfx950: max |out - float64| per case, as a multiple of max(ref_fp32_err, 2^-23 max |want|)\n"
+                        f"(bound: {f64_bound.FACTOR}); ref_fp32_err: the unmodified reference's own fp32 error (golden) or, marked *, the torch form's")
+dev = functools.partial(f64_bound.dev, device=DEV, dtype=torch.float32)
 
 
 @pytest.fixture(scope="module")
@@ -88,7 +60,7 @@ def test_sample_transform(g_sample, case):
     out = eco.sample_transform(*args)
     assert out.shape == want.shape
     got = host(out)
-    held("sample " + case, got, want, g_sample[case + "/ref_fp32_err"])
+    f64_bound.held("sample " + case, got, want, g_sample[case + "/ref_fp32_err"], floor=f64_bound.ulp_of_max, table=TABLE)
     near_golden(g_sample, case, c["seed"], got)
     assert torch.equal(eco.sample_transform(*args), out)                                # no atomics: the same bits again
 
@@ -98,7 +70,7 @@ def test_sample_transform_without_window_and_factors_is_cfft2():
     out = eco.cfft2_device(dev(x))
     want = EC.to_r(EC.cfft2_np(x))
     ref = eco.cfft2(torch.from_numpy(x)).numpy()
-    held("cfft2 6x9", host(out), want, np.abs(ref - want).max(), own=True)
+    f64_bound.held("cfft2 6x9", host(out), want, np.abs(ref - want).max(), floor=f64_bound.ulp_of_max, table=TABLE, star=True)
     assert torch.equal(out[:, :, 0], out[:, :, -1])                                     # even H: the Nyquist row at both ends
 
 
@@ -109,7 +81,7 @@ def test_real_interpolation_factors_and_views():
     want = EC.sample_np(x, P, win, (np.stack((iy, 0 * iy), -1), np.stack((ix, 0 * ix), -1)))
     out = eco.sample_transform(dev(x), dev(P), dev(win), (dev(iy), dev(ix)))
     ref = eco.sample_transform_torch(*[torch.from_numpy(a) for a in (x, P, win)], (torch.from_numpy(iy), torch.from_numpy(ix))).numpy()
-    held("sample real factors", host(out), want, np.abs(ref - want).max(), own=True)
+    f64_bound.held("sample real factors", host(out), want, np.abs(ref - want).max(), floor=f64_bound.ulp_of_max, table=TABLE, star=True)
     xt = dev(np.ascontiguousarray(x.transpose(0, 1, 3, 2))).transpose(2, 3)
     assert not xt.is_contiguous() and torch.equal(eco.sample_transform(xt, dev(P), dev(win), (dev(iy), dev(ix))), out)
 
@@ -121,7 +93,7 @@ def test_apply_filter(g_ops, case):
     want = EC.apply_filter_np(hf, xf)
     out = eco.apply_filter(dev(hf), dev(xf))
     assert out.shape == want.shape
-    held("apply " + case, host(out), want, g_ops[f"apply/{case}/ref_fp32_err"])
+    f64_bound.held("apply " + case, host(out), want, g_ops[f"apply/{case}/ref_fp32_err"], floor=f64_bound.ulp_of_max, table=TABLE)
     near_golden(g_ops, "apply/" + case, EC.APPLY_CASES[case]["seed"], host(out))
     assert torch.equal(eco.apply_filter(dev(hf), dev(xf)), out)
 
@@ -140,8 +112,8 @@ def test_localize(g_ops, case):
         assert np.array_equal(g_ops[f"loc/{case}/argmax"], am.cpu().numpy())
     else:                                                                               # grid equal to the series: the torch form's fp32 error
         ref_err, own = float(np.abs(eco.localize_torch([torch.from_numpy(e) for e in sfs], c["weights"], c["grid"])[0].numpy() - want).max()), True
-    held("localize " + case, host(scores), want, ref_err, own)
-    held("localize max " + case, host(mv), max_val, ref_err, own)
+    f64_bound.held("localize " + case, host(scores), want, ref_err, floor=f64_bound.ulp_of_max, table=TABLE, star=own)
+    f64_bound.held("localize max " + case, host(mv), max_val, ref_err, floor=f64_bound.ulp_of_max, table=TABLE, star=own)
     assert np.array_equal(am.cpu().numpy(), argmax)
     again = eco.localize([dev(e) for e in sfs], c["weights"], c["grid"])
     assert all(torch.equal(a, b) for a, b in zip(again, (scores, mv, am)))
@@ -164,7 +136,7 @@ def test_insert(g_ops, case):
     m = dev(mem)
     assert eco.insert(m, dev(xf), c["ind"], c["shift"]) is m
     got = m.cpu().numpy()
-    held("insert " + case, got.astype(np.float64), want, g_ops[f"insert/{case}/ref_fp32_err"])
+    f64_bound.held("insert " + case, got.astype(np.float64), want, g_ops[f"insert/{case}/ref_fp32_err"], floor=f64_bound.ulp_of_max, table=TABLE)
     near_golden(g_ops, "insert/" + case, c["seed"], got)
     keep = np.ones(c["n"], dtype=bool)
     keep[c["ind"]] = False
@@ -211,13 +183,13 @@ def test_filter_update(g_fu, case):
             got = host(x)
             if ref is None:
                 assert np.abs(want[k][b].reshape(-1)[EC.sample_positions(c["seed"], got.size)] - g_fu[key + "/want_f64"]).max() <= 1e-10 * float(g_fu[key + "/max_abs"])       # the restatement is the reference's float64
-                held("filter_update " + key, got, want[k][b], g_fu[key + "/ref_fp32_err"])
+                f64_bound.held("filter_update " + key, got, want[k][b], g_fu[key + "/ref_fp32_err"], floor=f64_bound.ulp_of_max, table=TABLE)
                 near_golden(g_fu, key, c["seed"], got)
             else:
-                held("filter_update " + key, got, want[k][b], np.abs(ref[k][b] - want[k][b]).max(), own=True)
+                f64_bound.held("filter_update " + key, got, want[k][b], np.abs(ref[k][b] - want[k][b]).max(), floor=f64_bound.ulp_of_max, table=TABLE, star=True)
     if c["iters"][-1] > 0 and c.get("new_xf", True):
         for b, e in enumerate(energy):
-            assert np.abs(host(e) - want_energy[b]).max() <= 4 * EC.EPS * np.abs(want_energy[b]).max()
+            assert np.abs(host(e) - want_energy[b]).max() <= 4 * f64_bound.ulp_of_max(want_energy[b])
     again = fu_device(case)[0]
     assert all(torch.equal(a, b) for ca, cb in zip(again, outs) for a, b in zip(ca, cb))                   # the same call twice: the same bits
 
@@ -347,11 +319,11 @@ def check_loop(tag, got, want, ref):
     boxes, wboxes = np.array([e["box"] for e in log]), np.array([e["box"] for e in wlog])
     assert np.array_equal(boxes, wboxes)                 # the arg-max positions agree and the host arithmetic is the same float64
     ms, wms, rms = (np.array([e["max_score"] for e in lg]) for lg in (log, wlog, rlog))
-    held(tag + " max_score", ms, wms, np.abs(rms - wms).max(), own=True)
+    f64_bound.held(tag + " max_score", ms, wms, np.abs(rms - wms).max(), floor=f64_bound.ulp_of_max, table=TABLE, star=True)
     assert [e["trained"] for e in log].count(True) == 2
     nb = len(mems) // 2
     for b, (m, w, r) in enumerate(zip(mems, wmems, rmems)):
-        held(f"{tag} {'memory' if b < nb else 'final filter'}[{b % nb}]", m, w, np.abs(r - w).max(), own=True)
+        f64_bound.held(f"{tag} {'memory' if b < nb else 'final filter'}[{b % nb}]", m, w, np.abs(r - w).max(), floor=f64_bound.ulp_of_max, table=TABLE, star=True)
 
 
 def test_closed_loop(loop_anchor):
@@ -421,13 +393,13 @@ def test_unmodified_eco_on_device_through_install(monkeypatch):
                     continue
                 w = w.cpu().numpy()
                 err, ref_err = float(np.abs(host(o) - w).max()), float(np.abs(host(r) - w).max())
-                units.append(max(ref_err, EC.EPS * float(np.abs(w).max())))
+                units.append(max(ref_err, f64_bound.ulp_of_max(w)))
                 calls.setdefault(name, []).append(err / units[-1] if units[-1] > 0 else 0.0)
-                assert err <= fused_f64.FACTOR * units[-1], (name, q, err, units[-1])
+                assert err <= f64_bound.bound(units[-1]), (name, q, err, units[-1])
             if name == "localize":                       # the arg-max: the float64 score at the kernel's position is the maximum up to the bound
                 s64, am = want[0].cpu().numpy(), out[2].cpu().numpy()
                 for sc in range(am.shape[0]):
-                    assert s64[sc, 0].max() - s64[sc, 0, am[sc, 0, 0], am[sc, 0, 1]] <= 2 * fused_f64.FACTOR * units[0], (name, sc)
+                    assert s64[sc, 0].max() - s64[sc, 0, am[sc, 0, 0], am[sc, 0, 1]] <= 2 * f64_bound.bound(units[0]), (name, sc)
             return out
         return fn
 
@@ -451,9 +423,9 @@ def test_unmodified_eco_on_device_through_install(monkeypatch):
             runs.append([EC.to_r(x) for x in o.x])
         out = real_update(filters, samples, weights, yf, regs, energy, new_xf, state, num_iter, lrs, reg_energy, fr, std_alpha, forget, dp, rp)
         for f, w, r in zip(filters, *runs):
-            err, unit = float(np.abs(host(f) - w).max()), max(float(np.abs(r - w).max()), EC.EPS * float(np.abs(w).max()))
+            err, unit = float(np.abs(host(f) - w).max()), max(float(np.abs(r - w).max()), f64_bound.ulp_of_max(w))
             fu_ratios.append(err / unit)
-            assert err <= fused_f64.FACTOR * unit, ("filter_update", err, unit)
+            assert err <= f64_bound.bound(unit), ("filter_update", err, unit)
         return out
     monkeypatch.setattr(eco, "filter_update", checked_update)
     amd.install(eco=True)

@@ -1,11 +1,11 @@
 """ECO's first-frame joint Gauss-Newton optimisation on the kernels (pytracking_amd.eco.joint_init, eco_init.hip) against the float64
 restatement of tests/eco_init_cases.py, which tests/test_eco_init_cpu.py holds to the unmodified reference's float64 run.  The bound is the
-project's (tests/fused_f64.py): FACTOR x the larger of the reference's own fp32 error on the case (the golden's `ref_fp32_err`: autograd
+project's (tests/f64_bound.py): FACTOR x the larger of the reference's own fp32 error on the case (the golden's `ref_fp32_err`: autograd
 GaussNewtonCG in fp32 on CPU) and one fp32 ulp of the largest value.  With ECO_INIT_F64_OUT set the table of ratios is written
 (profiles/eco_init_f64.txt)."""
+import functools
 import os
 import sys
-from collections import OrderedDict
 
 import numpy as np
 import pytest
@@ -16,46 +16,17 @@ sys.path.insert(0, HERE)
 
 import eco_cases as EC  # noqa: E402
 import eco_init_cases as IC  # noqa: E402
-import fused_f64  # noqa: E402
+import f64_bound  # noqa: E402
+from f64_bound import host, needs_bundle  # noqa: E402
 from oracle import ref_harness  # noqa: E402
 from pytracking_amd import eco  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-TABLE = os.environ.get("ECO_INIT_F64_OUT")
-needs_bundle = pytest.mark.skipif(not ref_harness.available(), reason="no reference tree / bundle (oracle/_ref)")
-_ROWS = OrderedDict()
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a)).to(device=DEV, dtype=torch.float32)
-
-
-def host(t):
-    return t.detach().double().cpu().numpy()
-
-
-@pytest.fixture(scope="module", autouse=True)
-def table():
-    yield
-    if TABLE and _ROWS:
-        with open(TABLE, "w") as fh:
-            fh.write("ECO first-frame joint optimisation on gfx950: max |out - float64| per output, as a multiple of max(ref_fp32_err, 2^-23 max |want|)\n"
-                     f"(bound: {fused_f64.FACTOR}); ref_fp32_err: the unmodified reference's own fp32 error (golden) or, marked *, the restatement's fp32 mode\n")
-            fh.write(f"{'output':58s} {'err':>10s} {'ref_err':>10s} {'ulp*max':>10s} {'ratio':>7s}\n")
-            for k, (err, ref, ulp, ratio) in _ROWS.items():
-                fh.write(f"{k:58s} {err:10.3e} {ref:10.3e} {ulp:10.3e} {ratio:7.2f}\n")
-
-
-def held(tag, got, want, ref_err, own=False):
-    """Print, record and assert the float64 bound of one output."""
-    err = float(np.abs(got - want).max())
-    ulp = EC.EPS * float(np.abs(want).max())
-    unit = max(float(ref_err), ulp)
-    ratio = err / unit if unit > 0 else 0.0
-    _ROWS[tag + ("*" if own else "")] = (err, float(ref_err), ulp, ratio)
-    print(f"\n{tag}: max |out - float64| {err:.3e} = {ratio:.2f} x max(ref_fp32_err {float(ref_err):.3e}, ulp {ulp:.3e}); bound {fused_f64.FACTOR} x")
-    assert err <= fused_f64.FACTOR * unit, (tag, err, unit)
+TABLE = f64_bound.Table("ECO_INIT_F64_OUT",
+                        "ECO first-frame joint optimisation on gfx950: max |out - float64| per output, as a multiple of max(ref_fp32_err, 2^-23 max |want|)\n"
+                        f"(bound: {f64_bound.FACTOR}); ref_fp32_err: the unmodified reference's own fp32 error (golden) or, marked *, the restatement's fp32 mode")
+dev = functools.partial(f64_bound.dev, device=DEV, dtype=torch.float32)
 
 
 @pytest.fixture(scope="module")
@@ -82,7 +53,7 @@ def test_joint_init(g_init, case):
     for key, x, want in zip(IC.keys(case), outs, IC.run_np(case)):
         got = host(x)
         assert got.shape == want.shape
-        held("joint_init " + key, got, want, g_init[key + "/ref_fp32_err"])
+        f64_bound.held("joint_init " + key, got, want, g_init[key + "/ref_fp32_err"], floor=f64_bound.ulp_of_max, table=TABLE)
         idx = EC.sample_positions(c["seed"], got.size)
         assert np.abs(got.reshape(-1)[idx] - g_init[key + "/out"]).max() <= 1e-4, key
     assert all(torch.equal(a, b) for a, b in zip(on_device(case), outs))                  # the same call twice: the same bits
@@ -180,9 +151,8 @@ def test_unmodified_eco_initialises_on_the_kernels(monkeypatch):
         out = real(filters, projections, samples, weights_sqrt, yf, reg_filters, diag_M, proj_precond, num_cg_iter, num_gn_iter, projection_reg)
         for q, (x, w, r) in enumerate(zip(list(filters) + list(projections), *runs)):
             assert not np.array_equal(host(x), (pre[0] + pre[1])[q])                        # the tracker's tensors moved
-            err, unit = float(np.abs(host(x) - w).max()), max(float(np.abs(r - w).max()), EC.EPS * float(np.abs(w).max()))
-            ratios.append(err / unit)
-            held(f"tracker joint_init output {q}", host(x), w, np.abs(r - w).max(), own=True)
+            err = f64_bound.held(f"tracker joint_init output {q}", host(x), w, np.abs(r - w).max(), floor=f64_bound.ulp_of_max, table=TABLE, star=True)[""]
+            ratios.append(err / max(float(np.abs(r - w).max()), f64_bound.ulp_of_max(w)))
         return out
     monkeypatch.setattr(eco, "joint_init", checked)
     amd.install(eco=True, eco_init=True)

@@ -3,7 +3,8 @@ the MI355X: the cases of tests/fast_pass_cases.py through pytracking_amd.filter 
 optimizer modules (pt_sd_solve_f32) against the same operation in float64 on the CPU.
 
   (a) random data: scores within 2e-5, the adjoint within 2e-5 * max(1, |ref|max) -- the project's flat bounds -- and both within
-      FACTOR x max(the fp32 CPU evaluation's own distance from float64 on the case, one fp32 ulp of the output's range); two calls
+      FACTOR x max(the fp32 CPU evaluation's own distance from float64 on the case, one fp32 ulp of the output's range), the bound of
+      tests/f64_bound.py with its spacing_of_max floor; two calls
       bit-identical; <F w, r> = <w, F^T r>.
   (b) structured data: one-hot channels against power-of-two taps and small-integer residual maps.  The float64 reference is integral and
       below 2^24, so every summation order is exact and the device result must be EQUAL.
@@ -12,41 +13,24 @@ optimizer modules (pt_sd_solve_f32) against the same operation in float64 on the
 
 Every test prints its figures before it asserts (run with -s); with FAST_PASSES_F64_OUT set the table is written to that file
 (profiles/fast_passes_f64.txt).  Needs no reference tree."""
-import os
-from collections import OrderedDict
-
 import numpy as np
 import pytest
 import torch
 
 import fast_pass_cases as FP
-import fused_f64
+import f64_bound
 from pytracking_amd import _lib, filter as F
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-FACTOR = fused_f64.FACTOR                          # 4 x max(ref_err, ulp): the bound of feat_head_f64, seg_readout_f64 and eco_f64
-TABLE = os.environ.get("FAST_PASSES_F64_OUT")
-_ROWS = OrderedDict()
 IDS = ["-".join(str(v) for v in c[0]) for c in FP.CASES]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def table():
-    yield
-    if TABLE and _ROWS:
-        with open(TABLE, "w") as fh:
-            fh.write("XCD-aligned feature passes and the steepest-descent solve on gfx950 against float64 (tests/test_gpu_fast_pass_plans.py -s).\n"
-                     "passes: max |out - float64| per case (n-C-H-W-K-out-sf) and output, ref_err = the fp32 CPU evaluation's own distance from\n"
-                     f"float64 (torch conv2d, {FP.THREADS} threads), ulp = one fp32 ulp of the output's range, ratio = err / max(ref_err, ulp); bound {FACTOR}.\n"
-                     "solver: max |iterates - float64 oracle| (bound 2e-5), max |losses - float64 oracle|, and the fp32 oracle's own distances.\n")
-            fh.write(f"{'case':44s} {'err':>10s} {'ref_err':>10s} {'ulp':>10s} {'ratio':>7s}\n")
-            for k, (err, ref, ulp, ratio) in _ROWS.items():
-                fh.write(f"{k:44s} {err:10.3e} {ref:10.3e} {ulp:10.3e} {ratio:7.2f}\n")
-            passes = [v[3] for k, v in _ROWS.items() if not k.startswith("solve")]
-            if passes:
-                fh.write(f"worst ratio of the passes: {max(passes):.2f}\n")
+TABLE = f64_bound.Table("FAST_PASSES_F64_OUT",
+                        "XCD-aligned feature passes and the steepest-descent solve on gfx950 against float64 (tests/test_gpu_fast_pass_plans.py -s).\n"
+                        "passes: max |out - float64| per case (n-C-H-W-K-out-sf) and output, ref_err = the fp32 CPU evaluation's own distance from\n"
+                        f"float64 (torch conv2d, {FP.THREADS} threads), floor = one fp32 ulp of the output's range, ratio = err / max(ref_err, floor);\n"
+                        f"bound {f64_bound.FACTOR}, and the worst ratio is that of the passes.\n"
+                        "solver: max |iterates - float64 oracle| (bound 2e-5), max |losses - float64 oracle|, and the fp32 oracle's own distances.")
 
 
 def _dev_problem(case, feat, filt, r):
@@ -102,17 +86,6 @@ def _where_adj(case, got, ref, hot=None):
     return msg
 
 
-def _held(tag, got, want, ref_err, flat):
-    """Print, record and assert both bounds of one output."""
-    err = float(np.abs(got - want).max())
-    ulp = float(np.spacing(np.float32(np.abs(want).max())))
-    unit = max(ref_err, ulp)
-    ratio = err / unit
-    _ROWS[tag] = (err, ref_err, ulp, ratio)
-    print(f"\n{tag}: max |out - float64| {err:.3e} = {ratio:.2f} x max(ref_fp32_err {ref_err:.3e}, ulp {ulp:.3e}); bounds {FACTOR} x and {flat:.3e}")
-    return err, FACTOR * unit
-
-
 @pytest.mark.parametrize("idx", range(len(FP.CASES)), ids=IDS)
 def test_random_data_matches_float64(idx):
     case = _on_its_cell(idx)
@@ -127,12 +100,10 @@ def test_random_data_matches_float64(idx):
     assert sg.shape == s64.shape and ag.shape == g64.shape
     tag = IDS[idx]
     flat_a = 2e-5 * max(1.0, float(np.abs(g64).max()))
-    e_s, b_s = _held(tag + " corr", sg, s64, s_err, 2e-5)
-    e_a, b_a = _held(tag + " adj", ag, g64, g_err, flat_a)
     msg = f"{FP.CASES[idx]}\n{_where_corr(case, sg, s64)}\n{_where_adj(case, ag, g64)}"
     assert np.isfinite(sg).all() and np.isfinite(ag).all(), msg
-    assert e_s <= 2e-5 and e_a <= flat_a, msg
-    assert e_s <= b_s and e_a <= b_a, msg
+    f64_bound.held(tag + " corr", sg, s64, s_err, floor=f64_bound.spacing_of_max, flat=2e-5, table=TABLE, msg=msg)
+    f64_bound.held(tag + " adj", ag, g64, g_err, floor=f64_bound.spacing_of_max, flat=flat_a, table=TABLE, msg=msg)
     assert torch.equal(s, s2) and torch.equal(a, a2), f"{tag}: two calls differ"           # fixed-order sums: bit-identical
     lhs, rhs = float((sg * r.astype(np.float64)).sum()), float((ag * filt.astype(np.float64)).sum())
     assert abs(lhs - rhs) <= 1e-4 * max(1.0, abs(lhs)), (tag, lhs, rhs)                     # <F w, r> = <w, F^T r>
@@ -181,7 +152,7 @@ def test_solver_case_matches_float64_oracle(case):
     (n, C, H, W, K), want = FP.SOLVER_SHAPES[tag]
     L = _lib.lib()
     w0, feat, bb, sw = FP.solver_problem(case)
-    T = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    T = f64_bound.dev
     wd, fd = T(w0)[None], T(feat)
     mod = _module(v)
     outs = {}
@@ -200,8 +171,8 @@ def test_solver_case_matches_float64_oracle(case):
     e_i, e_l = float(np.abs(ig - i64).max()), float(np.abs(lg - l64).max())
     o_i, o_l = float(np.abs(i32 - i64).max()), float(np.abs(l32 - l64).max())
     name = f"solve {FP.V_NAMES[v]}-{tag}{'-sw' if has_sw else ''}"
-    _ROWS[name + " iterates"] = (e_i, o_i, float(np.spacing(np.float32(np.abs(i64).max()))), e_i / max(o_i, 1e-30))
-    _ROWS[name + " losses"] = (e_l, o_l, float(np.spacing(np.float32(np.abs(l64).max()))), e_l / max(o_l, 1e-30))
+    TABLE.row(name + " iterates", e_i, o_i, f64_bound.spacing_of_max(i64), e_i / max(o_i, 1e-30), bounded=False)
+    TABLE.row(name + " losses", e_l, o_l, f64_bound.spacing_of_max(l64), e_l / max(o_l, 1e-30), bounded=False)
     print(f"\n{name} {(n, C, H, W, K)} x {iters} iterations, route {want}: max |iterates - float64| {e_i:.3e} (fp32 oracle {o_i:.3e}, bound 2e-5), "
           f"max |losses - float64| {e_l:.3e} (fp32 oracle {o_l:.3e}); losses {l64[0]:.4f} -> {l64[-1]:.4f}")
     assert np.isfinite(ig).all() and np.isfinite(lg).all()

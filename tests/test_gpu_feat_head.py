@@ -15,7 +15,9 @@ import numpy as np
 import pytest
 import torch
 
+import f64_bound
 import feat_head_cases as FC
+from f64_bound import needs_bundle
 from oracle import ref_harness
 from pytracking_amd import _lib, features as FM, synth
 from pytracking_amd.filter import _ptr, _stream, workspace
@@ -24,7 +26,6 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 ATOL = 1e-4
-needs_bundle = pytest.mark.skipif(not ref_harness.available(), reason="no reference tree / bundle (oracle/_ref)")
 
 
 def _head(w, stride, scale=FC.SCALE, basic=False):
@@ -68,11 +69,11 @@ def test_stride_2_within_the_float64_bound_and_the_golden(name):
         out = head(x.to(DEV))
         again = head(x.to(DEV))
     assert out.shape == (n, Cout, *FC.out_hw(H, W, 2))
-    err = FC.max_err(a.want, out)
+    err = f64_bound.errors(a.want, out)[""]
     g = FC.golden(name)
     gerr = float(np.abs(out.cpu().numpy() - g["out"]).max())
-    print(FC.report(f"feat_head_{name} stride 2", err, a.ref_err) + f"  max |gpu - reference fp32 golden| {gerr:.3e} (bound {ATOL:.0e})")
-    assert err <= FC.bound(a.ref_err)
+    print(f64_bound.report(f"feat_head_{name} stride 2", {"": err}, a.ref_err) + f"  max |gpu - reference fp32 golden| {gerr:.3e} (bound {ATOL:.0e})")
+    assert err <= f64_bound.bound(a.ref_err)
     assert gerr <= ATOL
     assert torch.equal(out, again)                                      # two calls are bit-identical
 
@@ -82,8 +83,8 @@ def test_stride_1_is_the_classification_head_bit_for_bit(name):
     x, w, a = FC.small(name, stride=1)
     xd, wd = x.to(DEV), w.to(DEV)
     new, old = _abi(xd, wd, 1), _abi(xd, wd, None)
-    err = FC.max_err(a.want, new)
-    print(FC.report(f"feat_head_{name} stride 1", err, a.ref_err))
+    err = f64_bound.errors(a.want, new)[""]
+    print(f64_bound.report(f"feat_head_{name} stride 1", {"": err}, a.ref_err))
     assert torch.equal(new, old)
     with torch.no_grad():
         assert torch.equal(_head(w, 1, basic=True)(xd), old)            # the host module at stride 1 stays on pt_clf_head_f32
@@ -111,9 +112,7 @@ def test_deployed_shapes(n, stride, basic):
     with torch.no_grad():
         out = _head(w, stride, basic=basic)(x.to(DEV))
     assert out.shape == (n, 512, *FC.out_hw(30, 52, stride))
-    err = FC.max_err(a.want, out)
-    print(FC.report(f"feat_head deployed n = {n} stride {stride}", err, a.ref_err))
-    assert err <= FC.bound(a.ref_err)
+    f64_bound.held(f"feat_head deployed n = {n} stride {stride}", out, a.want, a.ref_err)
 
 
 def test_leading_dimensions_are_preserved():

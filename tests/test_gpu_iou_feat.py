@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import iou_feat_cases as IC
+from f64_bound import dev, needs_bundle
 from oracle import ref_harness
 from pytracking_amd import iou_feat as IF, iou_refine as IR, synth
 
@@ -16,18 +17,13 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 ATOL = 1e-4
-needs_bundle = pytest.mark.skipif(not ref_harness.available(), reason="no reference tree / bundle (oracle/_ref)")
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _run(name, net=None):
     g, n, t3, t4, sd, (f3, f4) = IC.case(name)
     net = IC.module(name, DEV) if net is None else net
     with torch.no_grad():
-        feats = [_dev(f3), _dev(f4)]
+        feats = [dev(f3), dev(f4)]
         assert IF.covered(net, feats)
         c3, c4 = IF.get_iou_feat(net, feats)
     return g, net, feats, c3, c4
@@ -77,7 +73,7 @@ def test_graph_capture_replays_the_eager_bits(name):
 def test_cache_follows_load_state_dict_and_in_place_updates():
     g, n, t3, t4, sd, (f3, f4) = IC.case("c")
     net = IC.module("c", DEV)
-    feats = [_dev(f3), _dev(f4)]
+    feats = [dev(f3), dev(f4)]
     other = synth.iou_feat_state(int(g["state_seed"]) + 50, t3[0], t4[0], t3[1], t3[2], t4[1], t4[2])
     with torch.no_grad():
         first = IF.get_iou_feat(net, feats)
@@ -120,7 +116,7 @@ def _bundle_net(seed=1234):
     state = IC.state_tensors(sd)
     state.update({k: torch.from_numpy(v.copy()) for k, v in synth.iou_net_params(seed).items()})
     net.load_state_dict(state, strict=False)
-    return g, net.to(DEV).eval(), [_dev(f3), _dev(f4)]
+    return g, net.to(DEV).eval(), [dev(f3), dev(f4)]
 
 
 @needs_bundle
@@ -149,7 +145,7 @@ def test_refined_boxes_downstream_agree_with_the_stock_features(amd):
     with torch.no_grad():
         fused = net.get_iou_feat(feats)
         stock = amd.original(AtomIoUNet, "get_iou_feat")(net, feats)
-        out = [IR.refine_boxes(net, (_dev(mod3), _dev(mod4)), f, torch.from_numpy(boxes.copy()), 5, 1.0, 1.0, False) for f in (fused, stock)]
+        out = [IR.refine_boxes(net, (dev(mod3), dev(mod4)), f, torch.from_numpy(boxes.copy()), 5, 1.0, 1.0, False) for f in (fused, stock)]
     (bf, jf), (bs, js) = [(b.cpu().numpy(), j.cpu().numpy()) for b, j in out]
     tol = 1e-4 + 1e-6 * float(np.abs(bs).max())
     db, dj = float(np.abs(bf - bs).max()), float(np.abs(jf - js).max())

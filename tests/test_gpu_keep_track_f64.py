@@ -2,7 +2,7 @@
 tests/tcm_np.py on the cases of tests/tcm_cases.py, which lie off the shapes of the two deployed configurations: peaks exactly (several
 compaction passes, more than 1024 hits, H != W, ks of 1, 3 and 127, ties, non-finite values, the 4-D form); descriptors (B > 1, H != W, both
 coordinate forms, 16 / 17 / 32 / 33 points, one K slice) and the matcher (1x1, 64x1, 1x64, T = 17 and 49, unequal image sizes, four layer
-masks, zero and one Sinkhorn iteration) within fused_f64.bound(ref_err) of float64, ref_err being the fp32 CPU run's own distance from
+masks, zero and one Sinkhorn iteration) within f64_bound.bound(ref_err) of float64, ref_err being the fp32 CPU run's own distance from
 float64 on the case; the matcher's matches0 / matches1 and the zero pattern of its scores exactly (every case is well-conditioned:
 tests/test_keep_track_cpu.py); every second call bit-equal to the first.
 
@@ -17,18 +17,15 @@ import numpy as np
 import pytest
 import torch
 
+import f64_bound
 import tcm_cases as TC
+from f64_bound import dev, needs_bundle
 from oracle import ref_harness
 from pytracking_amd import candidate_matching as CM
 
 pytestmark = pytest.mark.gpu
-needs_bundle = pytest.mark.skipif(not ref_harness.available(), reason="reference bundle missing")
 
 DEV = "cuda:0"
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 @pytest.mark.parametrize("name", [pytest.param(n, marks=needs_bundle) if TC.PEAK_CASES[n][4] == "batch3" else n for n in TC.PEAK_CASES])
@@ -37,7 +34,7 @@ def test_peaks_exact(name):
     want = TC.peak_want(name)
     if how == "batch3":
         ref_harness.install()                  # the 4-D form returns the reference's TensorList
-    scores = _dev(TC.peak_map(name))
+    scores = dev(TC.peak_map(name))
     cs, vs = CM.find_local_maxima(scores, th, ks)
     cs2, vs2 = CM.find_local_maxima(scores, th, ks)
     if how == "batch3":
@@ -61,15 +58,15 @@ def test_descriptors_within_the_float64_bound(name):
         conv.weight.copy_(torch.from_numpy(i.weight))
         conv.bias.copy_(torch.from_numpy(i.bias))
     ext = types.SimpleNamespace(conv=conv.to(DEV).eval())
-    x, coords = _dev(i.x), _dev(i.coords)
+    x, coords = dev(i.x), dev(i.coords)
     with torch.no_grad():
         assert CM.covered_get_descriptors(ext, x, coords)
         out = CM.get_descriptors(ext, x, coords)
         again = CM.get_descriptors(ext, x, coords)
     assert out.dtype == torch.float32 and tuple(out.shape) == (B, D, P)
     err = np.abs(out.double().cpu().numpy() - a.want)
-    print(TC.report(f"desc {name}", {f"image {b}": float(err[b].max()) for b in range(B)}, a.ref_err))
-    assert err.max() <= TC.bound(a.ref_err)
+    print(f64_bound.report(f"desc {name}", {f"image {b}": float(err[b].max()) for b in range(B)}, a.ref_err))
+    assert err.max() <= f64_bound.bound(a.ref_err)
     assert torch.equal(out, again)
 
 
@@ -87,11 +84,11 @@ def test_matcher_within_the_float64_bound(name):
     assert pred["log_assignment"].shape == (1, M + 1, N + 1) and pred["log_assignment"].dtype == torch.float32
     assert pred["matches0"].dtype == torch.int64 and pred["matches0"].shape == (1, M) and pred["matches1"].shape == (1, N)
     assert pred["match_scores0"].dtype == torch.float32 and pred["bin_score"] is sg.bin_score
-    b = TC.bound(a.ref_err)
+    b = f64_bound.bound(a.ref_err)
     errs = {"log_assignment": float(np.abs(got["log_assignment"].astype(np.float64) - a.want["log_assignment"]).max())}
     for k in ("match_scores0", "match_scores1"):                  # in units of the score's own bound: b where it is <= 1, b x score above
         errs[k + " / max(1, score)"] = float((np.abs(got[k].astype(np.float64) - a.want[k]) / np.maximum(1.0, a.want[k])).max())
-    print(TC.report(f"match {name} ({M}x{N}, {len(layers)} layers, {iters} iterations)", errs, a.ref_err)
+    print(f64_bound.report(f"match {name} ({M}x{N}, {len(layers)} layers, {iters} iterations)", errs, a.ref_err)
           + f"  matches {int((a.want['matches0'] >= 0).sum())}")
     assert all(e <= b for e in errs.values()), errs
     np.testing.assert_array_equal(got["matches0"], a.want["matches0"])

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import label_enc_cases as LC
+from f64_bound import dev, needs_bundle
 from oracle import ref_harness
 from pytracking_amd import label_encoder as LE, synth
 
@@ -17,18 +18,13 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 ATOL = 1e-4
-needs_bundle = pytest.mark.skipif(not ref_harness.available(), reason="no reference tree / bundle (oracle/_ref)")
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _run(name):
     g, n, H, W, dims, use_bn, sd, masks = LC.case(name)
     net = LC.module(name, DEV)
     with torch.no_grad():
-        m = _dev(masks)[:, None]                                        # (frames, 1 sequence, H, W)
+        m = dev(masks)[:, None]                                        # (frames, 1 sequence, H, W)
         assert LE.covered(net, m)
         enc, sw = LE.forward(net, m)
     return g, net, m, enc, sw
@@ -106,7 +102,7 @@ def test_mask_views_and_sequences():
 def test_cache_follows_load_state_dict_and_in_place_updates():
     g, n, H, W, dims, use_bn, sd, masks = LC.case("bn_odd")
     net = LC.module("bn_odd", DEV)
-    m = _dev(masks)[:, None]
+    m = dev(masks)[:, None]
     other = synth.label_enc_state(int(g["state_seed"]) + 50, dims, use_bn)
     with torch.no_grad():
         first = LE.forward(net, m)
@@ -146,7 +142,7 @@ def amd():
 def test_install_dispatches_the_bundles_lwl_net(amd):
     from oracle import tracker_harness as TH
     net = TH.build_lwl(4900).to(DEV)
-    masks = _dev(synth.label_enc_masks(5, 3, 480, 832))[:, None]
+    masks = dev(synth.label_enc_masks(5, 3, 480, 832))[:, None]
     amd.stats.clear()
     with torch.no_grad():
         enc, sw = net.label_encoder(masks)

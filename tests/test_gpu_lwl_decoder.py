@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import lwl_decoder_cases as DC
+from f64_bound import needs_bundle
 from oracle import ref_harness
 from pytracking_amd import lwl_decoder as LD, synth
 
@@ -20,7 +21,6 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 ATOL = 1e-4
-needs_bundle = pytest.mark.skipif(not ref_harness.available(), reason="no reference tree / bundle (oracle/_ref)")
 _RUNS = {}
 
 

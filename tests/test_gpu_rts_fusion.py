@@ -1,6 +1,6 @@
 """RTS instance-score encoder and learners fusion on the MI355X (rts_fusion.hip through pytracking_amd.rts_fusion): every encoder, fusion
 and chain case against the golden of the unmodified reference's fp32 CPU run (tools/make_golden_rts_fusion.py) within the project's 1e-4
-absolute and bit-identical on a second call; every case against the float64 run of the plain-torch stand-in within fused_f64.bound(ref_err)
+absolute and bit-identical on a second call; every case against the float64 run of the plain-torch stand-in within f64_bound.bound(ref_err)
 (FACTOR x the fp32 CPU stand-in's own distance from float64 on that case, tests/rts_fusion_cases.py) -- the measured ratios are printed
 and, when RTS_FUSION_F64_OUT names a file, written there as a table (profiles/rts_fusion_f64.txt is the table of such a run); a null
 sample_w, score-map views and (frames, seq) inputs, graph capture of the chain, the weight cache, and install(rts_fusion=True,
@@ -14,8 +14,9 @@ import numpy as np
 import pytest
 import torch
 
-import fused_f64
+import f64_bound
 import rts_fusion_cases as RC
+from f64_bound import dev, needs_bundle
 from oracle import ref_harness
 from pytracking_amd import rts_fusion as RF, synth
 
@@ -24,20 +25,17 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 ATOL = 1e-4
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TABLE = os.environ.get("RTS_FUSION_F64_OUT")                          # a run that records the table names the file; otherwise nothing is written
-needs_bundle = pytest.mark.skipif(not ref_harness.available(), reason="no reference tree / bundle (oracle/_ref)")
-_ROWS = OrderedDict()
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+TABLE = f64_bound.Table("RTS_FUSION_F64_OUT",
+                        "RTS instance-score encoder and learners fusion on the MI355X against the float64 run of the plain-torch stand-in\n"
+                        "(tests/test_gpu_rts_fusion.py): per output max |out - float64| and its ratio to ref_err, the fp32 CPU stand-in's own\n"
+                        f"distance from float64 on that case; bound = {f64_bound.FACTOR} x ref_err.")
 
 
 def _run_enc(name):
     g, n, H, W, dims, use_bn, sd, scores = RC.enc_case(name)
     net = RC.enc_module(name, DEV)
     with torch.no_grad():
-        s = _dev(scores)[:, None]                                       # (frames, 1 sequence, H, W)
+        s = dev(scores)[:, None]                                       # (frames, 1 sequence, H, W)
         assert RF.encoder_covered(net, s)
         enc, sw = RF.encode(net, s)
     return g, net, s, enc, sw
@@ -47,7 +45,7 @@ def _run_fuse(name, kind):
     g, n, f, source, target, sds, seg, clf = RC.fuse_case(name)
     net = RC.fuse_module(name, kind, DEV)
     with torch.no_grad():
-        seg, clf = _dev(seg), _dev(clf)
+        seg, clf = dev(seg), dev(clf)
         assert RF.fuse_covered(net, seg, clf)
         out = RF.fuse(net, seg, clf)
     return g, net, seg, clf, out
@@ -56,7 +54,7 @@ def _run_fuse(name, kind):
 def _run_chain(kind, want_sample_w=False):
     g, _, _, scores, seg = RC.chain_case()
     enc_net, fusion = RC.chain_modules(kind, DEV)
-    scores, seg = _dev(scores), _dev(seg)
+    scores, seg = dev(scores), dev(seg)
 
     def chain():
         return RF.fuse(fusion, seg, RF.encode(enc_net, scores, want_sample_w=want_sample_w)[0])
@@ -64,20 +62,6 @@ def _run_chain(kind, want_sample_w=False):
     with torch.no_grad():
         out = chain()
     return g, chain, out
-
-
-def _record(tag, errs, ref_err):
-    """Print the line of a case and keep it for the table; the table is rewritten whenever a row is added."""
-    line = fused_f64.report(tag, errs, ref_err)
-    print(line)
-    _ROWS[tag] = line.strip()
-    if not TABLE:
-        return
-    os.makedirs(os.path.dirname(os.path.abspath(TABLE)), exist_ok=True)
-    with open(TABLE, "w") as fh:
-        fh.write("RTS instance-score encoder and learners fusion on the MI355X against the float64 run of the plain-torch stand-in\n"
-                 "(tests/test_gpu_rts_fusion.py): per output max |out - float64| and its ratio to ref_err, the fp32 CPU stand-in's own\n"
-                 f"distance from float64 on that case; bound = {fused_f64.FACTOR} x ref_err.\n\n" + "\n".join(_ROWS.values()) + "\n")
 
 
 @pytest.mark.parametrize("name", RC.ENC_CASES)
@@ -110,7 +94,7 @@ def test_fuse_matches_reference_golden(name, kind):
             plain = torch.nn.functional.conv2d(torch.cat([seg[0], clf[0]], 1).double(), net.fusion_conv1.weight.double(),
                                                net.fusion_conv1.bias.double(), padding=1)
             anchor = RC.fuse_anchor(name, kind)
-            assert float((out[0].double() - plain).abs().max()) <= fused_f64.bound(anchor.ref_err)
+            assert float((out[0].double() - plain).abs().max()) <= f64_bound.bound(anchor.ref_err)
 
 
 @pytest.mark.parametrize("kind", RC.FUSION_TYPES)
@@ -128,9 +112,7 @@ def test_chain_matches_reference_golden(kind):
 def test_encoder_within_float64_bound(name):
     g, net, s, enc, sw = _run_enc(name)
     a = RC.enc_anchor(name)
-    errs = fused_f64.errors(a.want, {"label_enc": enc, "sample_w": sw})
-    _record(f"enc_{name}", errs, a.ref_err)
-    assert max(errs.values()) <= fused_f64.bound(a.ref_err)
+    f64_bound.held(f"enc_{name}", {"label_enc": enc, "sample_w": sw}, a.want, a.ref_err, table=TABLE)
 
 
 @pytest.mark.parametrize("kind", RC.FUSION_TYPES)
@@ -138,18 +120,14 @@ def test_encoder_within_float64_bound(name):
 def test_fuse_within_float64_bound(name, kind):
     g, net, seg, clf, out = _run_fuse(name, kind)
     a = RC.fuse_anchor(name, kind)
-    errs = fused_f64.errors(a.want, {"decoder_input": out})
-    _record(f"fuse_{name}_{kind}", errs, a.ref_err)
-    assert max(errs.values()) <= fused_f64.bound(a.ref_err)
+    f64_bound.held(f"fuse_{name}_{kind}", {"decoder_input": out}, a.want, a.ref_err, table=TABLE)
 
 
 @pytest.mark.parametrize("kind", RC.FUSION_TYPES)
 def test_chain_within_float64_bound(kind):
     g, chain, out = _run_chain(kind)
     a = RC.chain_anchor(kind)
-    errs = fused_f64.errors(a.want, {"decoder_input": out})
-    _record(f"{RC.CHAIN}_{kind}", errs, a.ref_err)
-    assert max(errs.values()) <= fused_f64.bound(a.ref_err)
+    f64_bound.held(f"{RC.CHAIN}_{kind}", {"decoder_input": out}, a.want, a.ref_err, table=TABLE)
 
 
 @pytest.mark.parametrize("name", ["odd", "deployed", "dims"])
@@ -198,7 +176,7 @@ def test_graph_capture_of_the_chain_replays_the_eager_bits(kind):
 def test_cache_follows_load_state_dict_and_in_place_updates():
     g, n, H, W, dims, use_bn, sd, scores = RC.enc_case("bn")
     net = RC.enc_module("bn", DEV)
-    s = _dev(scores)[:, None]
+    s = dev(scores)[:, None]
     other = synth.label_enc_state(int(g["state_seed"]) + 50, dims, use_bn)
     with torch.no_grad():
         first = RF.encode(net, s)
@@ -257,11 +235,11 @@ def test_install_dispatches_an_rts_net_built_from_the_bundles_parts(amd, kind):
                  clf_encoder=ResidualDS16SW_Clf(layer_dims=synth.LABEL_ENC_DIMS, use_bn=False), clf_enc_input="sc",
                  fusion_module=LearnersFusion(kind)).to(DEV).eval()
     rng = np.random.default_rng(5101)
-    feats = {L: _dev(np.maximum(rng.standard_normal((1, fc, H, W), dtype=np.float32), 0)) for L, fc, H, W in c["levels"]}
+    feats = {L: dev(np.maximum(rng.standard_normal((1, fc, H, W), dtype=np.float32), 0)) for L, fc, H, W in c["levels"]}
     h, w = c["levels"][1][2:]
-    feat_tm = _dev(rng.standard_normal((1, C, h, w), dtype=np.float32) * np.float32(0.05))
-    filt = _dev(rng.standard_normal((1, f, C, 3, 3), dtype=np.float32) * np.float32(0.3))
-    scores = _dev(synth.score_maps(5102, 1, 2, 3))[None]                # (1 frame, 1 sequence, 2, 3): resized to 3 x 4 by the fuse
+    feat_tm = dev(rng.standard_normal((1, C, h, w), dtype=np.float32) * np.float32(0.05))
+    filt = dev(rng.standard_normal((1, f, C, 3, 3), dtype=np.float32) * np.float32(0.3))
+    scores = dev(synth.score_maps(5102, 1, 2, 3))[None]                # (1 frame, 1 sequence, 2, 3): resized to 3 x 4 by the fuse
     enc_key, seg_key = "ResidualDS16SW_Clf.forward", "RTSNet.segment_target"
     amd.stats.clear()
     with torch.no_grad():

@@ -1,7 +1,7 @@
 """Segmentation read-out, object merge and mask patch on the MI355X (seg_readout.hip through pytracking_amd.seg_readout) against the goldens
 of the unmodified reference (tools/make_golden_seg_readout.py) and the float64 restatements of tests/seg_readout_cases.py.
 
-Bounds.  Every fp32 output is held to FACTOR x max(ref_fp32_err, 2^-23 max|want|) of float64 -- FACTOR is tests/fused_f64.py's, unchanged;
+Bounds.  Every fp32 output is held to FACTOR x max(ref_fp32_err, 2^-23 max|want|) of float64 -- the bound of tests/f64_bound.py with its ulp_of_max floor;
 ref_fp32_err is the reference's own fp32 distance from float64 on that output, the floor is one fp32 ulp of the output's range -- and to the
 project's 1e-4 of the golden, absolute (1e-4 of the magnitude only where FACTOR fp32 ulp of the quantity already exceed 1e-4: prob_sum
 above 200, the moments of the 720 x 1280 image -- see golden_tol).  Masks,
@@ -10,15 +10,15 @@ boxes and label maps are compared exactly wherever the float64 decision has a ma
 SEG_READOUT_F64_OUT names a file, written there as a table (profiles/seg_readout_f64.txt is the table of such a run).
 
 Every test prints its measured figures before it asserts (run with -s)."""
-import os
 from collections import OrderedDict
 
 import numpy as np
 import pytest
 import torch
 
-import fused_f64
+import f64_bound
 import seg_readout_cases as SC
+from f64_bound import dev, needs_bundle
 from oracle import ref_harness
 from pytracking_amd import seg_readout as SR
 
@@ -26,41 +26,25 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 ATOL = 1e-4
-ULP = 2.0 ** -23
 MARGIN, EXCLUDED_MAX = 1e-5, 0.005
-TABLE = os.environ.get("SEG_READOUT_F64_OUT")
-needs_bundle = pytest.mark.skipif(not ref_harness.available(), reason="no reference tree / bundle (oracle/_ref)")
-_ROWS, _WANT = OrderedDict(), {}
+TABLE = f64_bound.Table("SEG_READOUT_F64_OUT",
+                        "Segmentation read-out, object merge and their statistics on the MI355X against float64 (tests/test_gpu_seg_readout.py):\n"
+                        "per output max |out - float64| and its ratio to max(ref_fp32_err, 2^-23 max|want|) -- the reference's own fp32\n"
+                        f"distance from float64 on that output, floored at one fp32 ulp of its range; bound = {f64_bound.FACTOR} x that.")
+_WANT = {}
 
 
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def bound(ref_err, want):
-    return fused_f64.FACTOR * max(float(ref_err), ULP * float(np.abs(want).max()))
+def hold_rows(tag, rows, table=TABLE):
+    """rows: [(output, error, want, ref_err)], each output held to its own ref_err and the ulp of its own range."""
+    for q, e, w, r in rows:
+        f64_bound.held(tag, {q: float(e)}, None, r, floor=f64_bound.ulp_of_max(w), table=table)
 
 
 def golden_tol(golden):
     """The project's absolute 1e-4 against a golden; for a quantity so large that FACTOR fp32 ulp of it exceed 1e-4 (prob_sum and the
     moments of the 720 x 1280 image: both sides are fp32 numbers, each a few ulp from float64) 1e-4 of its magnitude instead."""
     top = float(np.abs(golden).max())
-    return ATOL if fused_f64.FACTOR * ULP * top <= ATOL else ATOL * top
-
-
-def _record(tag, rows):
-    """rows: [(output, error, bound, ref_err)].  Print the line of a case and keep it for the table."""
-    line = f"{tag}: " + "  ".join(f"{q} {e:.3e} ({e / b * fused_f64.FACTOR:.2f}x of {b / fused_f64.FACTOR:.2e})" for q, e, b, _ in rows)
-    print("\n" + line)
-    _ROWS[tag] = line
-    if not TABLE:
-        return
-    os.makedirs(os.path.dirname(os.path.abspath(TABLE)), exist_ok=True)
-    with open(TABLE, "w") as fh:
-        fh.write("Segmentation read-out, object merge and their statistics on the MI355X against float64 (tests/test_gpu_seg_readout.py):\n"
-                 "per output max |out - float64| and, in brackets, its ratio to max(ref_fp32_err, 2^-23 max|want|) -- the reference's own fp32\n"
-                 f"distance from float64 on that output, floored at one fp32 ulp of its range; bound = {fused_f64.FACTOR} x that.\n\n"
-                 + "\n".join(_ROWS.values()) + "\n")
+    return ATOL if f64_bound.FACTOR * f64_bound.ULP * top <= ATOL else ATOL * top
 
 
 def readout_want(name):
@@ -78,17 +62,17 @@ def merge_want(name):
 
 def run_readout(name, outputs=SR.OUTPUTS):
     crop, image, scale, pos, _ = SC.READOUT_CASES[name] if name != "miss" else SC.MISS
-    return SR.crop_to_image(_dev(SC.readout_input(name))[None, None], image, scale, pos, outputs=outputs)
+    return SR.crop_to_image(dev(SC.readout_input(name))[None, None], image, scale, pos, outputs=outputs)
 
 
 def _stat_rows(got, want, ref):
-    """Statistics of a device block against a float64 dict: [(name, error, bound, ref_err)] for the moments as the trackers read them."""
+    """Statistics of a device block against a float64 dict: [(name, error, want, ref_err)] for the moments as the trackers read them."""
     rows = []
     for key in ("prob_sum", "e_y", "e_x"):
-        rows.append((key, abs(got[key] - want[key]), bound(ref.get(key, 0.0), want[key]), ref.get(key, 0.0)))
+        rows.append((key, abs(got[key] - want[key]), want[key], ref.get(key, 0.0)))
     for key in ("var_y", "var_x"):                                      # held as the size the reference returns: sqrt(var) * factor
         g, w = SC.SZ_FACTOR * np.sqrt(got[key]), SC.SZ_FACTOR * np.sqrt(want[key])
-        rows.append(("sz" + key[3:], abs(g - w), bound(ref.get("sz", 0.0), w), ref.get("sz", 0.0)))
+        rows.append(("sz" + key[3:], abs(g - w), w, ref.get("sz", 0.0)))
     return rows
 
 
@@ -103,14 +87,9 @@ def test_readout_against_float64_and_golden(name):
     st = SC.stats_dict(host.stats.numpy())
     ref = {"prob_sum": float(g["ref_fp32_err.prob_sum"]), "e_y": float(g["ref_fp32_err.lwl_pos"]), "e_x": float(g["ref_fp32_err.lwl_pos"]),
            "sz": float(g["ref_fp32_err.lwl_sz"])}
-    rows = [("scores_im", float(np.abs(scores - want["scores_im"]).max()), bound(g["ref_fp32_err.scores_im"], want["scores_im"]),
-             float(g["ref_fp32_err.scores_im"])),
-            ("prob_im", float(np.abs(prob - want["prob_im"]).max()), bound(g["ref_fp32_err.scores_im"] / 4, want["prob_im"]),
-             float(g["ref_fp32_err.scores_im"]) / 4)]                   # sigmoid' <= 1/4
-    rows += _stat_rows(st, want["stats"], ref)
-    _record("readout_" + name, rows)
-    for q, e, b, _ in rows:
-        assert e <= b, (q, e, b)
+    rows = [("scores_im", float(np.abs(scores - want["scores_im"]).max()), want["scores_im"], float(g["ref_fp32_err.scores_im"])),
+            ("prob_im", float(np.abs(prob - want["prob_im"]).max()), want["prob_im"], float(g["ref_fp32_err.scores_im"]) / 4)]   # sigmoid' <= 1/4
+    hold_rows("readout_" + name, rows + _stat_rows(st, want["stats"], ref))
     # the golden, within the project's 1e-4 (golden_tol: relative only where fp32 cannot resolve 1e-4)
     assert np.abs(scores[::sub, ::sub] - g["scores_im"]).max() <= ATOL
     gprob = 1.0 / (1.0 + np.exp(-g["scores_im"].astype(np.float64)))   # the reference's next line: sigmoid of its score image
@@ -159,7 +138,7 @@ def test_readout_optional_outputs_and_input_views():
     none = run_readout(name, outputs=())
     assert torch.equal(none.stats, full.stats)
     crop, image, scale, pos, _ = SC.READOUT_CASES[name]
-    s = _dev(SC.readout_input(name))
+    s = dev(SC.readout_input(name))
     padded = torch.zeros(crop[0] + 3, crop[1] + 5, device=DEV)
     padded[1:crop[0] + 1, 2:crop[1] + 2] = s
     view = padded[1:crop[0] + 1, 2:crop[1] + 2]                         # a non-contiguous view of the same values
@@ -182,7 +161,7 @@ def test_state_repeats_the_readout_statistics_bit_for_bit(name):
 def test_state_of_a_signed_image_separates_the_clamped_moments():
     img = (SC.blob_scores(4401, 45, 70) / 6.0).astype(np.float32)      # values in about [-0.6, 0.6]
     want = SC.state_f64(img, img > 0.5)
-    got = SC.stats_dict(SR.state(_dev(img)).cpu().numpy())
+    got = SC.stats_dict(SR.state(dev(img)).cpu().numpy())
     for k in SC.STAT_KEYS[:10]:                                         # blocked fp32 sums of 3150 terms of magnitude <= 0.6: well inside 2e-5 relative
         assert abs(got[k] - want[k]) <= 2e-5 * max(1.0, abs(want[k])), (k, got[k], want[k])
     assert got["prob_sum_c"] > got["prob_sum"]
@@ -193,23 +172,19 @@ def test_state_of_a_signed_image_separates_the_clamped_moments():
 def test_merge_against_float64_and_golden(name):
     g, want = SC.golden("merge", name), merge_want(name)
     N, (H, W), _ = SC.MERGE_CASES[name]
-    scores = _dev(SC.merge_input(name)[0])
+    scores = dev(SC.merge_input(name)[0])
     out = SR.merge(scores)
     host = out.to_host()
     prob, labels = host.prob.numpy(), host.labels.numpy()
     assert prob.shape == (N + 1, H, W) and labels.shape == (H, W) and labels.dtype == np.uint8 and host.stats.shape == (N, SR.STATS)
     assert not np.isnan(prob).any() and not np.isnan(host.stats.numpy()[:, :1]).any()
     ref = float(g["ref_fp32_err.prob"])
-    rows = [("prob", float(np.abs(prob - want["prob"]).max()), bound(ref, want["prob"]), ref)]
+    hold_rows("merge_" + name, [("prob", float(np.abs(prob - want["prob"]).max()), want["prob"], ref)])
     box_ref = float(g["ref_fp32_err.lwl_boxes"])
     for i in range(N):
         st, w = SC.stats_dict(host.stats[i].numpy()), want["stats"][i]
         srows = _stat_rows(st, w, {"prob_sum": box_ref, "e_y": box_ref, "e_x": box_ref, "sz": box_ref})
-        rows += [(f"{q}[{i}]", e, b, r) for q, e, b, r in srows] if N <= 3 else []
-        for q, e, b, _ in srows:
-            assert e <= b, (i, q, e, b)
-    _record("merge_" + name, rows)
-    assert rows[0][1] <= rows[0][2]
+        hold_rows("merge_" + name, [(f"{q}[{i}]", e, v, r) for q, e, v, r in srows], table=TABLE if N <= 3 else None)   # the table keeps the small cases' rows
     assert np.abs(prob[1:] - g["prob"]).max() <= ATOL
     # 0 and 1 where the reference has them
     assert np.array_equal(prob[1:] == 0, g["prob"] == 0) and np.array_equal(prob[1:] == 1, g["prob"] == 1)
@@ -239,7 +214,7 @@ def test_merge_extreme_scores_end_in_zero_and_one():
     want = SC.merge_f64(s.cpu().numpy())
     p = m.prob.numpy()
     print("\nmerge extremes:\n", p.reshape(3, 8))
-    assert not np.isnan(p).any() and np.abs(p - want["prob"]).max() <= 4 * ULP
+    assert not np.isnan(p).any() and np.abs(p - want["prob"]).max() <= 4 * f64_bound.ULP
     assert p[1, 0, 0] == 1.0 and p[2, 0, 0] == 0.0 and p[0, 0, 0] == 0.0                 # +100 against -100
     assert p[0, 0, 1] == 1.0 and p[1, 0, 1] == 0.0 and p[2, 0, 1] == 0.0                 # both at -100: background
     assert p[1, 0, 2] == 0.5 and p[2, 0, 2] == 0.5 and m.labels[0, 2] == 1               # a tie: the first maximum wins
@@ -250,7 +225,7 @@ def test_merge_extreme_scores_end_in_zero_and_one():
 def test_mask_patch_equals_golden(name):
     g = SC.golden("patch", name)
     _, pos, ssz, osz, mode, _ = SC.PATCH_CASES[name]
-    im = _dev(SC.patch_input(name))[None, None]
+    im = dev(SC.patch_input(name))[None, None]
     patch, coord = SR.sample_mask_patch(im, torch.Tensor(list(pos)), torch.Tensor(list(ssz)), None if osz is None else torch.Tensor(list(osz)),
                                         mode=mode)
     assert patch.shape == (1, 1) + g["patch"].shape and np.array_equal(patch[0, 0].cpu().numpy(), g["patch"])
@@ -266,8 +241,8 @@ def test_mask_patch_equals_golden(name):
 def test_graph_capture_of_readout_then_merge_replays_the_eager_bits():
     name = "ragged_a"
     crop, image, scale, pos, _ = SC.READOUT_CASES[name]
-    s = _dev(SC.readout_input(name))
-    other = _dev(SC.blob_scores(4500, *image))
+    s = dev(SC.readout_input(name))
+    other = dev(SC.blob_scores(4500, *image))
 
     def chain():
         r = SR.crop_to_image(s, image, scale, pos)
@@ -326,7 +301,7 @@ def test_installed_methods_keep_the_reference_contract(amd):
     cpu_scores = torch.from_numpy(SC.readout_input(name))[None, None]
     scores, im = cpu_scores.to(DEV), torch.empty(1, 3, *image)
     s_t, p_t = torch.tensor(scale, dtype=torch.float32), torch.tensor(pos, dtype=torch.float64)
-    b = bound(g["ref_fp32_err.scores_im"], g["scores_im"]) + 4 * float(g["ref_fp32_err.scores_im"])      # both sides against float64
+    b = f64_bound.bound(g["ref_fp32_err.scores_im"], floor=f64_bound.ulp_of_max(g["scores_im"])) + 4 * float(g["ref_fp32_err.scores_im"])      # both sides against float64
     amd.stats.clear()
     for cls in (LWL, STAHelper):
         key = cls.__name__ + ".convert_scores_crop_to_image"
@@ -365,7 +340,7 @@ def test_installed_methods_keep_the_reference_contract(amd):
             for i in got["segmentation_raw"]:
                 a, w = got["segmentation_raw"][i], want["segmentation_raw"][i]
                 assert isinstance(a, np.ndarray) and a.dtype == w.dtype and a.shape == w.shape
-                assert np.abs(a - w).max() <= bound(gm["ref_fp32_err.prob"], w) + 4 * float(gm["ref_fp32_err.prob"])
+                assert np.abs(a - w).max() <= f64_bound.bound(gm["ref_fp32_err.prob"], floor=f64_bound.ulp_of_max(w)) + 4 * float(gm["ref_fp32_err.prob"])
             assert got["time"] == want["time"] and list(got["target_bbox"]) == list(want["target_bbox"])
             for i in got["target_bbox"]:
                 a, w = got["target_bbox"][i], want["target_bbox"][i]

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import tamos_cases as TC
+import f64_bound
 import tamos_f64 as F64
 from pytracking_amd import _lib
 from pytracking_amd.filter import _ptr, _stream
@@ -58,16 +59,14 @@ def test_case_within_the_float64_bound(name):
     cfg = TC.CASES[name]
     assert TC.case_routes(_lib.lib(), name) == (0, TC.ROUTES[name])                     # the library under test picks the pinned routes
     got, again, inputs_unchanged = run(name)
-    want = F64.want(name)
+    want = F64.anchor(name).want
     assert set(got) == set(want)
     for q, t in got.items():
         assert t.numel() == want[q].size and bool(torch.isfinite(t).all()), q
         assert torch.equal(t, again[q]), q                                               # no atomics: the same inputs give the same bits
     assert inputs_unchanged
     assert tuple(got["scores"].shape) == (1, cfg["n_seq"], cfg["T"], cfg["H"], cfg["W"])
-    errs = F64.errors(want, got)
-    print(F64.report(name, errs, TC.REF_ERR[name]))
-    assert F64.within(errs, TC.REF_ERR[name]), errs
+    f64_bound.held(name, got, want, TC.REF_ERR[name], F64.F, group=F64.group)
 
 
 def _abi(cfg, params, inputs, parallel, gth, stream_call=None):
@@ -106,11 +105,9 @@ def test_abi_fills_nan_prefilled_outputs(name):
         call()
     torch.cuda.synchronize()
     assert bool(torch.isfinite(filters).all()) and bool(torch.isfinite(enc).all())
-    want = F64.want(name)
+    want = F64.anchor(name).want
     got = ({"cls_filter": filters[0:1], "bbreg_filter": filters[1:2], "cls_enc": enc[0], "bbreg_enc": enc[1]} if par else {"filter": filters, "enc": enc})
-    errs = F64.errors({q: want[q] for q in got}, got)
-    print(F64.report(name + " (C ABI)", errs, TC.REF_ERR[name]))
-    assert F64.within(errs, TC.REF_ERR[name]), errs
+    f64_bound.held(name + " (C ABI)", got, {q: want[q] for q in got}, TC.REF_ERR[name], F64.F, group=F64.group)
     if name == "mask9_gth2":                                     # an empty mask: both batch rows are the same problem
         assert torch.equal(filters[0], filters[1]) and torch.equal(enc[0], enc[1])
 

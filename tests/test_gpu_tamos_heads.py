@@ -14,8 +14,10 @@ import pytest
 import torch
 
 import tamos_heads_cases as HC
+import f64_bound
 import tamos_heads_f64 as F64
 import tomp_cases as TPC
+from f64_bound import dev
 from pytracking_amd import _lib
 from pytracking_amd.filter import _ptr, _stream
 
@@ -24,10 +26,6 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _RUNS = {}
-
-
-def dv(a):
-    return torch.from_numpy(a.copy()).to(DEV)
 
 
 def golden(name):
@@ -40,7 +38,7 @@ def run_reg(name):
         n_img, T, D, H, W = HC.REG[name]
         params, feat, filt = HC.reg_case(name)
         reg = HC.build_regressor(D, params, DEV)
-        f, w = dv(feat)[None], dv(filt).reshape(n_img, T, D, 1, 1)
+        f, w = dev(feat)[None], dev(filt).reshape(n_img, T, D, 1, 1)
         keep = (f.clone(), w.clone())
         with torch.no_grad():
             got = reg(f, w).clone()
@@ -56,7 +54,7 @@ def run_fpn(name):
         n, C_hi, C_lo, D, H3, W3, H2, W2 = HC.FPN[name]
         params, hi, lo = HC.fpn_case(name)
         m = HC.build_fpn(name, params, DEV)
-        enc, back = dv(lo)[None], {"layer2": dv(hi)}
+        enc, back = dev(lo)[None], {"layer2": dev(hi)}
         keep = (enc.clone(), back["layer2"].clone())
         with torch.no_grad():
             got = {q: t.clone() for q, t in m(enc, back).items()}
@@ -73,23 +71,21 @@ def _check(name, got, again, unchanged, want):
         assert bool(torch.isfinite(t).all()), q
         assert torch.equal(t, again[q]), q                         # no atomics: the same inputs give the same bits
     assert unchanged
-    errs = F64.errors(want, got)
-    print(F64.report(name, errs, HC.REF_ERR[name]))
-    assert F64.within(errs, HC.REF_ERR[name]), errs
+    f64_bound.held(name, got, want, HC.REF_ERR[name], F64.F)
 
 
 @pytest.mark.parametrize("name", HC.SMALL_REG)
 def test_regressor_within_the_float64_bound(name):
     assert HC.case_routes(_lib.lib(), name) == (0, HC.ROUTES[name])
     got, again, unchanged = run_reg(name)
-    _check(name, {"ltrb": got}, {"ltrb": again}, unchanged, F64.want(name))
+    _check(name, {"ltrb": got}, {"ltrb": again}, unchanged, F64.anchor(name).want)
 
 
 @pytest.mark.parametrize("name", HC.SMALL_FPN)
 def test_fpn_within_the_float64_bound(name):
     assert HC.case_routes(_lib.lib(), name) == (0, HC.ROUTES[name])
     got, again, unchanged = run_fpn(name)
-    _check(name, got, again, unchanged, F64.want(name))
+    _check(name, got, again, unchanged, F64.anchor(name).want)
 
 
 def test_deployed_regressor_within_the_float64_bound_and_equals_the_reference_golden():
@@ -106,7 +102,7 @@ def test_deployed_regressor_within_the_float64_bound_and_equals_the_reference_go
         print(f"\n{name} vs reference {tag}: max |gpu - reference| {err:.3e} ({err / HC.REF_ERR[name]:.2f}x ref_err {HC.REF_ERR[name]:.3e}, "
               f"bound {F64.F} x ref_err for f64)")
         assert err <= 1e-4, (tag, err)
-        assert tag != "f64" or err <= F64.bound(HC.REF_ERR[name]), err
+        assert tag != "f64" or err <= f64_bound.bound(HC.REF_ERR[name], F64.F), err
 
 
 def test_deployed_fpn_within_the_float64_bound():
@@ -119,7 +115,7 @@ def test_deployed_fpn_within_the_float64_bound():
         assert bool(torch.isfinite(t).all()) and torch.equal(t, again[q]), q
         err = float(np.abs(t.double().cpu().numpy().reshape(-1)[::int(g[f"{q}_stride"])] - g[f"{q}_f64"]).max())
         print(f"\n{name} {q}: max |gpu - float64| {err:.3e} ({err / HC.REF_ERR[name]:.2f}x ref_err {HC.REF_ERR[name]:.3e}, bound {F64.F} x)")
-        assert err <= F64.bound(HC.REF_ERR[name]), (q, err)
+        assert err <= f64_bound.bound(HC.REF_ERR[name], F64.F), (q, err)
 
 
 def _reg_abi(name):
@@ -129,7 +125,7 @@ def _reg_abi(name):
     reg = HC.build_regressor(D, params, DEV)
     with torch.cuda.device(0):
         pack = reg._params()
-    f, w = dv(feat), dv(filt)
+    f, w = dev(feat), dev(filt)
     nb = L.pt_tamos_bbreg_ws_bytes(n_img, T, D, H, W)
     assert nb > 0
     ws = torch.empty(nb, dtype=torch.uint8, device=DEV)
@@ -148,9 +144,7 @@ def test_regressor_abi_fills_nan_prefilled_output(name):
         call()
     torch.cuda.synchronize()
     assert bool(torch.isfinite(out).all())
-    errs = F64.errors(F64.want(name), {"ltrb": out})
-    print(F64.report(name + " (C ABI)", errs, HC.REF_ERR[name]))
-    assert F64.within(errs, HC.REF_ERR[name]), errs
+    f64_bound.held(name + " (C ABI)", {"ltrb": out}, F64.anchor(name).want, HC.REF_ERR[name], F64.F)
 
 
 @pytest.mark.parametrize("name", ["fpn_odd", "fpn_d256"])
@@ -161,11 +155,11 @@ def test_fpn_abi_fills_nan_prefilled_outputs_and_skips_feat3_on_request(name):
     m = HC.build_fpn(name, params, DEV)
     with torch.cuda.device(0):
         pack = m._params()
-    h, l = dv(hi), dv(lo)
+    h, l = dev(hi), dev(lo)
     nb = L.pt_fpn2_ws_bytes(n, C_hi, C_lo, D, H2, W2, H3, W3)
     assert nb > 0
     ws = torch.empty(nb, dtype=torch.uint8, device=DEV)
-    want = F64.want(name)
+    want = F64.anchor(name).want
     for want3 in (1, 0):
         f2 = torch.full((n, D, H2, W2), float("nan"), device=DEV)
         f3 = torch.full((n, D, H3, W3), float("nan"), device=DEV)
@@ -179,9 +173,7 @@ def test_fpn_abi_fills_nan_prefilled_outputs_and_skips_feat3_on_request(name):
             got["feat3"] = f3
         else:
             assert bool(torch.isnan(f3).all())                       # skipped: left as it was
-        errs = F64.errors({q: want[q] for q in got}, got)
-        print(F64.report(f"{name} (C ABI, want_feat3={want3})", errs, HC.REF_ERR[name]))
-        assert F64.within(errs, HC.REF_ERR[name]), errs
+        f64_bound.held(f"{name} (C ABI, want_feat3={want3})", got, {q: want[q] for q in got}, HC.REF_ERR[name], F64.F)
 
 
 def test_graph_replay_equals_the_eager_call():
@@ -213,11 +205,11 @@ def test_each_object_equals_the_single_filter_path(name):
     with torch.no_grad():
         for i in range(n_img):
             for o in range(T):
-                one = single(dv(feat[i:i + 1])[None], dv(filt[i, o]).reshape(1, D, 1, 1))
+                one = single(dev(feat[i:i + 1])[None], dev(filt[i, o]).reshape(1, D, 1, 1))
                 assert tuple(one.shape) == (1, 1, 4, H, W)
                 worst = max(worst, float((one[0, 0].double() - got[0, i, o].double()).abs().max()))
     print(f"\n{name}: max |multi-object - single-filter path| {worst:.3e} ({worst / HC.REF_ERR[name]:.2f}x ref_err)")
-    assert worst <= F64.bound(HC.REF_ERR[name]), worst
+    assert worst <= f64_bound.bound(HC.REF_ERR[name], F64.F), worst
 
 
 def test_fpn_to_regressor_chain_through_the_classes():
@@ -228,14 +220,12 @@ def test_fpn_to_regressor_chain_through_the_classes():
     params, hi, lo = HC.fpn_case(fname)
     fpn, reg = HC.build_fpn(fname, params, DEV), HC.build_regressor(D, rp, DEV)
     with torch.no_grad():
-        maps = fpn(dv(lo)[None], {"layer2": dv(hi)})
-        ltrb = reg(maps["feat2"], dv(filt).reshape(n, T, D, 1, 1))
+        maps = fpn(dev(lo)[None], {"layer2": dev(hi)})
+        ltrb = reg(maps["feat2"], dev(filt).reshape(n, T, D, 1, 1))
     torch.cuda.synchronize()
     got = {"feat2": maps["feat2"], "ltrb": ltrb}
     assert all(bool(torch.isfinite(t).all()) for t in got.values())
-    errs = F64.errors(F64.want(name), got)
-    print(F64.report(name, errs, HC.REF_ERR[name]))
-    assert F64.within(errs, HC.REF_ERR[name]), errs
+    f64_bound.held(name, got, F64.anchor(name).want, HC.REF_ERR[name], F64.F)
 
 
 def test_mirror_raises_before_any_launch_on_what_the_abi_refuses():

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import tomp_cases as TC
+import f64_bound
 import tomp_f64 as F64
 from pytracking_amd import _lib
 from pytracking_amd.filter import _ptr, _stream
@@ -26,9 +27,7 @@ def _check(name, want, got):
     assert set(got) == set(want)
     for q, t in got.items():
         assert t.numel() == want[q].size and bool(torch.isfinite(t).all()), q          # finite before anything is compared
-    errs = F64.errors(want, got)
-    print(F64.report(name, errs, TC.REF_ERR[name]))
-    assert F64.within(errs, TC.REF_ERR[name]), errs
+    f64_bound.held(name, got, want, TC.REF_ERR[name], F64.F, group=F64.group)
 
 
 @pytest.mark.parametrize("name", list(TC.PREDICT))
@@ -45,7 +44,7 @@ def test_predictor_case_within_the_float64_bound(name):
             w, enc = pred.predict_filter(train, test, lab, ltrb)
             got = dict(filter=w, enc=enc)
     torch.cuda.synchronize()
-    _check(name, F64.want("predict", name), got)
+    _check(name, F64.anchor("predict", name).want, got)
 
 
 @pytest.mark.parametrize("name", list(TC.BBREG))
@@ -56,7 +55,7 @@ def test_box_regressor_case_within_the_float64_bound(name):
     with torch.no_grad():
         got = dict(ltrb=reg(T(feat), T(filt).reshape(1, D, 1, 1)))
     torch.cuda.synchronize()
-    _check(name, F64.want("bbreg", name), got)
+    _check(name, F64.anchor("bbreg", name).want, got)
 
 
 @pytest.mark.parametrize("name", list(TC.LINEAR))
@@ -70,7 +69,7 @@ def test_linear_case_within_the_float64_bound(name):
         rc = L.pt_tomp_linear_f32(_ptr(wd), _ptr(bd) if bias else None, _ptr(xd), _ptr(y), B, N, K, int(relu), _stream())
     assert rc == 0
     torch.cuda.synchronize()
-    _check(name, F64.want("linear", name), dict(y=y))
+    _check(name, F64.anchor("linear", name).want, dict(y=y))
 
 
 def test_module_refuses_what_the_abi_refuses():

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+import f64_bound
 import tcm_cases as TC
 import tcm_np
 from oracle import ref_harness
@@ -304,7 +305,7 @@ def test_numpy_descriptors_match_conv2d_in_float64(name):
             assert {(0, 0), (0, W), (H, 0), (H, W)} <= set(map(tuple, i.coords3[b]))
     f64 = TC.conv2d_at_points(i.x, i.weight, i.bias, i.coords3, torch.float64)
     err = float(np.abs(f64 - a.want).max())
-    print(f"\ndesc {name}: max |numpy - conv2d float64| {err:.3e}, ref_err {a.ref_err:.3e}, bound {TC.bound(a.ref_err):.3e}")
+    print(f"\ndesc {name}: max |numpy - conv2d float64| {err:.3e}, ref_err {a.ref_err:.3e}, bound {f64_bound.bound(a.ref_err):.3e}")
     assert a.want.shape == (B, D, P) and err <= 1e-9
     assert 0 < a.ref_err < 1e-5                                                # fp32 rounding of sums of C * 16 terms of order 1
 
@@ -326,7 +327,7 @@ def test_numpy_matcher_matches_the_reference_in_float64(name):
     w, a = TC.match_want(name), TC.match_anchor(name)
     r64 = TC.reference_match(name, torch.float64)
     err = float(np.abs(r64["log_assignment"] - w["log_assignment"]).max())
-    print(f"\nmatch {name}: max |numpy - reference float64| {err:.3e}, ref_err {a.ref_err:.3e}, bound {TC.bound(a.ref_err):.3e}")
+    print(f"\nmatch {name}: max |numpy - reference float64| {err:.3e}, ref_err {a.ref_err:.3e}, bound {f64_bound.bound(a.ref_err):.3e}")
     assert r64["log_assignment"].dtype == np.float64 and err <= 1e-9
     np.testing.assert_array_equal(r64["matches0"], w["matches0"])
     np.testing.assert_array_equal(r64["matches1"], w["matches1"])
@@ -366,10 +367,10 @@ def test_desc_mutant_helper_is_the_anchor_without_a_mutation():
 def test_the_descriptor_bound_catches_the_mutant(name, mutation):
     a = TC.desc_anchor(name)
     diff = np.abs(_desc_mutant(name, **{mutation: True}) - a.want)
-    print(f"\ndesc {name}, mutant {mutation}: max |mutant - float64| {diff.max():.3e}, bound {TC.bound(a.ref_err):.3e}")
-    assert diff.max() > TC.bound(a.ref_err)
+    print(f"\ndesc {name}, mutant {mutation}: max |mutant - float64| {diff.max():.3e}, bound {f64_bound.bound(a.ref_err):.3e}")
+    assert diff.max() > f64_bound.bound(a.ref_err)
     if mutation == "drop_batch":                                               # image 0 is right, every later image is not
-        assert diff[0].max() == 0 and all(diff[b].max() > TC.bound(a.ref_err) for b in range(1, diff.shape[0]))
+        assert diff[0].max() == 0 and all(diff[b].max() > f64_bound.bound(a.ref_err) for b in range(1, diff.shape[0]))
 
 
 @pytest.mark.parametrize("name", ["9x64", "64x9"])
@@ -399,7 +400,7 @@ def test_the_matcher_bound_catches_the_mutant(name, mutation):
     diff = float(np.abs(Z - a.want["log_assignment"]).max())
     discrete = (not np.array_equal(m0, a.want["matches0"]) or not np.array_equal(m1, a.want["matches1"])
                 or not np.array_equal(ms0 == 0, a.want["match_scores0"] == 0))
-    print(f"\nmatch {name}, mutant {mutation}: max |mutant - float64| {diff:.3e}, bound {TC.bound(a.ref_err):.3e}, "
+    print(f"\nmatch {name}, mutant {mutation}: max |mutant - float64| {diff:.3e}, bound {f64_bound.bound(a.ref_err):.3e}, "
           f"discrete outputs differ: {discrete}")
-    assert diff > TC.bound(a.ref_err)
+    assert diff > f64_bound.bound(a.ref_err)
     assert discrete

@@ -13,7 +13,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-import fused_f64
+import f64_bound
 import label_enc_cases as LC
 import rts_fusion_cases as RC
 from oracle import ref_harness
@@ -118,7 +118,7 @@ def test_encoder_pack_arithmetic_reproduces_golden(name, L):
     enc, sw = RC.from_pack(pack, dims, scores)
     assert enc.shape == (n, dims[3], H, W) and sw.shape == enc.shape and g["label_enc"].shape == enc.shape
     err = max(float(np.abs(enc - g["label_enc"]).max()), float(np.abs(sw - g["sample_w"]).max()))
-    bound = fused_f64.bound(float(g["ref_fp32_err"]))
+    bound = f64_bound.bound(float(g["ref_fp32_err"]))
     print(f"\nrts_fusion_enc_{name}: max |pack arithmetic (float64) - golden| = {err:.3e}, bound {bound:.3e}")
     assert err <= bound
     assert float(g["ref_fp32_err"]) <= 1e-5
@@ -135,7 +135,7 @@ def test_fuse_pack_arithmetic_reproduces_golden(name, kind, L):
     out = RC.fuse_from_pack(kind, pack, seg[0], clf[0])
     assert out.shape == g["out." + kind].shape == (n, f) + target
     err = float(np.abs(out - g["out." + kind]).max())
-    bound = fused_f64.bound(float(g["ref_fp32_err." + kind]))
+    bound = f64_bound.bound(float(g["ref_fp32_err." + kind]))
     print(f"\nrts_fusion_fuse_{name} {kind}: max |float64 restatement - golden| = {err:.3e}, bound {bound:.3e}")
     assert err <= bound and float(g["ref_fp32_err." + kind]) <= 1e-5
 
@@ -149,7 +149,7 @@ def test_chain_pack_arithmetic_reproduces_golden(kind, L):
     pack = RF.pack_fusion(fusion).numpy() if kind == "concat" else None
     out = RC.fuse_from_pack(kind, pack, seg[0], enc)
     err = float(np.abs(out - g["out." + kind]).max())
-    bound = fused_f64.bound(float(g["ref_fp32_err." + kind]))
+    bound = f64_bound.bound(float(g["ref_fp32_err." + kind]))
     print(f"\nrts_fusion_{RC.CHAIN} {kind}: max |float64 restatement - golden| = {err:.3e}, bound {bound:.3e}")
     assert out.shape == (1, dims[3]) + synth.RTS_CHAIN_CASE["target"] and err <= bound
 

@@ -1,6 +1,6 @@
 """Segmentation read-out, object merge and mask patch (pytracking_amd.seg_readout, seg_readout.hip) without a GPU: the exports exist and
 refuse bad arguments before any launch; the float64 restatements of tests/seg_readout_cases.py reproduce the goldens of the unmodified
-reference (tools/make_golden_seg_readout.py) within fused_f64.FACTOR x their ref_fp32_err (measured by the generator against float64 torch code of its own, not against these restatements);
+reference (tools/make_golden_seg_readout.py) within FACTOR x their ref_fp32_err (tests/f64_bound.py) (measured by the generator against float64 torch code of its own, not against these restatements);
 the restated fp32 nearest indices reproduce the golden mask patches bit for bit, where the float64 formula does not; the host placement
 rule reproduces the reference's window; install(seg_readout=True) rebinds exactly five symbols and hands CPU tensors to the reference."""
 import ctypes
@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-import fused_f64
+import f64_bound
 import seg_readout_cases as SC
 from oracle import ref_harness
 from pytracking_amd import _lib, seg_readout as SR
@@ -25,12 +25,6 @@ NAMES = ["pytracking.tracker.lwl.lwl.LWL.convert_scores_crop_to_image", "pytrack
          "pytracking.tracker.rts.sta_helper.STAHelper.convert_scores_crop_to_image"]
 SYMBOLS = ("pt_seg_readout_ws_bytes", "pt_seg_readout_f32", "pt_seg_state_ws_bytes", "pt_seg_state_f32", "pt_seg_merge_ws_bytes",
            "pt_seg_merge_f32", "pt_sample_mask_patch_f32")
-ULP = 2.0 ** -23
-
-
-def bound(ref_err):
-    """FACTOR x ref_fp32_err: the golden is the reference's fp32 run, ref_fp32_err its own distance from float64."""
-    return fused_f64.FACTOR * float(ref_err)
 
 
 @pytest.fixture(scope="module")
@@ -139,7 +133,7 @@ def test_readout_restatement_reproduces_golden(name):
     for kind in ("lwl", "rts"):
         got[kind + "_pos"], got[kind + "_sz"] = SC.target_state_f64(st, kind)
     for k, v in got.items():
-        err, b = float(np.abs(np.asarray(v) - g[k]).max()), bound(g["ref_fp32_err." + k])
+        err, b = float(np.abs(np.asarray(v) - g[k]).max()), f64_bound.bound(g["ref_fp32_err." + k])
         print(f"\nreadout_{name} {k}: |float64 restatement - golden| = {err:.3e}, bound {b:.3e}")
         assert err <= b, k
     assert int(g["near_zero"]) == 0                                     # no pixel of the reference sits on the zero crossing
@@ -192,7 +186,7 @@ def test_merge_restatement_reproduces_golden(name):
     assert scores.shape == (N, H, W) and scores.dtype == np.float32 and (scores == SC.FILL).any()
     assert N == 1 or set(np.unique(scores[0])) == {-100.0, 100.0}      # the GT-mask convention
     want = SC.merge_f64(scores)
-    err, b = float(np.abs(want["prob"][1:] - g["prob"]).max()), bound(g["ref_fp32_err.prob"])
+    err, b = float(np.abs(want["prob"][1:] - g["prob"]).max()), f64_bound.bound(g["ref_fp32_err.prob"])
     print(f"\nmerge_{name}: |float64 restatement - golden| = {err:.3e}, bound {b:.3e} (ref_fp32_err {float(g['ref_fp32_err.prob']):.2e})")
     assert err <= b and float(g["ref_fp32_err.prob"]) <= 2e-7 and not np.isnan(want["prob"]).any()
     assert np.abs(want["prob"].sum(0) - 1).max() <= 1e-6               # the aggregation is a distribution over background + objects
@@ -201,11 +195,11 @@ def test_merge_restatement_reproduces_golden(name):
     for i, st in enumerate(want["stats"]):
         p, s = SC.target_state_f64(st, "lwl")
         box = np.array([p[1] - (s[1] - 1) / 2, p[0] - (s[0] - 1) / 2, s[1], s[0]])
-        assert np.abs(box - g["lwl_boxes"][i]).max() <= bound(g["ref_fp32_err.lwl_boxes"])
+        assert np.abs(box - g["lwl_boxes"][i]).max() <= f64_bound.bound(g["ref_fp32_err.lwl_boxes"])
         x0, y0, x1, y1 = st["bbox"]
         assert np.array_equal(np.array([x0, y0, x1 - x0 + 1, y1 - y0 + 1]), g["rts_boxes"][i])
     # the reference's fp32 boxes are within a few ulp of their largest coordinate of float64
-    assert float(g["ref_fp32_err.lwl_boxes"]) <= 4 * ULP * float(np.abs(g["lwl_boxes"]).max())
+    assert float(g["ref_fp32_err.lwl_boxes"]) <= 4 * f64_bound.ULP * float(np.abs(g["lwl_boxes"]).max())
 
 
 @pytest.mark.parametrize("name", SC.PATCH_CASES)

@@ -16,9 +16,10 @@ import pytest
 import torch
 
 import tamos_cases as TC
+import f64_bound
 import tamos_f64 as F64
 import tamos_np as TN
-from fused_f64 import FACTOR
+from f64_bound import FACTOR
 from oracle import ref_harness
 from pytracking_amd import _lib
 
@@ -63,10 +64,10 @@ def test_restatement_equals_the_reference(name):
 def test_ref_err_is_the_committed_one(name):
     a = F64.anchor(name)
     assert list(a.ref_err) == list(TC.REF_ERR[name]) == ["predictor", "scores"]
-    print(F64.report(f"{name} (fp32 restatement)", a.ref_errs, TC.REF_ERR[name]))
+    print(f64_bound.report(f"{name} (fp32 restatement)", a.ref_errs, TC.REF_ERR[name], F64.F, group=F64.group))
     for grp, r in a.ref_err.items():
         assert F64.REF_ERR_BAND[0] * TC.REF_ERR[name][grp] <= r <= F64.REF_ERR_BAND[1] * TC.REF_ERR[name][grp], (grp, r)
-    assert F64.within(a.ref_errs, TC.REF_ERR[name])
+    assert f64_bound.within(a.ref_errs, TC.REF_ERR[name], F64.F, group=F64.group)
 
 
 def test_factor():
@@ -257,12 +258,12 @@ def test_bound_catches_seeded_defect(defect):
     ratios = {}
     for name in reached:
         a = F64.anchor(name)
-        errs = F64.errors_np(a.want, F64.outputs(name, np.float32, defect=defect))
+        errs = f64_bound.errors(a.want, F64.outputs(name, np.float32, defect=defect))
         ratios[name] = max(e / TC.REF_ERR[name]["predictor"] for q, e in errs.items() if F64.group(q) == "predictor")
-        assert not F64.within(errs, TC.REF_ERR[name]), (name, ratios[name])
+        assert not f64_bound.within(errs, TC.REF_ERR[name], F64.F, group=F64.group), (name, ratios[name])
     print(f"\n{defect}: worst output / ref_err " + " ".join(f"{n} {r:.3g}" for n, r in ratios.items()))
     assert min(ratios.values()) > F64.F_MAX
     if defect == "ln_eps":
         assert ratios["base_t3"] >= 12
     # the unmodified fp32 run stays inside
-    assert all(F64.within(F64.anchor(n).ref_errs, TC.REF_ERR[n]) for n in reached)
+    assert all(f64_bound.within(F64.anchor(n).ref_errs, TC.REF_ERR[n], F64.F, group=F64.group) for n in reached)

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import tamos_heads_cases as HC
+import f64_bound
 import tamos_heads_f64 as F64
 import tamos_heads_np as HN
 from oracle import ref_harness
@@ -46,7 +47,7 @@ def test_restatement_matches_the_reference_golden(name):
     e32 = float(np.abs(a.f32["ltrb"].reshape(-1).astype(np.float64) - g["ltrb_f64"]).max())
     ref32 = float(np.abs(g["ltrb_f32"].astype(np.float64) - g["ltrb_f64"]).max())
     print(f"\n{name}: float64 restatement vs reference float64 {e64:.3e}, fp32 restatement {e32:.3e}, reference fp32 vs its float64 {ref32:.3e}")
-    assert e64 <= 1e-10 and e32 <= 1e-4 and e32 <= F64.bound(HC.REF_ERR[name]) and ref32 <= 1e-4
+    assert e64 <= 1e-10 and e32 <= 1e-4 and e32 <= f64_bound.bound(HC.REF_ERR[name], F64.F) and ref32 <= 1e-4
 
 
 def test_deployed_golden_is_a_stride_and_the_reference_is_close_to_its_own_float64():
@@ -93,7 +94,7 @@ def test_seeded_defect_fails_the_bound(defect):
     """Each defect, run in fp32 like the kernel, must exceed F_MAX x ref_err on at least one small case (it does on every one)."""
     over = []
     for name in F64.DEFECT_CASES[defect]:
-        e = max(F64.errors_np(F64.want(name), F64.outputs(name, np.float32, defect)).values())
+        e = max(f64_bound.errors(F64.anchor(name).want, F64.outputs(name, np.float32, defect)).values())
         print(f"\ndefect {defect} on {name}: {e:.3e} = {e / HC.REF_ERR[name]:.1f} x ref_err")
         over.append(e > F64.F_MAX * HC.REF_ERR[name])
     assert any(over) and F64.F <= F64.F_MAX

@@ -17,8 +17,9 @@ import numpy as np
 import pytest
 
 import tomp_cases as TC
+import f64_bound
 import tomp_f64 as F64
-from fused_f64 import FACTOR
+from f64_bound import FACTOR
 from oracle import tomp_oracle as TO
 from pytracking_amd import _lib
 
@@ -195,8 +196,7 @@ def test_refusals_sit_at_the_documented_limits(L):
 def test_fp32_oracle_stays_within_the_bound_and_ref_err_is_the_committed_one(kind, name):
     a = F64.anchor(kind, name)                                   # asserts that the fp32 run's outputs are fp32
     assert list(a.ref_err) == list(TC.REF_ERR[name])
-    print(F64.report(f"{name} (fp32 oracle)", a.ref_errs, TC.REF_ERR[name]))
-    assert F64.within(a.ref_errs, TC.REF_ERR[name])
+    f64_bound.held(f"{name} (fp32 oracle)", a.ref_errs, None, TC.REF_ERR[name], F64.F, group=F64.group)
     lo, hi = F64.REF_ERR_BAND
     for g, r in a.ref_err.items():
         assert lo * TC.REF_ERR[name][g] <= r <= hi * TC.REF_ERR[name][g], (g, r, TC.REF_ERR[name][g])
@@ -292,7 +292,7 @@ def test_bound_catches_seeded_defect(monkeypatch, defect):
         with monkeypatch.context() as m:
             kw = seed(m, cfg)
             got = F64.predict_outputs(cfg, params, inputs, np.float32, **kw)
-        errs = F64.by_group(F64.errors_np(F64.want("predict", name), got))
+        errs = f64_bound.by_group(f64_bound.errors(F64.anchor("predict", name).want, got), F64.group)
         ratio = errs["predictor"] / TC.REF_ERR[name]["predictor"]
         ratios[name] = ratio
         assert ratio > F64.F, (name, ratio)

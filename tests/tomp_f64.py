@@ -9,23 +9,22 @@ them would hold the filters to the scores' error.
 numpy's BLAS blocks its sums by the thread count, so ref_err moves with the machine: tomp_cases.REF_ERR carries the values measured where
 the table was written, the CPU test holds the recomputed value to [0.5, 2] x the committed one, and the GPU test uses the committed one.
 
-F starts from the fused modules' FACTOR (tests/fused_f64.py) and is defined here and nowhere else.  The predictor's device error was
-measured against ref_err on the MI355X (profiles/tomp_routes_f64.txt): where every case stays at or below half of FACTOR x ref_err, F is
-FACTOR; otherwise twice the worst measured ratio, rounded up (the 2 covers the tens of per cent by which ref_err itself moves with the
+The anchor, the bound and the report are those of tests/f64_bound.py.  F starts from its FACTOR and is defined here and nowhere else.
+The predictor's device error was measured against ref_err on the MI355X (profiles/tomp_routes_f64.txt): where every case stays at or
+below half of FACTOR x ref_err, F is FACTOR; otherwise twice the worst measured ratio, rounded up (the 2 covers the tens of per cent by which ref_err itself moves with the
 summation blocking), and never above F_MAX = 32 -- the weakest seeded defect of tests/test_tomp_routes_cpu.py, a LayerNorm eps of 2e-5,
 still has to fail by a wide margin.
 
 `python tests/tomp_f64.py` prints the ROUTES_TEXT and REF_ERR tables of tests/tomp_cases.py from the built library and this CPU.
 Reads nothing outside the repository.  Test infrastructure only."""
-import math
 import os
 import sys
-from collections import OrderedDict, namedtuple
+from collections import OrderedDict
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from fused_f64 import FACTOR                   # noqa: E402
+import f64_bound                               # noqa: E402
 import tomp_cases as TC                        # noqa: E402
 from oracle import tomp_oracle as TO           # noqa: E402
 
@@ -34,17 +33,14 @@ F_MAX = 32
 # fifteen more outputs between 2.0 and 2.9, spread over the D = 128 ... 512 cases, none apart from the rest).  Above FACTOR / 2 = 2, so
 # F is twice it, rounded up.
 WORST_MEASURED = 2.98
-F = FACTOR if WORST_MEASURED <= FACTOR / 2 else math.ceil(2 * WORST_MEASURED)
-assert FACTOR <= F <= F_MAX
+F = f64_bound.raised_factor(WORST_MEASURED, F_MAX)
 REF_ERR_BAND = (0.5, 2.0)                     # recomputed ref_err / committed ref_err the CPU test accepts
 
 PREDICTOR = ("cls_filter", "bbreg_filter", "cls_enc", "bbreg_enc", "filter", "enc")
-Anchor = namedtuple("Anchor", "want f32 ref_err ref_errs")     # {output: float64 numpy, read-only}, {output: fp32 numpy}, {group: float}, {output: float}
-_CACHE = {}
 
 
 def bound(ref_err):
-    return F * ref_err
+    return f64_bound.bound(ref_err, F)
 
 
 def group(output):
@@ -88,54 +84,9 @@ def outputs(kind, name, dtype):
     return linear_outputs(w, b, x, relu, dtype)
 
 
-def want(kind, name):
-    """{output: float64 array, read-only} of a case, computed once per session."""
-    if ("want", kind, name) not in _CACHE:
-        out = outputs(kind, name, np.float64)
-        for v in out.values():
-            assert v.dtype == np.float64
-            v.setflags(write=False)
-        _CACHE[("want", kind, name)] = out
-    return _CACHE[("want", kind, name)]
-
-
-def errors_np(w, got):
-    return OrderedDict((q, float(np.abs(np.asarray(got[q], dtype=np.float64).reshape(v.shape) - v).max())) for q, v in w.items())
-
-
 def anchor(kind, name):
-    """want + the fp32 oracle run and its distance from want, computed once per session."""
-    if ("anchor", kind, name) not in _CACHE:
-        w = want(kind, name)
-        f32 = outputs(kind, name, np.float32)
-        assert all(v.dtype == np.float32 for v in f32.values()), {q: v.dtype for q, v in f32.items()}     # the fp32 run stays fp32
-        errs = errors_np(w, f32)
-        _CACHE[("anchor", kind, name)] = Anchor(w, f32, by_group(errs), errs)
-    return _CACHE[("anchor", kind, name)]
-
-
-def by_group(errs):
-    """{group: largest error of its outputs}"""
-    out = OrderedDict()
-    for q, e in errs.items():
-        out[group(q)] = max(out.get(group(q), 0.0), e)
-    return out
-
-
-def within(errs, ref_err):
-    """every output within the bound of its group's ref_err"""
-    return all(e <= bound(ref_err[group(q)]) for q, e in errs.items())
-
-
-def errors(w, got):
-    """{output: max |got - want|} for device tensors `got`."""
-    return errors_np(w, {q: got[q].detach().double().cpu().numpy() for q in w})
-
-
-def report(tag, errs, ref_err):
-    """The line every test prints before it asserts: per output the measured error and its ratio to ref_err."""
-    return (f"\n{tag}: max |out - float64| " + "  ".join(f"{q} {e:.3e} ({e / ref_err[group(q)]:.2f}x)" for q, e in errs.items())
-            + "  ref_err " + " ".join(f"{g} {r:.3e}" for g, r in ref_err.items()) + f", bound {F} x ref_err")
+    """want, the fp32 oracle run and its distance from want per group, computed once per session."""
+    return f64_bound.anchor(("tomp", kind, name), lambda dtype: outputs(kind, name, dtype), group)
 
 
 TABLES = (("predict", TC.PREDICT), ("bbreg", TC.BBREG), ("linear", TC.LINEAR))

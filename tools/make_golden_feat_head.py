@@ -22,7 +22,7 @@ from oracle import ref_harness  # noqa: E402
 ref_harness.install()
 
 import feat_head_cases as FC  # noqa: E402
-import fused_f64 as F64  # noqa: E402
+import f64_bound  # noqa: E402
 from pytracking_amd import synth  # noqa: E402
 
 OUT = os.environ.get("FEAT_HEAD_GOLDEN_OUT", os.path.join(ROOT, "tests", "golden"))
@@ -41,7 +41,7 @@ def reference_module(Cin, Cout, w, stride, basic=False):
 
 
 def main():
-    torch.set_num_threads(F64.THREADS)
+    torch.set_num_threads(f64_bound.THREADS)
     for k, (name, (n, Cin, Cout, H, W)) in enumerate(synth.FEAT_HEAD_CASES.items()):
         x, w = FC.problem(name)
         with torch.no_grad():

@@ -10,7 +10,7 @@
   rts_fusion_chain_deployed  the encoder at 16 x 27, then the fuse to 30 x 52, for both fusion types; to stay within the size of the other
                            files it stores the 'concat' state only: the encoder's is synth.label_enc_state(state_seed).
 Inputs are regenerated from the stored seeds by the tests.  `ref_fp32_err` (per fusion type: `ref_fp32_err.<type>`) is the largest
-difference between the fp32 run, with the 8 threads tests/fused_f64.py pins, and the SAME modules in float64; asserted <= 1e-5, a tenth of
+difference between the fp32 run, with the 8 threads tests/f64_bound.py pins, and the SAME modules in float64; asserted <= 1e-5, a tenth of
 the 1e-4 bound the GPU tests hold against these files."""
 import copy
 import os
@@ -28,7 +28,7 @@ from oracle import ref_harness  # noqa: E402
 ref_harness.install()
 
 from pytracking_amd import synth  # noqa: E402
-import fused_f64  # noqa: E402
+import f64_bound  # noqa: E402
 import rts_fusion_cases as RC  # noqa: E402
 
 OUT = os.environ.get("RTS_FUSION_GOLDEN_OUT", os.path.join(ROOT, "tests", "golden"))
@@ -67,7 +67,7 @@ def both(fn, nets, args):
         want = fn([copy.deepcopy(m).double() for m in nets], [a.double() for a in args])
         threads = torch.get_num_threads()
         try:
-            torch.set_num_threads(fused_f64.THREADS)
+            torch.set_num_threads(f64_bound.THREADS)
             got = fn(nets, args)
         finally:
             torch.set_num_threads(threads)

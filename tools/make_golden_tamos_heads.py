@@ -52,7 +52,7 @@ def main(names):
             print(f"{name}: reference |f32 - f64| max {np.abs(out['f32'].astype(np.float64) - out['f64']).max():.3e}, values up to "
                   f"{out['f64'].max():.3f}, {os.path.getsize(path)} bytes", flush=True)
         elif name == HC.FPN_DEPLOYED:
-            w = F64.want(name)
+            w = F64.anchor(name).want
             path = os.path.join(gdir, "tamos_heads_fpn_deployed.npz")
             np.savez_compressed(path, **{f"{q}_f64": v.reshape(-1)[::HC.DEPLOYED_KEEP[q]] for q, v in w.items()},
                                 **{f"{q}_stride": HC.DEPLOYED_KEEP[q] for q in w})
