@@ -904,6 +904,44 @@ int pt_iou_feat_f32(const float* feat3, const float* feat4, const float* pack, f
 int pt_mf_corr_tm_plan(int n, int Ftot, int C, int H, int W, int* out);
 
 /* ------------------------------------------------------------------------------------------------
+ * IoU modulation vectors -- AtomIoUNet.get_modulation (ltr/models/bbreg/atom_iou_net.py:138-170), iou_mod.hip.
+ *
+ *   c3 = conv3_1r(feat3) (n, A, H3, W3),  c4 = conv4_1r(feat4) (n, D, H4, W4)      Conv2d(3x3, pad 1, bias) -> BatchNorm2d (eval) -> ReLU
+ *   roi3 = PrRoIPool(3 x 3, s3)(c3, roi),  roi4 = PrRoIPool(1 x 1, s4)(c4, roi),   roi of image i = (i, x, y, x + w, y + h)
+ *   fc3  = fc3_1r(roi3) (n, B)             a 3x3 VALID convolution over the 3 x 3 pooled map, i.e. a linear map 9 A -> B
+ *   out3 (n, P3) = fc34_3r([fc3, roi4]),   out4 (n, P4) = fc34_4r([fc3, roi4])     1x1 convolutions over the concatenation (B + D)
+ *   every block ends in BatchNorm2d (eval) -> ReLU.  feat3 (n, Cin3, H3, W3), feat4 (n, Cin4, H4, W4), boxes (n, 4) xywh in image
+ *   coordinates ON THE DEVICE, all fp32 contiguous.  PrRoIPool as pt_prroi_fwd_f32: a bin of zero area or without a pixel gives 0, the
+ *   box may hang over any edge.
+ *
+ * The two 3x3 convolutions are computed only where the pooling reads them: per image and level the pixel window
+ *       columns max(0, floor(x * s)) ... min(W - 1, ceil((x + w) * s)),  rows likewise (fp32, x + w formed first),
+ *   read from `boxes` by the kernels.  pt_iou_mod_window (host only, launches nothing) returns that window as inclusive
+ *   (x0, y0, x1, y1): PT_OK, or 1 when it is empty (x1 < x0 or y1 < y0: the pooled values of that level are 0).  Taps outside the map
+ *   read 0, taps outside the window read the map; nothing beyond the window and one ring around it enters the result.
+ *   Windowed convolution on the fp32 MFMA with fp32 accumulation, the tail in plain fp32 FMA; no atomics, every sum in a fixed order:
+ *   repeated calls are bit-identical.  Four launches (windowed convolution of both levels, pooling, fc3, fc34), no host synchronisation, no device-to-host copy: capturable in a graph.
+ *
+ * `pack` (pt_iou_mod_pack_floats floats, 16-byte aligned), the five blocks in the order conv3_1r, conv4_1r, fc3_1r, fc34_3r, fc34_4r,
+ *   per block:  weight (Cout, KH, KW, Cin) tap-major = Conv2d.weight.permute(0, 2, 3, 1)   (3x3, 3x3, 3x3, 1x1, 1x1)
+ *               scale  (Cout) = bn.weight / sqrt(bn.running_var + bn.eps)
+ *               shift  (Cout) = (conv.bias - bn.running_mean) * scale + bn.bias
+ *   and a block computes relu(conv_without_bias(x) * scale + shift): BatchNorm is NOT folded into the weights.
+ *
+ * Covered: Cin3, Cin4 % 64 == 0; A, B, D, P3, P4 % 16 == 0 (each <= 4096); 1 <= n <= 32; H * W <= 4096 per level; pooled sizes
+ * exactly 3 x 3 (level 3) and 1 x 1 (level 4); s3, s4 > 0; operands 16-byte aligned.
+ * Status: NULL pointer PT_ERR_NULL, non-positive size or scale PT_ERR_SHAPE, uncovered shape / misaligned operand PT_ERR_UNSUPPORTED,
+ * workspace too small or not 256-byte aligned PT_ERR_WORKSPACE -- all before anything is queued.  pt_iou_mod_ws_bytes and
+ * pt_iou_mod_pack_floats return 0 for sizes that are not covered.
+ * ---------------------------------------------------------------------------------------------- */
+size_t pt_iou_mod_pack_floats(int Cin3, int A, int B, int Cin4, int D, int P3, int P4);
+size_t pt_iou_mod_ws_bytes(int n, int Cin3, int A, int B, int Cin4, int D, int P3, int P4, int H3, int W3, int H4, int W4);
+int pt_iou_mod_f32(const float* feat3, const float* feat4, const float* boxes, const float* pack, float* out3, float* out4, int n,
+                   int Cin3, int A, int B, int Cin4, int D, int P3, int P4, int H3, int W3, int H4, int W4, float s3, float s4, void* ws,
+                   size_t ws_bytes, void* stream);
+int pt_iou_mod_window(const float box_xywh[4], float scale, int H, int W, int out_x0y0x1y1[4]);
+
+/* ------------------------------------------------------------------------------------------------
  * Mask label encoder -- ResidualDS16SW.forward (ltr/models/lwl/label_encoder.py:9-55, ltr/models/rts/label_encoder.py:9-55),
  * label_enc.hip.  LWL and RTS run it on every stored mask on every frame (lwl.py:560-564, rts.py:688).
  *

@@ -9,8 +9,8 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PT_HOT_LIB", os.path.join(_HERE, "libpt_hot.so"))   # override: experiments only
-SOURCES = ["filter_kernels.hip", "fast_passes.hip", "sd_solver.hip", "mf_kernels.hip", "lwl_solver.hip", "atom_cg.hip", "atom_gn.hip", "tomp.hip", "localize.hip", "iou_refine.hip", "prroi.hip", "patch.hip", "frame_full.hip", "api.hip", "gn_hinge.hip", "tcm.hip", "kys.hip", "iou_feat.hip", "label_enc.hip", "box_enc.hip", "lwl_decoder.hip", "rts_fusion.hip", "seg_readout.hip", "eco.hip", "eco_init.hip"]
-HEADERS = ["common.h", "pt_internal.h", "rbuild.h", "sd_common.h", "mfma_gemm.h", "conv_tokens.h", "prroi_dev.h", "localize_dev.h", "frame_mid.h", "ds16_enc.h", "box_slice.h", os.path.join("..", "..", "include", "pt_hot.h")]
+SOURCES = ["filter_kernels.hip", "fast_passes.hip", "sd_solver.hip", "mf_kernels.hip", "lwl_solver.hip", "atom_cg.hip", "atom_gn.hip", "tomp.hip", "localize.hip", "iou_refine.hip", "prroi.hip", "patch.hip", "frame_full.hip", "api.hip", "gn_hinge.hip", "tcm.hip", "kys.hip", "iou_feat.hip", "label_enc.hip", "box_enc.hip", "lwl_decoder.hip", "rts_fusion.hip", "seg_readout.hip", "eco.hip", "eco_init.hip", "iou_mod.hip"]
+HEADERS = ["common.h", "pt_internal.h", "rbuild.h", "sd_common.h", "mfma_gemm.h", "conv_tokens.h", "prroi_dev.h", "localize_dev.h", "frame_mid.h", "ds16_enc.h", "box_slice.h", "iou_window.h", os.path.join("..", "..", "include", "pt_hot.h")]
 # kernarg preload: leading scalar kernel parameters arrive in SGPRs at wave launch (kernels that take them that way only)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-pass-failed", "-mllvm", "-amdgpu-kernarg-preload-count=14"]
 
@@ -145,6 +145,7 @@ EXPORTS = [
     "pt_sample_mask_patch_f32",
     "pt_eco_sample_f32", "pt_eco_shift_f32", "pt_eco_apply_filter_f32", "pt_eco_localize_ws_bytes", "pt_eco_localize_f32", "pt_eco_insert_f32",
     "pt_eco_filter_update_ws_bytes", "pt_eco_filter_update_f32", "pt_eco_joint_init_ws_bytes", "pt_eco_joint_init_f32",
+    "pt_iou_mod_pack_floats", "pt_iou_mod_ws_bytes", "pt_iou_mod_f32", "pt_iou_mod_window",
 ]
 
 PT_TCM_MAX_POINTS, PT_TCM_MAX_LAYERS = 64, 32       # include/pt_hot.h
@@ -558,6 +559,14 @@ def lib():
     L.pt_eco_joint_init_ws_bytes.argtypes = [ctypes.POINTER(EcoInitBlock), i]
     L.pt_eco_joint_init_f32.restype = i
     L.pt_eco_joint_init_f32.argtypes = [ctypes.POINTER(EcoInitBlock), i, i, i, f, vp, sz, vp]
+    L.pt_iou_mod_pack_floats.restype = sz
+    L.pt_iou_mod_pack_floats.argtypes = [i] * 7
+    L.pt_iou_mod_ws_bytes.restype = sz
+    L.pt_iou_mod_ws_bytes.argtypes = [i] * 12
+    L.pt_iou_mod_f32.restype = i
+    L.pt_iou_mod_f32.argtypes = [vp] * 6 + [i] * 12 + [f, f, vp, sz, vp]
+    L.pt_iou_mod_window.restype = i
+    L.pt_iou_mod_window.argtypes = [fp, f, i, i, ctypes.POINTER(ctypes.c_int)]
     L.pt_mf_corr_tm_plan.restype = i
     L.pt_mf_corr_tm_plan.argtypes = [i] * 5 + [ctypes.POINTER(ctypes.c_int)]
     L.pt_sample_patch_f32.restype = i

@@ -43,6 +43,8 @@ What gets rebound (import path = contract; nothing in the reference tree is edit
                                                   install(feature_heads=True))        -> pytracking_amd.features
   ltr.models.bbreg.atom_iou_net.AtomIoUNet.get_iou_feat  (both IoU feature towers; only with install(iou_feat=True))
                                                                                       -> pytracking_amd.iou_feat
+  ltr.models.bbreg.atom_iou_net.AtomIoUNet.get_modulation  (the first frame's IoU modulation vectors; only with install(iou_mod=True))
+                                                                                      -> pytracking_amd.iou_mod
   ltr.models.lwl.label_encoder.ResidualDS16SW.forward, ltr.models.rts.label_encoder.ResidualDS16SW.forward
                                                   (mask label encoder; only with install(label_encoder=True))
                                                                                       -> pytracking_amd.label_encoder
@@ -677,6 +679,21 @@ def _install_iou_feat():
                                              name + ": call outside the gfx950 hot path"))
 
 
+def _install_iou_mod():
+    """`AtomIoUNet.get_modulation` (atom_iou_net.py:138-170): conv3_1r / conv4_1r on the pixel window under each first-frame box, both
+    poolings, fc3_1r and the two fc34 blocks in one call.  CPU tensors, training mode, grad-enabled calls (the training `forward` calls
+    it under autograd), blocks or pooling objects of another structure, a `bb` that is not (n, 4) on the maps' device and uncovered
+    shapes keep the reference's code.  Off unless `install(iou_mod=True)`: the set a default install() rebinds is pinned."""
+    from . import iou_mod as _im
+    try:
+        cls = importlib.import_module("ltr.models.bbreg.atom_iou_net").AtomIoUNet
+    except Exception:
+        return
+    name = "AtomIoUNet.get_modulation"
+    _rebind(cls, "get_modulation", _dispatcher(cls.get_modulation, name, _im.covered, functools.partial(_im.get_modulation, checked=True),
+                                               name + ": call outside the gfx950 hot path"))
+
+
 def _install_label_encoder():
     """`ResidualDS16SW.forward` of LWL and of RTS (label_encoder.py:38-55, the same code in both packages): stem, two BasicBlocks and both
     heads in six launches.  CPU tensors, training mode, grad-enabled calls, modules of another structure and uncovered channel counts keep
@@ -977,7 +994,7 @@ def _install_atom_cg():
 
 def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=True, iou_refine=True, preprocessing=True,
             candidate_matching=True, kys=True, iou_feat=False, label_encoder=False, decoder=False, feature_heads=False,
-            rts_fusion=False, seg_readout=False, eco=False, tamos=False, box_encoder=False, eco_init=False):
+            rts_fusion=False, seg_readout=False, eco=False, tamos=False, box_encoder=False, eco_init=False, iou_mod=False):
     """Rebind the boundary symbols.  Call after the reference is importable (`sys.path`) and before networks or
     trackers are constructed.  Idempotent.  If an installer raises, what was rebound so far is undone before the exception
     propagates (an optional reference module that does not import is not a failure: its family is skipped)."""
@@ -1000,7 +1017,7 @@ def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=T
                                 (iou_feat, _install_iou_feat), (label_encoder, _install_label_encoder),
                                 (decoder, _install_lwl_decoder), (rts_fusion, _install_rts_fusion),
                                 (seg_readout, _install_seg_readout), (eco, _install_eco), (tamos, _install_tamos),
-                                (box_encoder, _install_box_encoder), (eco_init, _install_eco_init)):
+                                (box_encoder, _install_box_encoder), (eco_init, _install_eco_init), (iou_mod, _install_iou_mod)):
             if flag:
                 installer()
     except BaseException:

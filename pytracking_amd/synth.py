@@ -548,6 +548,87 @@ def iou_feat_inputs(seed, n, cin3, h3, w3, cin4, h4, w4):
     return f3, f4
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# IoU modulation vectors (ltr/models/bbreg/atom_iou_net.py:138-170): the five reference-branch blocks, the first-frame maps and boxes
+IOU_MOD_DEPLOYED = (128, 256, 256, 256, 256)
+IOU_MOD_CASES = {   # name: (n, (Cin3, H3, W3), (Cin4, H4, W4), (A, B, D, P3, P4)); the image is 8 H3 x 8 W3 (strides 8 and 16)
+    "one": (1, (64, 1, 1), (64, 1, 1), (16, 16, 16, 16, 16)),                  # every tap but the centre is padding
+    "edges": (6, (64, 9, 11), (64, 5, 6), (16, 32, 16, 32, 16)),               # the six box conditions of IOU_MOD_EDGE_BOXES
+    "tiles": (2, (64, 20, 19), (64, 10, 9), (16, 16, 16, 16, 16)),             # a 17-column window; bins wider than 6 pixels
+    "batch": (32, (64, 6, 6), (64, 3, 3), (16, 16, 16, 16, 16)),               # one map, 32 boxes: per-image window indexing
+    "chan": (3, (128, 7, 5), (192, 4, 3), (48, 32, 80, 16, 48)),               # unequal B and D: the concatenation order
+    "dimp50": (9, (512, 36, 36), (1024, 18, 18), IOU_MOD_DEPLOYED),
+    "prdimp50": (9, (512, 44, 44), (1024, 22, 22), IOU_MOD_DEPLOYED),
+    "atom18": (11, (128, 36, 36), (256, 18, 18), IOU_MOD_DEPLOYED),
+}
+IOU_MOD_EDGE_BOXES = ((8, 8, 40, 30),          # inside the map
+                      (-20, -5, 30, 50),       # over the top-left edge
+                      (200, 200, 10, 10),      # wholly outside: pooled values 0, the output is the tail's response to zero
+                      (10, 10, 0, 5),          # zero width
+                      (0, 0, 88, 72),          # the whole map: every tile live
+                      (17, 9, 1, 1))           # inside one pixel
+
+
+def iou_mod_state(seed, cin3, cin4, A=128, B=256, D=256, P3=256, P4=256):
+    """A state dict (numpy, float32) for conv3_1r, conv4_1r, fc3_1r, fc34_3r, fc34_4r of an AtomIoUNet: kaiming (fan-in) weights, non-zero
+    biases, and BatchNorm gains, shifts and running statistics away from their defaults, as iou_feat_state."""
+    rng = np.random.default_rng(seed)
+    sd = {}
+    for name, i, o, k in (("conv3_1r", cin3, A, 3), ("conv4_1r", cin4, D, 3), ("fc3_1r", A, B, 3), ("fc34_3r", B + D, P3, 1),
+                          ("fc34_4r", B + D, P4, 1)):
+        sd[name + ".0.weight"] = (rng.standard_normal((o, i, k, k), dtype=np.float32) * np.float32(np.sqrt(2.0 / (k * k * i)))).astype(np.float32)
+        sd[name + ".0.bias"] = (rng.standard_normal(o, dtype=np.float32) * np.float32(0.1)).astype(np.float32)
+        sd[name + ".1.weight"] = rng.uniform(0.5, 1.5, o).astype(np.float32)
+        sd[name + ".1.bias"] = (rng.standard_normal(o) * 0.1).astype(np.float32)
+        sd[name + ".1.running_mean"] = (rng.standard_normal(o) * 0.2).astype(np.float32)
+        sd[name + ".1.running_var"] = rng.uniform(0.5, 2.0, o).astype(np.float32)
+        sd[name + ".1.num_batches_tracked"] = np.array(100, dtype=np.int64)
+    return sd
+
+
+def iou_mod_boxes(name, seed=0):
+    """(n, 4) float32 xywh boxes of a case of IOU_MOD_CASES, every coordinate a multiple of 1/4 (x + w is then exact in fp32).  The
+    deployed cases carry the boxes of the first-frame augmentations that keep a box (dimp.py:469-490): the centred target, a fifth of
+    the search side; the four `relativeshift` copies at +-0.6 of its size; the horizontally flipped copy; blur (and, for ATOM, rotation)
+    copies, which keep the centred box."""
+    n, (_, h3, w3), _, _ = IOU_MOD_CASES[name]
+    Hi, Wi = 8 * h3, 8 * w3
+    if name == "one":
+        bb = [(2, 1, 5, 6)]
+    elif name == "edges":
+        bb = IOU_MOD_EDGE_BOXES
+    elif name == "tiles":
+        bb = [(10, 20, 120, 60),            # stride-8 columns 1 .. 17: straddles a 16-position tile; bins 5 pixels wide
+              (0, 0, Wi, Hi)]               # bins 6.33 x 6.67 pixels at stride 8, 9.5 x 10 at stride 16: the general loop
+    elif name in ("batch", "chan"):
+        rng = np.random.default_rng(seed)
+        xy = rng.uniform(-0.25, 0.8, (n, 2)) * (Wi, Hi)
+        wh = rng.uniform(0.05, 0.7, (n, 2)) * (Wi, Hi)
+        bb = np.round(np.concatenate([xy, wh], 1) * 4) / 4
+    else:
+        w, h = np.round(Wi / 5.0) + 0.5, np.round(Hi / 5.6) + 0.25
+        x, y = np.round((Wi - w) / 2 * 4) / 4 + 1.25, np.round((Hi - h) / 2 * 4) / 4 - 2.5
+        dx, dy = np.round(0.6 * w * 4) / 4, np.round(0.6 * h * 4) / 4
+        bb = [(x, y, w, h), (x + dx, y + dy, w, h), (x - dx, y + dy, w, h), (x + dx, y - dy, w, h), (x - dx, y - dy, w, h),
+              (Wi - x - w, y, w, h)] + [(x, y, w, h)] * (n - 6)
+    bb = np.asarray(bb, dtype=np.float32).reshape(n, 4)
+    assert np.array_equal(bb * 4, np.round(bb * 4))
+    return bb
+
+
+def iou_mod_inputs(seed, name):
+    """(layer2 (n, Cin3, H3, W3), layer3 (n, Cin4, H4, W4), bb (n, 4) xywh): non-negative maps, as the outputs of ResNet blocks are;
+    `batch` repeats one map in every image."""
+    n, (c3, h3, w3), (c4, h4, w4), _ = IOU_MOD_CASES[name]
+    rng = np.random.default_rng(seed)
+    m = 1 if name == "batch" else n
+    f3 = np.maximum(rng.standard_normal((m, c3, h3, w3), dtype=np.float32), 0.0).astype(np.float32)
+    f4 = np.maximum(rng.standard_normal((m, c4, h4, w4), dtype=np.float32), 0.0).astype(np.float32)
+    if m != n:
+        f3, f4 = np.repeat(f3, n, 0), np.repeat(f4, n, 0)
+    return f3, f4, iou_mod_boxes(name, seed + 7)
+
+
 LABEL_ENC_DIMS = (16, 32, 64, 16)       # layer_dims of the deployed label encoders (lwl_stage2.py:94-99, rts50.py:130-135)
 LABEL_ENC_CASES = {   # name: (n, H, W, layer_dims, use_bn)
     "one": (1, 7, 9, LABEL_ENC_DIMS, False),                 # every stage collapses to 1 x 1: all taps but the centre are padding
