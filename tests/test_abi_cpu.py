@@ -2,15 +2,21 @@
 header declares (no compute calls -- there is no GPU here), argument checking returns the documented
 status codes, and the host-side mirrors keep the reference's names and state_dict keys."""
 import ctypes
+import importlib.util
+import json
 import os
-import re
+import shutil
+import subprocess
 
 import pytest
 import torch
 
-from pytracking_amd import _lib
+from pytracking_amd import _abi, _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LLVM = os.path.join(os.path.dirname(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")), "..", "llvm", "bin")
+with open(os.path.join(ROOT, "include", "pt_hot.h")) as _fh:
+    HEADER_ABI = _abi.parse(_fh.read())                 # the test's own reading of the header, not _lib's
 
 
 @pytest.fixture(scope="module")
@@ -19,14 +25,177 @@ def L():
     return _lib.lib()
 
 
+def _defined_dynamic_symbols(path):
+    """`llvm-nm -D --defined-only`; a toolchain without llvm-nm has llvm-readelf, whose --dyn-syms table says the same (Ndx UND = undefined)."""
+    nm = os.path.join(LLVM, "llvm-nm")
+    if os.path.exists(nm):
+        out = subprocess.run([nm, "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+        return {ln.split()[-1] for ln in out.splitlines() if ln.split()}
+    out = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--dyn-syms", "-W", path], capture_output=True, text=True, check=True).stdout
+    rows = [ln.split() for ln in out.splitlines()]
+    return {r[7].split("@")[0] for r in rows if len(r) == 8 and r[0].rstrip(":").isdigit() and r[6] != "UND"}
+
+
 def test_header_symbols_exported(L):
-    hdr = open(os.path.join(ROOT, "include", "pt_hot.h")).read()
-    declared = set(re.findall(r"\b(pt_[a-z0-9_]+)\s*\(", hdr))
-    declared -= {"pt_status", "pt_sd_params", "pt_profile"}
-    assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
+    """The dynamic symbol table of the built library holds exactly the functions include/pt_hot.h declares."""
+    defined = {s for s in _defined_dynamic_symbols(_lib.LIB_PATH) if s.startswith("pt_")}
+    declared = set(HEADER_ABI.functions)
+    assert len(declared) >= 142 and defined == declared == set(_lib.EXPORTS), (defined ^ declared, declared ^ set(_lib.EXPORTS))
+    assert _lib.EXPORTS == list(HEADER_ABI.functions)                      # header order
     for name in declared:
         assert hasattr(L, name), name
     assert L.pt_abi_version() == 1
+
+
+def _load_dump_abi():
+    spec = importlib.util.spec_from_file_location("dump_abi", os.path.join(ROOT, "tools", "dump_abi.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_bindings_match_parent_snapshot(L):
+    """tests/golden/abi_parent.json is tools/dump_abi.py at the last commit whose bindings were typed by hand.  The bindings derived from the
+    header equal it -- every restype, argtype, struct size, field name, type and offset, constant and tuple -- but for three allowances:
+    a pointer-to-int / float / void* slot may have become c_void_p; the two functions the hand mirror left without a prototype have the
+    header's; constants of the header that the hand mirror omitted exist."""
+    with open(os.path.join(ROOT, "tests", "golden", "abi_parent.json")) as fh:
+        old = json.load(fh)
+    new = _load_dump_abi().dump()
+    diffs = []
+    gained = {"pt_abi_version": {"restype": "c_int", "argtypes": []},
+              "pt_corr_pass_plan": {"restype": "c_int", "argtypes": ["c_int"] * 8 + ["c_void_p"]}}
+    assert {k for k, v in old["functions"].items() if v["argtypes"] is None} == set(gained)
+    if set(new["functions"]) != set(old["functions"]):
+        diffs.append(("function set", sorted(set(new["functions"]) ^ set(old["functions"]))))
+    for name, o in old["functions"].items():
+        n = new["functions"].get(name)
+        if n is None:
+            continue
+        if name in gained:
+            if n != gained[name]:
+                diffs.append((name, gained[name], n))
+            continue
+        same = n["restype"] == o["restype"] and len(n["argtypes"]) == len(o["argtypes"]) and all(
+            a == b or (b in ("LP_c_int", "LP_c_float", "LP_c_void_p") and a == "c_void_p") for a, b in zip(n["argtypes"], o["argtypes"]))
+        if not same:
+            diffs.append((name, o, n))
+    if new["structs"] != old["structs"]:
+        diffs += [(k, old["structs"].get(k), new["structs"].get(k)) for k in sorted(set(old["structs"]) | set(new["structs"]))
+                  if old["structs"].get(k) != new["structs"].get(k)]
+    if new["tuples"] != old["tuples"]:
+        diffs.append(("tuples", old["tuples"], new["tuples"]))
+    for k in sorted(set(old["constants"]) | set(new["constants"])):
+        if k in old["constants"]:
+            if new["constants"].get(k) != old["constants"][k]:
+                diffs.append((k, old["constants"][k], new["constants"].get(k)))
+        elif HEADER_ABI.constants.get(k) != new["constants"][k]:            # new: a constant of the header (its value: the compiler test below)
+            diffs.append((k, None, new["constants"][k]))
+    assert not diffs, diffs
+
+
+def _layout_program(abi):
+    """C source that prints what the compiler makes of the header: every constant, every struct's size, every field's offset and size."""
+    out = ["#include <stdio.h>", "#include <stddef.h>", '#include "pt_hot.h"', "int main(void) {"]
+    out += [f'    printf("{k} %lld\\n", (long long){k});' for k in abi.constants]
+    for cname, cls in abi.structs.items():
+        out.append(f'    printf("{cname} %zu\\n", sizeof({cname}));')
+        out += [f'    printf("{cname}.{f} %zu %zu\\n", offsetof({cname}, {f}), sizeof((({cname}*)0)->{f}));' for f, _ in cls._fields_]
+    return "\n".join(out + ["    return 0;", "}"]) + "\n"
+
+
+def test_struct_layout_and_constants_match_the_compiler(tmp_path):
+    """The host C compiler is the ground truth of the header: sizeof / offsetof of all 15 structs and the value of every constant, printed by a
+    program generated from the parsed header, equal the ctypes classes and the attributes of _lib."""
+    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
+    if cc is None:
+        pytest.skip("no host C compiler")
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text(_layout_program(HEADER_ABI))
+    subprocess.run([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True, capture_output=True, text=True)
+    got = {ln.split()[0]: [int(v) for v in ln.split()[1:]] for ln in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines()}
+    want = {k: [getattr(_lib, k)] for k in HEADER_ABI.constants}
+    assert len(HEADER_ABI.structs) == 15
+    for cname in HEADER_ABI.structs:
+        cls = getattr(_lib, _abi.class_name(cname))
+        want[cname] = [ctypes.sizeof(cls)]
+        for f, t in cls._fields_:
+            want[f"{cname}.{f}"] = [getattr(cls, f).offset, ctypes.sizeof(t)]
+    assert got == want, {k: (got.get(k), want.get(k)) for k in set(got) | set(want) if got.get(k) != want.get(k)}
+
+
+@pytest.mark.parametrize("what, text, names", [
+    ("union", "typedef union pt_u {\n    int a;\n    float b;\n} pt_u;\nint pt_f(const pt_u* u);\n", "typedef union pt_u"),
+    ("union in a struct", "typedef struct pt_s {\n    union { int a; float b; } u;\n} pt_s;\n", "union { int a"),
+    ("bitfield", "typedef struct pt_s {\n    int a : 3;\n    int b;\n} pt_s;\n", "int a : 3"),
+    ("function-pointer parameter", "int pt_f(int n,\n         void (*done)(void*),\n         void* stream);\n", "pt_f"),
+    ("function-pointer field", "typedef struct pt_s {\n    int (*cb)(int);\n} pt_s;\n", "(*cb)"),
+    ("unknown type", "typedef struct pt_s {\n    int a;\n} pt_s;\nint pt_f(const pt_t* t,\n         int n);\n", "'pt_t'"),
+    ("unknown scalar", "int pt_f(int16_t n);\n", "'int16_t'"),
+    ("stray #if", "#if PT_WIDE\nint pt_f(long n);\n#else\nint pt_f(int n);\n#endif\n", "#if PT_WIDE"),
+    ("expression constant", "#define PT_X (1 << 3)\n", "#define PT_X"),
+    ("struct by value", "typedef struct pt_s { int a; } pt_s;\nint pt_f(pt_s s);\n", "'pt_s' by value"),
+    ("global variable", "extern int pt_count;\n", "extern int pt_count"),
+    ("unterminated", "int pt_f(int n)\n", "int pt_f(int n)"),
+    ("repeated prototype", "int pt_f(int n);\nint pt_f(long n);\n", "'pt_f' declared twice"),
+])
+def test_reader_refuses(what, text, names):
+    """Whatever the reader would have to guess at raises, and the message quotes the offending text."""
+    with pytest.raises(_abi.AbiError) as exc:
+        _abi.parse(text)
+    assert names in str(exc.value), (what, str(exc.value))
+
+
+def test_reader_accepts_what_the_header_uses():
+    abi = _abi.parse("""
+/* a comment with a prototype in it: int pt_not_this(int x); */
+#ifndef PT_T_H
+#define PT_T_H
+#include <stddef.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define PT_N 6   /* trailing comment */
+typedef enum pt_st { PT_A = 0, PT_B = -2, PT_C } pt_st;
+enum { PT_D = 5, PT_E };
+enum pt_route { PT_R_X = 1000, PT_R_Y, PT_R_END, };
+typedef struct pt_in { int a, b; } pt_in;
+typedef struct {
+    const pt_in* in;                  // a pointer to an earlier struct
+    float *p, *q;
+    const float *r, s;
+    double m[PT_N];
+    float u[2], v;
+    unsigned flags;
+    unsigned char byte;
+    long stride; long long big;
+    size_t bytes;
+    void* stream;
+} pt_out_rec;
+const char* pt_name(int status);
+int pt_version(void);
+void pt_forget(const void* p);
+size_t pt_bytes(const pt_in* in, int n);
+int pt_run(const pt_out_rec* o, const float* const* rows, long long* idx, const float box_xywh[4], int* count, float th, double d,
+           long stride, size_t bytes, unsigned mask, void* const* streams);
+#ifdef __cplusplus
+}
+#endif
+#endif /* PT_T_H */
+""")
+    c = ctypes
+    assert abi.constants == {"PT_N": 6, "PT_A": 0, "PT_B": -2, "PT_C": -1, "PT_D": 5, "PT_E": 6, "PT_R_X": 1000, "PT_R_Y": 1001, "PT_R_END": 1002}
+    assert list(abi.structs) == ["pt_in", "pt_out_rec"] and [s.__name__ for s in abi.structs.values()] == ["In", "OutRec"]
+    In, Out = abi.structs.values()
+    assert In._fields_ == [("a", c.c_int), ("b", c.c_int)]
+    assert Out._fields_ == [("in", c.POINTER(In)), ("p", c.c_void_p), ("q", c.c_void_p), ("r", c.c_void_p), ("s", c.c_float), ("m", c.c_double * 6),
+                            ("u", c.c_float * 2), ("v", c.c_float), ("flags", c.c_uint), ("byte", c.c_ubyte), ("stride", c.c_long),
+                            ("big", c.c_longlong), ("bytes", c.c_size_t), ("stream", c.c_void_p)]
+    vp = c.c_void_p
+    assert abi.functions == {"pt_name": (c.c_char_p, [c.c_int]), "pt_version": (c.c_int, []), "pt_forget": (None, [vp]),
+                             "pt_bytes": (c.c_size_t, [c.POINTER(In), c.c_int]),
+                             "pt_run": (c.c_int, [c.POINTER(Out), vp, vp, vp, vp, c.c_float, c.c_double, c.c_long, c.c_size_t, c.c_uint, vp])}
+    assert list(abi.functions) == ["pt_name", "pt_version", "pt_forget", "pt_bytes", "pt_run"]
 
 
 def test_argument_checks_do_not_launch(L):
