@@ -829,29 +829,40 @@ int pt_tcm_match_f32(const pt_tcm_match_params* p, const float* weights, const f
  *
  * pt_kys_predict_response_f32: ResponsePredictor.forward (ltr/models/kys/response_predictor.py:65-159) in eval mode, with the
  *   shift_features calls PredictorWrapper.predict_response puts around it (predictor_wrapper.py:113-148): four launches, no host
- *   synchronisation.  state_dim 8, representation_predictor_dims (64, 32), gru_ksz 3, prev_max_pool_ksz 1 only; with_conf: 1 for
- *   conf_measure 'max', 0 for 'none'.  H*W <= PT_KYS_PRED_MAX_HW.
+ *   synchronisation.  prev_max_pool_ksz 1, H*W <= PT_KYS_PRED_MAX_HW.  with_conf is the conf_measure code PT_KYS_CONF_NONE /
+ *   PT_KYS_CONF_MAX (largest propagation weight) / PT_KYS_CONF_ENTROPY (-sum_q w log(w + 1e-4) over all H*W previous positions,
+ *   response_predictor.py:114-116).  rep_dim1 == 0 means one representation layer of rep_dim0 channels.  Covered structures, a
+ *   closed list (anything else: pt_kys_weight_floats returns 0 and the call PT_ERR_UNSUPPORTED):
+ *       state_dim 8, gru_ksz 3, representation_predictor_dims (64, 32), conf none / max     (the constructor defaults, kysnet.py:122-123)
+ *       state_dim 8, gru_ksz 3, representation_predictor_dims (16,): rep_dim0 16, rep_dim1 0, conf none / max / entropy
+ *                                                  (entropy: the trained network, ltr/train_settings/kys/kys.py:110-114)
+ *   (64, 32) with entropy is refused only because tests/test_gpu_kys.py pins that refusal; the kernels would not mind.
  *   Inputs: cost_volume (B, H*W, H, W); state_prev (B, 8, H, W) or NULL, then label_prev (B, H, W) (shifted by -shift_px and fed
  *   to init_hidden_state_predictor); dimp_score (B, H, W) unshifted; window NULL or (H, W) (window_stride 0) / (B, H, W)
  *   (window_stride H*W).  shift_px: the pixel offset of the reference's +-0.5 / size translation (0.25 at the defaults of
  *   affine_grid / grid_sample: bilinear, zero padding, align_corners False); inputs are sampled at -shift_px, outputs at +shift_px.
  *   Outputs: response (B, H, W) shifted back; state_cur (B, 8, H, W); propagation_weights (B, H*W, H, W) (= cost_volume_processed);
- *   propagated_h (B, 8, H, W); propagation_conf (B, H, W) (with_conf only, else may be NULL); fused_score_orig (B, H, W) (before
+ *   propagated_h (B, 8, H, W); propagation_conf (B, H, W) (with_conf != 0 only, else may be NULL); fused_score_orig (B, H, W) (before
  *   threshold, window and shift); is_target, is_target_after_prop, is_target_new (B, H, W) shifted back.
  *
  *   Weight pack (float32, conv weights (out, in, 3, 3) row-major, eval BatchNorm folded as for pt_tcm_match_f32), in this order:
  *     cost_volume_proc1  W 8x1, b 8 (BN folded, ReLU), W 1x8, b 1 (BN folded);  cost_volume_proc2 the same
  *     init_hidden_state_predictor  W 8x1 (no bias, tanh)
  *     is_target_predictor  W 4x8, b 4 (ReLU), W 1x4, b 1
- *     representation_predictor  W 64x(9 + with_conf), b 64, W 32x64, b 32 (ReLU);  response_predictor  W 1x32, b 1 (sigmoid)
+ *     representation_predictor  W 64x(9 + conf), b 64, W 32x64, b 32 (ReLU);  response_predictor  W 1x32, b 1 (sigmoid)
+ *       one layer (rep_dim1 == 0):  W 16x(9 + conf), b 16 (ReLU);  response_predictor  W 1x16, b 1 (sigmoid)
+ *       (conf = 1 where with_conf != 0; 27900 / 27324 floats for (64, 32), 4924 / 4780 for (16,))
  *     state_predictor (ConvGRU, input = [score, response, max score, max response, state])  reset W 8x12, b 8; update; state_new
  * ---------------------------------------------------------------------------------------------- */
 #define PT_KYS_CV_MAX_HW 1024
 #define PT_KYS_PRED_MAX_HW 400
+#define PT_KYS_CONF_NONE 0
+#define PT_KYS_CONF_MAX 1
+#define PT_KYS_CONF_ENTROPY 2
 typedef struct pt_kys_predict_params {
     int B, H, W;
     int state_dim, rep_dim0, rep_dim1, gru_ksz;
-    int with_conf;           /* conf_measure 'max': 1, 'none': 0 */
+    int with_conf;           /* conf_measure code: PT_KYS_CONF_NONE / _MAX / _ENTROPY */
     int has_thresh;          /* dimp_thresh is not None */
     float dimp_thresh;
     float shift_px;

@@ -8,14 +8,19 @@
 //                                 groups of PredictorWrapper.predict_response
 //       k_kys_prep                shifted label -> initial state (or state_prev), shifted score, is_target(state_prev)
 //       k_kys_cvproc              one workgroup per previous position q: proc1, softmax over p, proc2 (BatchNorm folded)
-//       k_kys_propagate           softmax over q, propagation weights, confidence, propagated state
-//       k_kys_head                is_target x2, 10 -> 64 -> 32 -> 1 predictor, threshold / window, max-pool concat, ConvGRU, shifts back
+//       k_kys_propagate           softmax over q, propagation weights, confidence (largest weight, or entropy over all q), propagated state
+//       k_kys_head                is_target x2, 10 -> 64 -> 32 -> 1 or 10 -> 16 -> 1 predictor, threshold / window, max-pool concat, ConvGRU,
+//                                 shifts back
+// Covered structures (a closed list, kys_structure_ok): state_dim 8, gru_ksz 3 and
+//     representation dims (64, 32)          conf_measure none / max       two wide maps through global scratch
+//     representation dims (16,)  (r1 == 0)  conf_measure none / max / entropy   the 16-channel map stays in LDS; the shipped network
 #include "common.h"
 #include "pt_internal.h"
 
 namespace {
 
-constexpr int KYS_SD = 8, KYS_R0 = 64, KYS_R1 = 32, KYS_GI = 4, KYS_IT = 4;   // deployed dims the kernels are written for
+constexpr int KYS_SD = 8, KYS_R0 = 64, KYS_R1 = 32, KYS_GI = 4, KYS_IT = 4;   // dims the kernels are written for
+constexpr int KYS_R16 = 16;                                                   // the one-layer representation stack (rep_dim1 == 0)
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // cost volume
@@ -155,7 +160,8 @@ struct KysW {      // offsets (floats) into the weight pack; layout in include/p
     int r0_w, r0_b, r1_w, r1_b, resp_w, resp_b, gr_w, gr_b, gu_w, gu_b, gn_w, gn_b, total;
 };
 
-KysW kys_offsets(int with_conf) {
+// r1 == 0: one representation layer of r0 channels, response_predictor reads it
+KysW kys_offsets(int with_conf, int r0 = KYS_R0, int r1 = KYS_R1) {
     KysW o{};
     int at = 0;
     auto take = [&](int n) { const int r = at; at += n; return r; };
@@ -164,8 +170,8 @@ KysW kys_offsets(int with_conf) {
     o.init_w = take(KYS_SD * 9);
     o.it1_w = take(KYS_IT * KYS_SD * 9); o.it1_b = take(KYS_IT); o.it2_w = take(KYS_IT * 9); o.it2_b = take(1);
     const int ci = KYS_SD + 1 + (with_conf ? 1 : 0);
-    o.r0_w = take(KYS_R0 * ci * 9); o.r0_b = take(KYS_R0); o.r1_w = take(KYS_R1 * KYS_R0 * 9); o.r1_b = take(KYS_R1);
-    o.resp_w = take(KYS_R1 * 9); o.resp_b = take(1);
+    o.r0_w = take(r0 * ci * 9); o.r0_b = take(r0); o.r1_w = take(r1 * r0 * 9); o.r1_b = take(r1);
+    o.resp_w = take((r1 ? r1 : r0) * 9); o.resp_b = take(1);
     const int gi = KYS_GI + KYS_SD;
     o.gr_w = take(KYS_SD * gi * 9); o.gr_b = take(KYS_SD); o.gu_w = take(KYS_SD * gi * 9); o.gu_b = take(KYS_SD);
     o.gn_w = take(KYS_SD * gi * 9); o.gn_b = take(KYS_SD);
@@ -237,7 +243,10 @@ __global__ __launch_bounds__(256) void k_kys_cvproc(const float* __restrict__ cv
     kys_conv3(t8, 8, z + mapi * HW, 1, wts + o.p2b_w, wts + o.p2b_b, H, W, ACT_NONE);
 }
 
-// workgroup (p tile of 16, b): 16 q groups x 16 positions.  Softmax over q for every p, then w[q, p], conf[p] = max_q w, h'[d, p] = sum_q w h[d, q]
+// workgroup (p tile of 16, b): 16 q groups x 16 positions.  Softmax over q for every p, then w[q, p], conf[p] = max_q w, h'[d, p] = sum_q w h[d, q].
+// ENT: conf[p] = -sum_q w[q, p] log(w[q, p] + 1e-4) over ALL previous positions (response_predictor.py:114-116), from the stored w, one
+// partial per q group, added in a fixed order through `red`.  logf, not a fast intrinsic: w log(w + 1e-4) at w = 1 is the whole result.
+template <bool ENT>
 __global__ __launch_bounds__(256) void k_kys_propagate(const float* __restrict__ z, const float* __restrict__ hbuf, float* __restrict__ wout,
                                                        float* __restrict__ conf, float* __restrict__ hprop, int HW) {
     __shared__ float red[16][17];
@@ -264,17 +273,23 @@ __global__ __launch_bounds__(256) void k_kys_propagate(const float* __restrict__
     float hs[KYS_SD];
 #pragma unroll
     for (int d = 0; d < KYS_SD; ++d) hs[d] = 0.f;
+    float ent = 0.f;
     if (ok) {
         float* wb = wout + (long)b * HW * HW;
         for (int q = qg; q < HW; q += 16) {
             const float wv = expf(zb[(long)q * HW + p] - mx) / sm;
             wb[(long)q * HW + p] = wv;
+            if (ENT) ent += wv * logf(wv + 1e-4f);
 #pragma unroll
             for (int d = 0; d < KYS_SD; ++d) hs[d] = fmaf(wv, hb[d * HW + q], hs[d]);
         }
     }
 #pragma unroll
     for (int d = 0; d < KYS_SD; ++d) hred[d][qg][pl] = hs[d];
+    if (ENT) {
+        __syncthreads();                                                   // `red` is still being read for the softmax sum
+        red[qg][pl] = ent;
+    }
     __syncthreads();
     if (ok && qg < KYS_SD) {
         float t = 0.f;
@@ -282,7 +297,16 @@ __global__ __launch_bounds__(256) void k_kys_propagate(const float* __restrict__
         for (int g = 0; g < 16; ++g) t += hred[qg][g][pl];
         hprop[((long)b * KYS_SD + qg) * HW + p] = t;
     }
-    if (ok && qg == KYS_SD && conf) conf[(long)b * HW + p] = 1.f / sm;     // the largest softmax term is exp(0) / sum
+    if (ENT) {
+        if (ok && qg == KYS_SD) {
+            float t = 0.f;
+#pragma unroll
+            for (int g = 0; g < 16; ++g) t += red[g][pl];
+            conf[(long)b * HW + p] = -t;
+        }
+    } else {
+        if (ok && qg == KYS_SD && conf) conf[(long)b * HW + p] = 1.f / sm;     // the largest softmax term is exp(0) / sum
+    }
 }
 
 struct KysHead {
@@ -293,6 +317,9 @@ struct KysHead {
     int H, W, with_conf, has_thresh; long window_stride; float thresh, shift;
 };
 
+// ONE: the one-layer representation stack.  Its 16-channel map lives in LDS over Y | R (20 HW contiguous floats, dead between the
+// is_target pass and the assembly of the GRU input; 16 HW <= 20 HW), response_predictor reads it there; no global round trip.
+template <bool ONE>
 __global__ __launch_bounds__(1024) void k_kys_head(KysHead a) {
     __shared__ float lds[39 * PT_KYS_PRED_MAX_HW];
     __shared__ float red[16];
@@ -309,14 +336,22 @@ __global__ __launch_bounds__(1024) void k_kys_head(KysHead a) {
     __syncthreads();
     kys_is_target(X, t4, it, wts, a.o, H, W);
     kys_store_shifted(it, a.it_after_prop + (long)b * HW, H, W, a.shift);
-    float* r0 = a.r0buf + (long)b * KYS_R0 * HW;
-    float* r1 = a.r1buf + (long)b * KYS_R1 * HW;
-    kys_conv3(X, ci, r0, KYS_R0, wts + a.o.r0_w, wts + a.o.r0_b, H, W, ACT_RELU);
-    __syncthreads();
-    kys_conv3(r0, KYS_R0, r1, KYS_R1, wts + a.o.r1_w, wts + a.o.r1_b, H, W, ACT_RELU);
-    __syncthreads();
-    kys_conv3(r1, KYS_R1, f, 1, wts + a.o.resp_w, wts + a.o.resp_b, H, W, ACT_SIGMOID);
-    __syncthreads();
+    if (ONE) {
+        static_assert(KYS_R16 <= 12 + KYS_SD, "the one-layer map must fit Y | R");
+        kys_conv3(X, ci, Y, KYS_R16, wts + a.o.r0_w, wts + a.o.r0_b, H, W, ACT_RELU);
+        __syncthreads();
+        kys_conv3(Y, KYS_R16, f, 1, wts + a.o.resp_w, wts + a.o.resp_b, H, W, ACT_SIGMOID);
+        __syncthreads();
+    } else {
+        float* r0 = a.r0buf + (long)b * KYS_R0 * HW;
+        float* r1 = a.r1buf + (long)b * KYS_R1 * HW;
+        kys_conv3(X, ci, r0, KYS_R0, wts + a.o.r0_w, wts + a.o.r0_b, H, W, ACT_RELU);
+        __syncthreads();
+        kys_conv3(r0, KYS_R0, r1, KYS_R1, wts + a.o.r1_w, wts + a.o.r1_b, H, W, ACT_RELU);
+        __syncthreads();
+        kys_conv3(r1, KYS_R1, f, 1, wts + a.o.resp_w, wts + a.o.resp_b, H, W, ACT_SIGMOID);
+        __syncthreads();
+    }
     const float* sc = X + KYS_SD * HW;
     float m0 = -INFINITY, m1 = -INFINITY;
     for (int p = tid; p < HW; p += nt) {
@@ -358,7 +393,13 @@ CvPlan cv_plan(int C) {
     return {kchunk, (C + kchunk - 1) / kchunk};
 }
 
-bool kys_dims_ok(int state_dim, int r0, int r1, int gru_ksz) { return state_dim == KYS_SD && r0 == KYS_R0 && r1 == KYS_R1 && gru_ksz == 3; }
+// The closed list of covered structures (include/pt_hot.h).  (64, 32) with entropy stays refused: tests/test_gpu_kys.py pins that.
+bool kys_structure_ok(int state_dim, int r0, int r1, int gru_ksz, int conf) {
+    if (state_dim != KYS_SD || gru_ksz != 3) return false;
+    if (r0 == KYS_R0 && r1 == KYS_R1) return conf == PT_KYS_CONF_NONE || conf == PT_KYS_CONF_MAX;
+    if (r0 == KYS_R16 && r1 == 0) return conf == PT_KYS_CONF_NONE || conf == PT_KYS_CONF_MAX || conf == PT_KYS_CONF_ENTROPY;
+    return false;
+}
 
 }  // namespace
 
@@ -391,8 +432,8 @@ extern "C" int pt_kys_cost_volume_f32(const float* feat_cur, const float* feat_p
 }
 
 extern "C" size_t pt_kys_weight_floats(int state_dim, int rep_dim0, int rep_dim1, int gru_ksz, int with_conf) {
-    if (!kys_dims_ok(state_dim, rep_dim0, rep_dim1, gru_ksz)) return 0;
-    return (size_t)kys_offsets(with_conf).total;
+    if (!kys_structure_ok(state_dim, rep_dim0, rep_dim1, gru_ksz, with_conf)) return 0;
+    return (size_t)kys_offsets(with_conf, rep_dim0, rep_dim1).total;
 }
 
 extern "C" size_t pt_kys_predict_ws_bytes(int B, int H, int W) {
@@ -412,13 +453,14 @@ extern "C" int pt_kys_predict_response_f32(const pt_kys_predict_params* p, const
     if (!state_prev && !label_prev) return PT_ERR_NULL;
     if (p->with_conf && !propagation_conf) return PT_ERR_NULL;
     if (p->B <= 0 || p->H <= 0 || p->W <= 0) return PT_ERR_SHAPE;
-    if (!kys_dims_ok(p->state_dim, p->rep_dim0, p->rep_dim1, p->gru_ksz)) return PT_ERR_UNSUPPORTED;
+    if (!kys_structure_ok(p->state_dim, p->rep_dim0, p->rep_dim1, p->gru_ksz, p->with_conf)) return PT_ERR_UNSUPPORTED;
     if ((long)p->H * p->W > PT_KYS_PRED_MAX_HW || p->B > 1024) return PT_ERR_UNSUPPORTED;
     if (p->weight_floats < pt_kys_weight_floats(p->state_dim, p->rep_dim0, p->rep_dim1, p->gru_ksz, p->with_conf)) return PT_ERR_SHAPE;
     const int B = p->B, H = p->H, W = p->W, HW = H * W;
     if (window && p->window_stride != 0 && p->window_stride != HW) return PT_ERR_SHAPE;
     if (ws_bytes < pt_kys_predict_ws_bytes(B, H, W)) return PT_ERR_WORKSPACE;
-    const KysW o = kys_offsets(p->with_conf);
+    const KysW o = kys_offsets(p->with_conf, p->rep_dim0, p->rep_dim1);
+    const bool one = p->rep_dim1 == 0, ent = p->with_conf == PT_KYS_CONF_ENTROPY;
     float* z = (float*)ws;
     float* hbuf = z + (size_t)B * HW * HW;
     float* sbuf = hbuf + (size_t)B * KYS_SD * HW;
@@ -430,12 +472,12 @@ extern "C" int pt_kys_predict_response_f32(const pt_kys_predict_params* p, const
     PT_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_kys_cvproc, dim3(HW, B), dim3(256), 0, st, cost_volume, weights, o, z, H, W);
     PT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_kys_propagate, dim3((HW + 15) / 16, B), dim3(256), 0, st, (const float*)z, (const float*)hbuf, propagation_weights,
-                       p->with_conf ? propagation_conf : nullptr, propagated_h, HW);
+    hipLaunchKernelGGL(ent ? k_kys_propagate<true> : k_kys_propagate<false>, dim3((HW + 15) / 16, B), dim3(256), 0, st, (const float*)z,
+                       (const float*)hbuf, propagation_weights, p->with_conf ? propagation_conf : nullptr, propagated_h, HW);
     PT_CHECK_LAUNCH();
     KysHead ha{weights, o, propagated_h, propagation_conf, sbuf, window, r0, r1, response, state_cur, fused_score_orig, is_target_after_prop,
                is_target_new, H, W, p->with_conf ? 1 : 0, p->has_thresh ? 1 : 0, p->window_stride, p->dimp_thresh, p->shift_px};
-    hipLaunchKernelGGL(k_kys_head, dim3(B), dim3(1024), 0, st, ha);
+    hipLaunchKernelGGL(one ? k_kys_head<true> : k_kys_head<false>, dim3(B), dim3(1024), 0, st, ha);
     PT_CHECK_LAUNCH();
     return PT_OK;
 }

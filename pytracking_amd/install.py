@@ -645,7 +645,9 @@ def provide_correlation_sampler():
 
 def _install_kys():
     """KYS (kys.py:314): `PredictorWrapper.predict_response` and `CostVolume.forward`.  CPU tensors, grad-enabled calls, training mode, a
-    list of reference frames, conf_measure 'entropy', other channel counts and maps above 20 x 20 keep the reference's code."""
+    list of reference frames, a structure off the covered list of include/pt_hot.h (covered: representation_predictor_dims (16,) with
+    conf_measure 'entropy' / 'max' / 'none' -- the trained network -- and (64, 32) with 'max' / 'none') and maps above 20 x 20 keep the
+    reference's code."""
     from . import kys as _kys
     provide_correlation_sampler()
     try:

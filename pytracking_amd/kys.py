@@ -3,6 +3,8 @@
   SpatialCorrelationSampler(3, 2 md + 1, 1, 1)    the class ltr/models/kys/cost_volume.py:5 imports         -> pt_kys_cost_volume_f32
   CostVolume(kernel_size, max_displacement, ...)  ltr.models.kys.cost_volume.CostVolume (remap fused)        -> pt_kys_cost_volume_f32
   predict_response(wrapper, data, ...)            PredictorWrapper.predict_response (eval, one reference)    -> pt_kys_predict_response_f32
+                                                  representation_predictor_dims (16,) with conf_measure 'entropy' / 'max' / 'none' (the network
+                                                  ltr/train_settings/kys/kys.py:110-114 trains) or (64, 32) with 'max' / 'none'
 
 `spatial_correlation_sampler` is a CUDA extension without a ROCm build: importing ltr.models.kys fails on this platform until install()
 registers this module under that name.  Its semantics are written here from the extension's documented behaviour (kernel_size 3,
@@ -137,17 +139,29 @@ def shift_px():
     return _SHIFT_PX[0]
 
 
+COVERED = ("state_dim 8, gru_ksz 3, representation_predictor_dims (64, 32) with conf_measure 'max' / 'none' or (16,) with "
+           "'max' / 'none' / 'entropy'")
+
+
+def _conf_codes():
+    return {"none": _lib.PT_KYS_CONF_NONE, "max": _lib.PT_KYS_CONF_MAX, "entropy": _lib.PT_KYS_CONF_ENTROPY}
+
+
 def _dims(pred):
-    """(state_dim, rep_dim0, rep_dim1, gru_ksz, conf_in) of a ResponsePredictor, or None if its structure is not the deployed one."""
+    """(state_dim, rep_dim0, rep_dim1 or 0, gru_ksz, conf code) of a ResponsePredictor whose structure is on the covered list of
+    include/pt_hot.h, else None.  A one-layer representation stack has rep_dim1 0."""
     try:
         convs = [blk[0] for blk in pred.representation_predictor]
         gru = pred.state_predictor
-        if len(convs) != 2 or not all(isinstance(c, torch.nn.Conv2d) for c in convs + [gru.conv_reset, gru.conv_update, gru.conv_state_new]):
+        if len(convs) not in (1, 2) or not all(isinstance(c, torch.nn.Conv2d) for c in convs + [gru.conv_reset, gru.conv_update, gru.conv_state_new]):
             return None
-        if pred.conf_measure not in ("max", "none") or pred.prev_max_pool_ksz != 1:
+        code = _conf_codes().get(pred.conf_measure)
+        if code is None or pred.prev_max_pool_ksz != 1:
             return None
-        return (int(gru.hidden_dim), convs[0].out_channels, convs[1].out_channels, int(gru.conv_reset.kernel_size[0]),
-                int(pred.conf_measure != "none"))
+        d = (int(gru.hidden_dim), convs[0].out_channels, convs[1].out_channels if len(convs) == 2 else 0, int(gru.conv_reset.kernel_size[0]), code)
+        if d[:4] == (8, 64, 32, 3):
+            return d if code != _lib.PT_KYS_CONF_ENTROPY else None
+        return d if d[:4] == (8, 16, 0, 3) else None
     except (AttributeError, TypeError, IndexError):
         return None
 
@@ -162,19 +176,20 @@ def pack_weights(pred):
     d = _dims(pred)
     n = _lib.lib().pt_kys_weight_floats(*d) if d is not None else 0
     if n == 0:
-        raise NotImplementedError("ResponsePredictor: state_dim 8, representation_predictor_dims (64, 32), gru_ksz 3 only")
+        raise NotImplementedError("ResponsePredictor: " + COVERED + " only")
     parts = []
     for stack in (pred.cost_volume_proc1, pred.cost_volume_proc2):
         parts += _fold(stack[0][0], stack[0][1]) + _fold(stack[1][0], stack[1][1])
     parts += _fold(pred.init_hidden_state_predictor[0][0])
     parts += _fold(pred.is_target_predictor[0][0]) + _fold(pred.is_target_predictor[1][0])
-    parts += _fold(pred.representation_predictor[0][0]) + _fold(pred.representation_predictor[1][0])
+    for blk in pred.representation_predictor:
+        parts += _fold(blk[0])
     parts += _fold(pred.response_predictor[0][0])
     g = pred.state_predictor
     parts += _fold(g.conv_reset) + _fold(g.conv_update) + _fold(g.conv_state_new)
     pack = torch.cat([p.reshape(-1) for p in parts]).float().contiguous()
     if pack.numel() != n:
-        raise NotImplementedError("ResponsePredictor: layer shapes differ from the deployed structure")
+        raise NotImplementedError("ResponsePredictor: layer shapes differ from the covered structures")
     return pack
 
 
@@ -230,11 +245,12 @@ def covered_predict_response(wrapper, data, dimp_thresh=None, output_window=None
 @device_guarded
 def predict_response(wrapper, data, dimp_thresh=None, output_window=None, checked=False):
     """reference: PredictorWrapper.predict_response (predictor_wrapper.py:88-153) -> the reference's dict: response (the shape of
-    dimp_score_cur), state_cur (B, 8, H, W), cost_volume (B, H*W, H, W), auxiliary_outputs with every key the reference fills."""
+    dimp_score_cur), state_cur (B, 8, H, W), cost_volume (B, H*W, H, W), auxiliary_outputs with exactly the keys the reference fills
+    ('propagation_conf' for conf_measure 'max' and 'entropy')."""
     _packs.require_device(data.get("feat1"), data.get("feat2"), data.get("dimp_score_cur"))
     if not checked and not covered_predict_response(wrapper, data, dimp_thresh, output_window):
-        raise NotImplementedError("predict_response: eval mode, one reference frame, device fp32, conf_measure 'max' / 'none', state_dim 8, "
-                                  f"representation dims (64, 32), H*W <= {_lib.PT_KYS_PRED_MAX_HW}, no grad")
+        raise NotImplementedError(f"predict_response: eval mode, one reference frame, device fp32, {COVERED}, "
+                                  f"H*W <= {_lib.PT_KYS_PRED_MAX_HW}, no grad")
     pred = wrapper.predictor
     score = data["dimp_score_cur"]
     score_shape = score.shape
