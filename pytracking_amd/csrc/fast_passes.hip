@@ -34,8 +34,13 @@
 #define PT_ADJ_UMAX_WIDE (192 / PT_ADJ_WAVES)
 #endif
 // experiment knobs (profiles/r03f_*): feature loads requested ahead of the MFMAs / register cap of k_corr2
-#ifndef PT_C2_CD
-#define PT_C2_CD 2       // round 3 sweep (profiles/r03l_*): 2 / 3 / 4 / 6 / 8 ahead -> 8.72 / 8.97 / 8.99 / 9.49 / 9.76 us
+// k_corr2: feature k-steps in flight in the MFMA loop (and requested in front of barrier 1); NK and above = the whole slice.
+// (The sweeps of the former knob PT_C2_CD -- round 3, profiles/r03l_*: 2 / 3 / 4 / 6 / 8 ahead -> 8.72 / 8.97 / 8.99 / 9.49 / 9.76 us,
+// under the 80-VGPR cap; round 6 likewise -- measured a loop whose waits the compiler had made inexact: whatever the depth, the
+// prologue requests were drained and the waves with the leftover quads ran one k-step ahead.  They say nothing about an exact schedule;
+// its sweep is in profiles/r10a_corr2_feature_stream.txt.)
+#ifndef PT_C2_D
+#define PT_C2_D 4
 #endif
 #ifndef PT_C2_MINW
 #define PT_C2_MINW 6
@@ -207,7 +212,7 @@ __device__ __forceinline__ float corr2_filter_elem(const Corr2Args& a, int KK, i
         v += a.reg * a.w[ge];
         if (ok) {
             gsq += v * v;
-            if (publish) a.g_out[ge] = v;
+            if (publish) pt_global(a.g_out)[ge] = v;
         }
     } else {
         v = a.filt[ge];
@@ -269,7 +274,7 @@ __global__ __launch_bounds__(1024, (NK <= 8 && NH == 2 ? PT_C2_MINW : 4)) void k
     const int cx0 = hCX * x;
     const int nsl = hCX * 16;
     float* __restrict__ afilt = lds;
-    float* __restrict__ Tl = lds + nsl + (long)(ws * NH + (MIX ? 0 : h)) * KK * hHWp;
+    float* __restrict__ Tl = lds + nsl + (long)__builtin_amdgcn_readfirstlane((ws * NH + (MIX ? 0 : h)) * KK * hHWp);   // wave-uniform: no vector register across the loop
     const bool over = h_src != nullptr && i == h_slot;
     const float* __restrict__ fi = over ? h_src : h_feat + (long)i * h_stride;
     const bool publish = FUSE != 0 && i0 == 0;                      // uniform per workgroup
@@ -291,9 +296,12 @@ __global__ __launch_bounds__(1024, (NK <= 8 && NH == 2 ? PT_C2_MINW : 4)) void k
             // partial k in the scalar offset of the buffer load: no 64-bit address arithmetic per load on the VALU
             const unsigned ckk_b = (unsigned)hC * 16u * 4u;
             const __amdgpu_buffer_rsrc_t rg = pt_rsrc(h_filt, (unsigned)h_KSPL * ckk_b);
+            // the last partial's index, stated to be wave-uniform: folded with the `k < h_KSPL` of the reduction into one vector
+            // subtract-with-borrow, the scalar offsets below became vector values and every load a readfirstlane loop
+            const int klast = __builtin_amdgcn_readfirstlane(h_KSPL - 1);
 #pragma unroll
             for (int k = 0; k < FP; ++k)
-                part4[k] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rg, (unsigned)g4 * 8u, (unsigned)min(k, h_KSPL - 1) * ckk_b, 0));
+                part4[k] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rg, (unsigned)g4 * 8u, (unsigned)min(k, klast) * ckk_b, 0));
             wv4 = ((const f32x2*)h_w)[g4];
         } else if (FUSE < 0) {
             part4[0] = ((const f32x2*)h_filt)[g4];                  // w_{T-1}
@@ -324,9 +332,12 @@ __global__ __launch_bounds__(1024, (NK <= 8 && NH == 2 ? PT_C2_MINW : 4)) void k
     }
 
     // ---- feature slice of this wave: NK float4 (+ NK scalars for the trailing quads).  A wave stalls at a load it
-    //      cannot issue (the CU accepts ~45 B/clk), so only the first CD k-steps are requested before the filter is
-    //      staged; the rest are issued CD k-steps ahead of the MFMAs that consume them.
-    constexpr int CD = NK < PT_C2_CD ? NK : PT_C2_CD;    // 6 or 8 ahead: register spills under the 80-VGPR cap, 10.3 vs 10.15 us
+    //      cannot issue (the CU accepts ~45 B/clk), so the first D k-steps are requested behind the filter reduction,
+    //      directly in front of barrier 1; the rest are issued D k-steps ahead of the MFMAs that consume them (mfma_phase).
+    // (the k-half arms of up to 8 k-steps live under the 80-VGPR cap of their launch bounds: more than 2 k-steps in flight spill there,
+    // and a spill is a scratch store in front of the loop that the first wait then has to drain)
+    constexpr int DW = (NK <= 8 && NH == 2 && PT_C2_D > 2) ? 2 : PT_C2_D;   // 2: what those arms ran with before; not a knob
+    constexpr int D = NK < DW ? NK : DW;
     const int cbase = cx0 + 4 * ((MIX ? 0 : h) * NK) + kq;
     const int pos = 64 * t + 4 * j + (half ? 2 * h : 0);
     const bool pv = pos < HW;
@@ -335,28 +346,9 @@ __global__ __launch_bounds__(1024, (NK <= 8 && NH == 2 ? PT_C2_MINW : 4)) void k
     const int lpos = 64 * h_TF + j;
     const bool lv = lt && j < 4 * h_rem;
     const unsigned lo = lv ? ((unsigned)cbase * HW + lpos) * 4u : 0xFFFFFFF0u - 64u * (unsigned)HW * 4u;   // no position: reads 0
-    f32x4 bq[NK];
-    float bl[NK];
-    auto ldf = [&](int k) {                                         // a half wave: its two positions in bq[k][0], bq[k][1]
-        if (MIX && half) {
-            const f32x2 v = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(fr, fo + (unsigned)(4 * k) * HW * 4u, 0, 0));
-            bq[k] = (f32x4){v[0], v[1], 0.f, 0.f};
-        } else {
-            bq[k] = pt_bload4(fr, fo + (unsigned)(4 * k) * HW * 4u);
-        }
-    };
-    auto ldq = [&](int k) {
-        ldf(k);
-        if (lt) bl[k] = pt_bload1(fr, lo + (unsigned)(4 * k) * HW * 4u);
-    };
-    // the leftover-quad scalars first: the filter reduction below then waits for vmcnt(CD) on every wave -- the 16-byte loads stay
-    // in flight behind it -- instead of a count that fits the waves without the leftover tile
-    if (lt) {
-#pragma unroll
-        for (int k = 0; k < CD; ++k) bl[k] = pt_bload1(fr, lo + (unsigned)(4 * k) * HW * 4u);
-    }
-#pragma unroll
-    for (int k = 0; k < CD; ++k) ldf(k);
+    // No feature load is requested up here.  (Up to round 9 the first two k-steps were, "in flight behind the reduction" -- but the
+    // requests sat under wave-uniform branches (leftover quads, position halves), the compiler's load counter has to cover the static
+    // path that skips them all, and the reduction drained them with `s_waitcnt vmcnt(0)`: profiles/r10a_corr2_feature_stream.txt.)
     __builtin_amdgcn_sched_barrier(0);                              // nothing that needs the argument block above this line
     const Corr2Args a = pt_late_args<Corr2Args>(56);                // 5 pointers / longs + 3 dwords = 52 bytes, 8-aligned
     PT_STAMP(a, 1);
@@ -373,14 +365,14 @@ __global__ __launch_bounds__(1024, (NK <= 8 && NH == 2 ? PT_C2_MINW : 4)) void k
             v4 += a.reg * wv4;
             if ((int)threadIdx.x < n4) {
                 gsq = v4[0] * v4[0] + v4[1] * v4[1];
-                if (publish) ((f32x2*)a.g_out)[((long)cx0 * 16 >> 1) + e4] = v4;
+                if (publish) pt_global((f32x2*)a.g_out)[((long)cx0 * 16 >> 1) + e4] = v4;
             }
         } else if (FUSE < 0) {
             float qt = 0.f;
             for (int k = lane + 64; k < h_n; k += 64) qt += (h_w + h_aux)[64 + k];   // memories of more than 64 samples
             const float astep = sd_final_astep(lz_q, qt, lz_an, a.step, a.reg);
             v4 = (f32x2){sd_final_apply(part4[0][0], wv4[0], astep), sd_final_apply(part4[0][1], wv4[1], astep)};
-            if ((int)threadIdx.x < n4 && publish) ((f32x2*)a.g_out)[((long)cx0 * 16 >> 1) + e4] = v4;
+            if ((int)threadIdx.x < n4 && publish) pt_global((f32x2*)a.g_out)[((long)cx0 * 16 >> 1) + e4] = v4;
         } else {
             v4 = part4[0];
         }
@@ -399,7 +391,7 @@ __global__ __launch_bounds__(1024, (NK <= 8 && NH == 2 ? PT_C2_MINW : 4)) void k
                 v += a.reg * wv[q];
                 if (okv[q]) {
                     gsq += v * v;
-                    if (publish) a.g_out[gev[q]] = v;
+                    if (publish) pt_global(a.g_out)[gev[q]] = v;
                 }
             } else {
                 v = part[q][0];
@@ -411,49 +403,85 @@ __global__ __launch_bounds__(1024, (NK <= 8 && NH == 2 ? PT_C2_MINW : 4)) void k
     }
     if (FUSE > 0 && publish) {                                      // uniform per workgroup
         const float tot = block_sum(gsq, scratch, nthreads);
-        if (threadIdx.x == 0) a.anum_part[x] = tot;
+        if (threadIdx.x == 0) pt_global(a.anum_part)[x] = tot;
     }
-    PT_STAMP(a, 2);
-    __syncthreads();
-    PT_STAMP(a, 3);
-
-    // HALF (MIX, tile 0): two positions per lane (bq[k][0], bq[k][1]) instead of four
-    auto mfma_phase = [&](auto half_c) {
-        constexpr bool HALF = decltype(half_c)::value;
+    // ---- barrier 1 and the MFMA loop: ONE straight-line body per wave kind, selected once (wave-uniform).  The kinds are
+    //      (HALF, LT): full tile / full tile + leftover quads / MIX: half 0 of tile 0 + leftover quads / MIX: half 1 of tile 0.
+    //      With the leftover load and the fifth MFMA under branches inside every k-step the compiler kept ONE load count for the waves
+    //      that take them and those that do not (vmcnt(2): two k-steps in flight for the plain waves, one for the busiest), and a
+    //      drained pipeline (vmcnt(0)) at k-step 2 (profiles/r10a_corr2_feature_stream.txt).  Here every body requests the k-steps
+    //      0 .. D-1 directly in front of barrier 1 -- they travel during the barrier wait and the LDS reads of the filter operand --
+    //      and k-step k + D at the head of k-step k, pinned there by a scheduling barrier as in k_adj2: the wait in front of
+    //      k-step k is exact and leaves the D k-steps behind it in flight.  The barrier is the LDS-only one: the filter operand is
+    //      handed over through LDS, and a full fence would drain the requests.
+    //      Same accumulator per element, k-steps in order: same bits.
+    auto mfma_phase = [&](auto half_c, auto left_c) {
+        constexpr bool HALF = decltype(half_c)::value;              // HALF (MIX, tile 0): two positions per lane (bq[k][0], bq[k][1]) instead of four
+        constexpr bool LT = decltype(left_c)::value;                // this wave also carries the leftover quads
+        f32x4 bq[HALF ? 1 : NK];
+        f32x2 bh[HALF ? NK : 1];
+        float bl[LT ? NK : 1];
+        auto issue = [&](int k) {
+            // the k-step in the SCALAR offset of the load: one address register per wave instead of one per k-step in flight (the
+            // NH == 2 arms live under an 80-VGPR cap).  A lane without a position is out of range by its vector offset alone.
+            const unsigned ko = (unsigned)(4 * k) * HW * 4u;
+            if constexpr (HALF) bh[k] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(fr, fo, ko, 0));
+            else bq[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(fr, fo, ko, 0));
+            if constexpr (LT) bl[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(fr, lo, ko, 0));
+        };
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            issue(k);
+            __builtin_amdgcn_sched_barrier(0);                      // in k-step order, as the waits of the loop count them
+        }
+        PT_STAMP(a, 2);
+        pt_lds_barrier();                                           // filter operand staged; the feature requests stay in flight
+        PT_STAMP(a, 3);
         f32x4 acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0}, acc2 = {0, 0, 0, 0}, acc3 = {0, 0, 0, 0}, accL = {0, 0, 0, 0};
         // the wave's NK filter-operand values in one batch of LDS reads in front of the loop (round 6: inside the loop every k-step was
-        // read -> wait -> 4 MFMAs, the uniform leftover-tile branches keep the compiler from hoisting the next read over them)
+        // read -> wait -> 4 MFMAs)
         float avv[NK];
 #pragma unroll
         for (int k = 0; k < NK; ++k) avv[k] = afilt[(4 * ((MIX ? 0 : h) * NK + k) + kq) * 16 + j];
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
-            if (k + CD < NK) ldq(k + CD);
+            if (k + D < NK) {
+                __builtin_amdgcn_sched_barrier(0);                  // the request stays at the head of its k-step
+                issue(k + D);
+                __builtin_amdgcn_sched_barrier(0);
+            }
             const float av = avv[k];
-            acc0 = mfma16(av, bq[k][0], acc0);
-            acc1 = mfma16(av, bq[k][1], acc1);
-            if constexpr (!HALF) {
+            if constexpr (HALF) {
+                acc0 = mfma16(av, bh[k][0], acc0);
+                acc1 = mfma16(av, bh[k][1], acc1);
+            } else {
+                acc0 = mfma16(av, bq[k][0], acc0);
+                acc1 = mfma16(av, bq[k][1], acc1);
                 acc2 = mfma16(av, bq[k][2], acc2);
                 acc3 = mfma16(av, bq[k][3], acc3);
             }
-            if (lt) accL = mfma16(av, bl[k], accL);
+            if constexpr (LT) accL = mfma16(av, bl[k], accL);
         }
         PT_STAMP(a, 4);
         // ---- memory insert rides on the pass (pytracking/tracker/dimp/dimp.py:429-441)
+        //      (global stores, pt_global: the bodies follow one another in the code, and a FLAT store left pending by one body makes
+        //      the compiler drain every counter at the first wait of the next)
         if (over && a.copy_dst) {
-            const pt_gf dp = a.copy_dst + pos + (long)cbase * HW;
+            const pt_gptr<float> dp = pt_global(a.copy_dst) + (fo >> 2);   // pv: fo = byte offset of (cbase, pos) -- no second copy of it across the loop
             if (pv) {
 #pragma unroll
                 for (int k = 0; k < NK; ++k) {
-                    if constexpr (HALF) *(f32x2*)(dp + (long)(4 * k) * HW) = (f32x2){bq[k][0], bq[k][1]};
-                    else *(f32x4*)(dp + (long)(4 * k) * HW) = bq[k];
+                    if constexpr (HALF) *(pt_gptr<f32x2>)(dp + (long)(4 * k) * HW) = bh[k];
+                    else *(pt_gptr<f32x4>)(dp + (long)(4 * k) * HW) = bq[k];
                 }
             }
-            if (lv) {
-                const pt_gf dl = a.copy_dst + lpos + (long)cbase * HW;
+            if constexpr (LT) {
+                if (lv) {
+                    const pt_gptr<float> dl = pt_global(a.copy_dst) + (lo >> 2);   // lv: likewise
 #pragma unroll
-                for (int k = 0; k < NK; ++k) dl[(long)(4 * k) * HW] = bl[k];
+                    for (int k = 0; k < NK; ++k) dl[(long)(4 * k) * HW] = bl[k];
+                }
             }
         }
 
@@ -467,15 +495,21 @@ __global__ __launch_bounds__(1024, (NK <= 8 && NH == 2 ? PT_C2_MINW : 4)) void k
                     f32x4 v = {acc0[r], acc1[r], acc2[r], acc3[r]};
                     *(f32x4*)(Tl + row * hHWp + pos) = v;             // columns >= HW land in the padding
                 }
-                if (lt) Tl[row * hHWp + lpos] = accL[r];              // j >= 4*rem: padding as well (lpos < HWp)
+                if constexpr (LT) Tl[row * hHWp + lpos] = accL[r];    // j >= 4*rem: padding as well (lpos < HWp)
             }
         }
     };
-    if constexpr (MIX) {
-        if (half) mfma_phase(std::true_type{});                     // uniform per wave
-        else mfma_phase(std::false_type{});
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    if constexpr (MIX) {                                            // uniform per wave; a full-tile wave of a mixed pair has t >= 1
+        if (half && lt) mfma_phase(yes, std::integral_constant<bool, LEFT>{});
+        else if (half) mfma_phase(yes, no);
+        else mfma_phase(no, no);
+    } else if constexpr (LEFT) {
+        if (lt) mfma_phase(no, yes);
+        else mfma_phase(no, no);
     } else {
-        mfma_phase(std::false_type{});
+        mfma_phase(no, no);
     }
     PT_STAMP(a, 5);
     __syncthreads();
