@@ -209,6 +209,13 @@ int pt_atom_cg_f32(float* x, const float* samples, long samples_stride_n, const 
                    int n, int C, int H, int W, int K, int num_iter, int fletcher_reeves,
                    float direction_forget_factor, float* cg_state,
                    void* ws, size_t ws_bytes, void* stream);
+/* Route pt_atom_cg_f32 takes for exactly these operands -- the update's own shape checks and route predicate, evaluated on the host,
+ * nothing launched or allocated.  Fused route (C = 64, 4x4 filter, 4 or 5 position tiles, aligned operands):
+ *   out = {1, position tiles, tail (0 none, 1 leftover quads on tile 0's wave, 2 a partial tile of its own), leftover quads, adjoint slices};
+ * generic route: out = {0, 16-byte feature loads (0 | 1), k-step arm of the correlation kernel (16 | 8 | 4, 0 = run-time count),
+ * channel slices, adjoint slices}.  Returns 0 or the status the update returns for the shape; `out` (5 ints) is zeroed then. */
+int pt_atom_cg_route(const float* x, const float* samples, long samples_stride_n, const float* cg_state,
+                     int n, int C, int H, int W, int K, int* out);
 
 /* ATOM first-frame joint optimisation -- GaussNewtonCG.run (pytracking/libs/optimization.py:328-421) on
  * FactorizedConvProblem (pytracking/tracker/atom/optim.py:6-68), identity projection activation, MLU response activation:
@@ -221,6 +228,15 @@ int pt_atom_gn_f32(float* filter, float* proj, const float* samples, long sample
                    const float* sample_weights, float filter_reg, float projection_reg, float act_min_val,
                    int n, int M, int Kc, int H, int W, int K, const int* cg_iters, int num_gn, int fletcher_reeves,
                    void* ws, size_t ws_bytes, void* stream);
+/* Routes of pt_atom_gn_f32 for exactly these samples -- the entry's own checks and dispatch helpers, evaluated on the host, nothing
+ * launched or allocated (the other operands are the caller's 16-byte aligned arrays and the 256-byte aligned workspace).  out (10 ints):
+ *   [0] conv1x1 arm (0 weights read in place, 1 banks of 16 rows in one launch, 2 one launch per group of <= 16 rows),
+ *   [1] projection-adjoint arm (0 batched GEMM, 1 banked multi-filter adjoint, 2 one launch per group),
+ *   [2] groups of 16 projection rows, [3] sample groups of the projection-adjoint partials, [4] 1 = the CG step's two correlations
+ *   share one launch, [5] grid.z of the filter adjoint (1 + input-gradient layers), [6] 16-byte loads of the compressed maps,
+ *   [7] k-step arm of the correlation kernel (16 | 8 | 4, 0 = run-time count), [8] channel slices, [9] adjoint slices.
+ * Returns 0 or the status the entry returns for the shape; `out` is zeroed then. */
+int pt_atom_gn_route(const float* samples, long samples_stride_n, int n, int M, int Kc, int H, int W, int K, int* out);
 
 /* ------------------------------------------------------------------------------------------------
  * ToMP transformer model predictor -- replaces, for inference,

@@ -697,6 +697,59 @@ def gen_atom_cg_c64():
     save("atom_cg_c64", **out)
 
 
+def gen_atom_routes():
+    """The ATOM solvers off the 4x4 / 12x12 shapes of the goldens above (tests/atom_cases.py pins each to its kernel route):
+      atom_cg_c64_fused   gen_atom_cg_c64's four variants and (3, 2, 3) schedule at 16x16 -- the smallest map of the fused CG route
+      atom_cg_k1 / k2 / k3   conv2d(mode='same') with a 1-, 2- and 3-tap filter side (operation.py:17-32), C = 24 / 32 / 40, state carried
+      atom_gn_k3, atom_gn_kc24   the joint Gauss-Newton with a 3x3 filter and with a ragged last group of projection rows."""
+    from pytracking import TensorList
+    from pytracking.libs import optimization
+    from pytracking.tracker.atom.optim import ConvProblem, FactorizedConvProblem
+    from ltr.models.layers import activation
+    acfg = synth.ATOM18
+
+    def cg(x0, samples, y, sw, fr, forget, schedule):
+        prob = ConvProblem(TensorList([T(samples)]), TensorList([T(y)[:, None]]), TensorList([acfg["filter_reg"]]),
+                           TensorList([T(sw)]), activation.MLU(acfg["act_min_val"]))
+        x = TensorList([T(x0.copy())[None].clone()])
+        opt = optimization.ConjugateGradient(prob, x, fletcher_reeves=fr, direction_forget_factor=forget)
+        outs = []
+        for iters in schedule:
+            opt.run(iters)
+            outs.append(x[0].detach()[0].numpy().copy())
+        return np.stack(outs)
+
+    small = dict(C=64, H=16, W=16)
+    out = dict(seed=322, n=12, H=16, W=16, iters=np.array([3, 2, 3]))
+    for tag, fr, forget in (("pr", False, 0.75), ("fr", True, 0.5), ("pr0", False, 0.0), ("fr0", True, 0.0)):
+        x0, samples, y, sw1 = synth.atom_problem(322, 12, acfg, small=small)
+        out[f"{tag}_x_out"] = cg(x0, samples, y, sw1, fr, forget, (3, 2, 3))
+        out[f"{tag}_fr"] = int(fr)
+        out[f"{tag}_forget"] = forget
+    save("atom_cg_c64_fused", **out)
+
+    for K, C, H, W, n, fr, forget, seed in ((1, 24, 7, 9, 3, False, 0.75, 331), (2, 32, 10, 10, 4, True, 0.75, 332),
+                                            (3, 40, 9, 11, 2, False, 0.0, 333)):
+        x0, samples, y, sw1 = synth.atom_problem(seed, n, acfg, small=dict(C=C, H=H, W=W, K=K))
+        save(f"atom_cg_k{K}", x0=x0, samples=samples, y=y, sw=sw1, x_out=cg(x0, samples, y, sw1, fr, forget, (3, 2, 3)),
+             iters=np.array([3, 2, 3]), fletcher_reeves=int(fr), forget=forget)
+
+    for tag, seed, n, M, Kc, H, W, K, cg_iters, fr in (("k3", 341, 3, 16, 8, 9, 11, 3, [3, 2], False),
+                                                        ("kc24", 342, 4, 16, 24, 10, 10, 4, [3, 3], True)):
+        rng = np.random.default_rng(seed)
+        samples = (rng.standard_normal((n, M, H, W), dtype=np.float32) * np.float32(0.1))
+        _, _, y, sw = synth.atom_problem(seed, n, acfg, small=dict(C=Kc, H=H, W=W))
+        f0 = rng.standard_normal((Kc, K, K), dtype=np.float32) * np.float32(0.05)
+        P0 = rng.standard_normal((Kc, M), dtype=np.float32) * np.float32(1.0 / np.sqrt(M))
+        prob = FactorizedConvProblem(TensorList([T(samples)]), TensorList([T(y)[:, None]]), TensorList([acfg["filter_reg"]]),
+                                     TensorList([1e-4]), None, TensorList([T(sw)]), lambda x: x, activation.MLU(acfg["act_min_val"]))
+        var = TensorList([T(f0.copy())[None].clone()]).concat(TensorList([T(P0.copy())[:, :, None, None].clone()]))
+        optimization.GaussNewtonCG(prob, var, fletcher_reeves=fr).run(list(cg_iters))
+        save(f"atom_gn_{tag}", samples=samples, y=y, sw=sw, f0=f0, P0=P0, f_out=var[0].detach()[0].numpy(),
+             P_out=var[1].detach()[:, :, 0, 0].numpy(), cg_iters=np.array(cg_iters), fletcher_reeves=int(fr),
+             filter_reg=acfg["filter_reg"], projection_reg=1e-4, act_min_val=acfg["act_min_val"])
+
+
 def gen_patches():
     """`sample_patch` / `sample_patch_multiscale` of the unmodified reference (preprocessing.py:33-148) on synthetic images:
     every border mode, pre-downsampling factors 1..3, crops hanging over each border, up- and down-sampling."""
@@ -808,7 +861,7 @@ def gen_trackers():
 if __name__ == "__main__":
     torch.set_num_threads(8)
     which = sys.argv[1:] or ["filter", "dimp", "l2", "prdimp", "atom", "prroi", "lwl", "atomgn", "tomp", "head", "localize", "iou",
-                             "branches", "ioufull", "atomgnfull", "lwlfull", "trackers", "patches", "long", "augment", "atomc64"]
+                             "branches", "ioufull", "atomgnfull", "lwlfull", "trackers", "patches", "long", "augment", "atomc64", "atomroutes"]
     if "tomp" in which:
         gen_tomp()
     if "head" in which:
@@ -851,3 +904,5 @@ if __name__ == "__main__":
         gen_augment()
     if "atomc64" in which:
         gen_atom_cg_c64()
+    if "atomroutes" in which:
+        gen_atom_routes()

@@ -328,14 +328,15 @@ def conv_same_input_grad(v, filt, H, W):
 
 
 def atom_gn_cg(filter0, P0, samples, y, sample_weights, *, filter_reg, projection_reg, act_min_val, cg_iters,
-               fletcher_reeves=True):
+               fletcher_reeves=True, defect=None, trace=None):
     """`GaussNewtonCG.run` (optimization.py:328-407) on `FactorizedConvProblem` (atom/optim.py:6-68), identity
     projection activation, MLU response activation, explicit Jacobian instead of double autograd.
 
     filter0 (Kc,K,K); P0 (Kc,M) [= (Kc,M,1,1)]; samples (n,M,H,W); y (n,H,W); cg_iters: list, one entry per GN iteration.
     Residuals [sqrt(sw)*(MLU(conv_same(conv1x1(S,P), f)) - y), sqrt(lf)*f, sqrt(lP)*P]  (optim.py:19-45);
     joint inner product over both blocks (:48-65); preconditioner M1 = diag(1/lf, 1/lP) (:67-68, :17).
-    Returns (filter, P)."""
+    defect: one of ATOM_GN_DEFECTS (seeded-defect tests); trace: as in atom_cg.  Returns (filter, P)."""
+    assert defect is None or defect in ATOM_GN_DEFECTS, defect
     dt = samples.dtype
     n, M, H, W = samples.shape
     K = filter0.shape[-1]
@@ -353,11 +354,11 @@ def atom_gn_cg(filter0, P0, samples, y, sample_weights, *, filter_reg, projectio
             v = d * ud
             gf = apply_feat_transpose(c, v, K) + sqf * uf
             gc = conv_same_input_grad(v, f, H, W)
-            gP = np.einsum("nkhw,nmhw->km", gc, samples, optimize=True) + sqP * uP
+            gP = np.einsum("nkhw,nmhw->km", gc, samples, optimize=True) + (0 if defect == "no_proj_reg" else sqP * uP)
             return gf, gP
 
         def J(pf, pP):
-            dc = conv1x1(samples, pP)
+            dc = conv1x1(samples, P if defect == "dc_from_P" else pP)
             return d * (apply_filter(c, pf, out_hw=(H, W)) + apply_filter(dc, f, out_hw=(H, W))), sqf * pf, sqP * pP
 
         ip = lambda a, b: (a[0] * b[0]).sum() + (a[1] * b[1]).sum()
@@ -368,15 +369,21 @@ def atom_gn_cg(filter0, P0, samples, y, sample_weights, *, filter_reg, projectio
             z = (r[0] / lf, r[1] / lP)                                   # M1, M2 = identity
             rho1, rho = rho, ip(r, z)
             if rho == 0:
+                if trace is not None:
+                    trace.append(dict(rho=0.0))
                 break
+            beta = None
             if p is None:
                 p = z
             else:
                 beta = rho / rho1 if fletcher_reeves else (rho - ip(r_prev, z)) / rho1
-                beta = max(beta, dt.type(0))
-                p = (z[0] + p[0] * beta, z[1] + p[1] * beta)
+                bc = max(beta, dt.type(0))
+                p = (z[0] + p[0] * bc, z[1] + p[1] * bc)
             q = JT(*J(*p))
-            alpha = rho / ip(p, q)
+            pq = ip(p, q)
+            alpha = rho / pq
+            if trace is not None:
+                trace.append(dict(beta=None if beta is None else float(beta), rho=float(rho), pq=float(pq)))
             if not fletcher_reeves:
                 r_prev = r
             delta = (p[0] * alpha, p[1] * alpha) if delta is None else (delta[0] + p[0] * alpha, delta[1] + p[1] * alpha)
@@ -448,45 +455,55 @@ def mlu_deriv(x, min_val):
     return np.where(x >= 0, 1.0, np.exp(np.minimum(x, 0) / min_val)).astype(x.dtype)
 
 
-def atom_conv_residuals(x, samples, y, sample_weights, filter_reg, act_min_val):
+def atom_conv_residuals(x, samples, y, sample_weights, filter_reg, act_min_val, defect=None):
     """`ConvProblem.__call__` (atom/optim.py:79-94): returns (data residuals (n,H,W), reg residual)."""
     H, W = samples.shape[-2:]
     s = apply_filter(samples, x, out_hw=(H, W))                          # conv2d mode='same'
-    r = np.sqrt(sample_weights).reshape(-1, 1, 1) * (mlu(s, act_min_val) - y)
+    ssw = sample_weights if defect == "sw_not_sqrt" else np.sqrt(sample_weights)
+    r = ssw.reshape(-1, 1, 1) * (mlu(s, act_min_val) - y)
     return s, r, math.sqrt(filter_reg) * x
 
 
+# Seeded defects of the two ATOM restatements (tests/test_atom_routes_cpu.py: each must miss the float64 bound).  None: the restatement.
+ATOM_CG_DEFECTS = ("forget_rho", "pr_for_fr", "stale_r_prev", "sw_not_sqrt", "no_lambda_p")
+ATOM_GN_DEFECTS = ("no_proj_reg", "dc_from_P")
+
+
 def atom_cg(x0, samples, y, sample_weights, *, filter_reg, act_min_val, num_iter,
-            fletcher_reeves=False, state=None, direction_forget_factor=0.0):
+            fletcher_reeves=False, state=None, direction_forget_factor=0.0, defect=None, trace=None):
     """`ConjugateGradient.run` + `ConjugateGradientBase.run_CG` for `ConvProblem`
     (optimization.py:72-163, 227-289; atom/optim.py:71-99), explicit J / J^T instead of autograd.
 
     x0 (C,K,K); samples (n,C,H,W); y (n,H,W); sample_weights (n,).
     state: dict(p, rho, r_prev) carried across calls (only used when direction_forget_factor != 0).
+    defect: one of ATOM_CG_DEFECTS, a deliberately wrong variant for the seeded-defect tests.  trace: a list that receives one
+    dict(beta (before the clamp; None for a first direction), rho, pq) per iteration, dict(rho=0) for a stop.
     Returns (x_new, state).
     """
+    assert defect is None or defect in ATOM_CG_DEFECTS, defect
     dt = samples.dtype
     if num_iter == 0:
         return x0, state
     H, W = samples.shape[-2:]
     K = x0.shape[-1]
     lam = dt.type(filter_reg)
-    s0, r0, _ = atom_conv_residuals(x0, samples, y, sample_weights, filter_reg, act_min_val)
-    d = np.sqrt(sample_weights).reshape(-1, 1, 1).astype(dt) * mlu_deriv(s0, act_min_val)
+    s0, r0, _ = atom_conv_residuals(x0, samples, y, sample_weights, filter_reg, act_min_val, defect)
+    ssw = sample_weights if defect == "sw_not_sqrt" else np.sqrt(sample_weights)
+    d = ssw.reshape(-1, 1, 1).astype(dt) * mlu_deriv(s0, act_min_val)
 
     def JT(rd, rr):
         return apply_feat_transpose(samples, d * rd, K) + dt.type(math.sqrt(filter_reg)) * rr
 
     def A(p):
         Jp = d * apply_filter(samples, p, out_hw=(H, W))
-        return apply_feat_transpose(samples, d * Jp, K) + lam * p
+        return apply_feat_transpose(samples, d * Jp, K) + (0 if defect == "no_lambda_p" else lam * p)
 
     b = -JT(r0, dt.type(math.sqrt(filter_reg)) * x0)                     # optimization.py:262-265
     if direction_forget_factor == 0 or state is None:                    # :82-85
         p, rho, r_prev = None, dt.type(1.0), None
     else:
         p, rho, r_prev = state["p"], state["rho"], state["r_prev"]
-        if p is not None:
+        if p is not None and defect != "forget_rho":
             rho = rho / dt.type(direction_forget_factor)
     r = b.copy()
     delta = None
@@ -495,20 +512,24 @@ def atom_cg(x0, samples, y, sample_weights, *, filter_reg, act_min_val, num_iter
         rho1 = rho
         rho = (r * z).sum()
         if rho == 0:                                                     # :108-113
+            if trace is not None:
+                trace.append(dict(rho=0.0))
             break
+        beta = None
         if p is None:
             p = z.copy()
         else:
-            if fletcher_reeves:
+            if fletcher_reeves and not (defect == "pr_for_fr" and r_prev is not None):
                 beta = rho / rho1
             else:
                 beta = (rho - (r_prev * z).sum()) / rho1                 # :121-122
-            beta = max(beta, dt.type(0))                                 # :124
-            p = z + p * beta
+            p = z + p * max(beta, dt.type(0))                            # :124
         q = A(p)
         pq = (p * q).sum()
         alpha = rho / pq                                                 # :131
-        if not fletcher_reeves:
+        if trace is not None:
+            trace.append(dict(beta=None if beta is None else float(beta), rho=float(rho), pq=float(pq)))
+        if (not fletcher_reeves or defect == "pr_for_fr") and not (defect == "stale_r_prev" and r_prev is not None):
             r_prev = r.copy()
         delta = p * alpha if delta is None else delta + p * alpha
         if ii < num_iter - 1:                                            # :145-146

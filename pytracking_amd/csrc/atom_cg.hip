@@ -627,20 +627,49 @@ static int acg_solve_fast(const PtFast& f, float* x, const float* samples, long 
     return PT_OK;
 }
 
+// The shape checks of the update and the ONE predicate of its fused route (pt_atom_cg_f32; pt_atom_cg_route repeats them through these
+// functions): the plan, what the raw 16-byte buffer loads need from the sample and filter pointers, and a 16-byte aligned state.
+static int acg_check(long samples_stride_n, int n, int C, int H, int W, int K) {
+    if (n <= 0 || C <= 0 || H <= 0 || W <= 0 || K <= 0) return PT_ERR_SHAPE;
+    if (K * K > 16) return PT_ERR_UNSUPPORTED;
+    if (samples_stride_n < (long)C * H * W) return PT_ERR_SHAPE;
+    return PT_OK;
+}
+static bool acg_route_fast(const PtFast& f, const float* x, const float* samples, long samples_stride_n, const float* cg_state) {
+    return acg_fast_ok(f) && pt_fast_usable(f, samples, samples_stride_n, x) && ((uintptr_t)cg_state % 16) == 0;
+}
+
+extern "C" int pt_atom_cg_route(const float* x, const float* samples, long samples_stride_n, const float* cg_state, int n, int C, int H,
+                                int W, int K, int* out) {
+    if (!out) return PT_ERR_NULL;
+    for (int k = 0; k < 5; ++k) out[k] = 0;
+    if (!x || !samples || !cg_state) return PT_ERR_NULL;
+    if (int rc = acg_check(samples_stride_n, n, C, H, W, K)) return rc;
+    const PtFast f = pt_fast_plan(n, C, H, W, K, K, H, W);
+    if (acg_route_fast(f, x, samples, samples_stride_n, cg_state)) {
+        const int v[5] = {1, f.tiles, f.rem == 0 ? 0 : (f.left ? 1 : 2), f.rem, f.KSPL};
+        for (int k = 0; k < 5; ++k) out[k] = v[k];
+        return PT_OK;
+    }
+    const PtPlan p = pt_make_plan(n, C, H, W, K, K, H, W);
+    const int v[5] = {0, pt_corr_vec(p, samples, samples_stride_n, nullptr) ? 1 : 0, pt_corr_nk_arm(p), p.KS, p.KSPL};
+    for (int k = 0; k < 5; ++k) out[k] = v[k];
+    return PT_OK;
+}
+
 extern "C" int pt_atom_cg_f32(float* x, const float* samples, long samples_stride_n, const float* y,
                               const float* sample_weights, float filter_reg, float act_min_val, int n, int C, int H,
                               int W, int K, int num_iter, int fletcher_reeves, float direction_forget_factor,
                               float* cg_state, void* ws, size_t ws_bytes, void* stream) {
     if (!x || !samples || !y || !sample_weights || !cg_state || !ws) return PT_ERR_NULL;
-    if (n <= 0 || C <= 0 || H <= 0 || W <= 0 || K <= 0 || num_iter < 0) return PT_ERR_SHAPE;
-    if (K * K > 16) return PT_ERR_UNSUPPORTED;
-    if (samples_stride_n < (long)C * H * W) return PT_ERR_SHAPE;
+    if (num_iter < 0) return PT_ERR_SHAPE;
+    if (int rc = acg_check(samples_stride_n, n, C, H, W, K)) return rc;
     if (num_iter == 0) return PT_OK;                                    // optimization.py:230-231
     hipStream_t st = (hipStream_t)stream;
     if (ws_bytes < pt_atom_cg_ws_bytes(n, C, H, W, K) || ((uintptr_t)ws % 256) != 0) return PT_ERR_WORKSPACE;
     {
         PtFast f = pt_fast_plan(n, C, H, W, K, K, H, W);
-        if (acg_fast_ok(f) && pt_fast_usable(f, samples, samples_stride_n, x) && ((uintptr_t)cg_state % 16) == 0)
+        if (acg_route_fast(f, x, samples, samples_stride_n, cg_state))
             return acg_solve_fast(f, x, samples, samples_stride_n, y, sample_weights, filter_reg, act_min_val, num_iter, fletcher_reeves,
                                   direction_forget_factor, cg_state, (float*)ws, st);
     }

@@ -363,11 +363,30 @@ extern "C" size_t pt_atom_gn_ws_bytes(int n, int M, int Kc, int H, int W, int K)
 }
 
 // conv1x1(S, rows of `proj`) -> out (n,Kc,H,W), 16 projection rows per launch
+// The arms of the two three-way dispatches, each decided in ONE place that the dispatcher and pt_atom_gn_route both read.
+enum { GN_PROJ_DIRECT = 0, GN_PROJ_BANKED = 1, GN_PROJ_GROUPS = 2 };
+enum { GN_JT_GEMM = 0, GN_JT_BANKED = 1, GN_JT_GROUPS = 2 };
+static int gn_project_arm(const GnArgs& a, const void* samples, long stride_n, const void* proj, const void* out) {
+    if (pt_mf_corr1_direct_ok(samples, stride_n, proj, out, a.n, a.Kc, a.M, a.H, a.W, (long)a.Kc * a.HW)) return GN_PROJ_DIRECT;
+    return a.Kc % 16 == 0 ? GN_PROJ_BANKED : GN_PROJ_GROUPS;
+}
+static int gn_jt_arm(const GnArgs& a, const void* samples, long stride_n) {
+    if (a.Kc % 16 == 0 && a.NSG == a.n && a.HW % 4 == 0 && stride_n % 4 == 0 && ((uintptr_t)samples % 16) == 0) return GN_JT_GEMM;
+    return a.Kc % 16 == 0 ? GN_JT_BANKED : GN_JT_GROUPS;
+}
+// the dimensions of a.* that the dispatch reads (pt_atom_gn_f32 fills the pointers behind it)
+static void gn_dims(GnArgs& a, const PtPlan& pl, int n, int M, int Kc, int H, int W, int K) {
+    a.n = n; a.M = M; a.Kc = Kc; a.H = H; a.W = W; a.K = K; a.HW = H * W; a.KK = K * K;
+    a.NF = Kc * K * K; a.NP = Kc * M; a.NV = a.NF + a.NP;
+    a.KS = pl.KS; a.KSPL = pl.KSPL; a.NGRP = (Kc + 15) / 16; a.NSG = pt_mf_groups(n, std::min(Kc, 16), M, H, W, 1);
+}
+
 static int gn_project(const GnArgs& a, const float* samples, long stride_n, const float* proj, float* out, float* wT,
                       hipStream_t st) {
-    if (pt_launch_mf_corr1_direct(samples, stride_n, proj, out, a.n, a.Kc, a.M, a.H, a.W, st, (long)a.Kc * a.HW) == PT_OK)
-        return PT_OK;                                               // weights read in place, no transposition launch
-    if (a.Kc % 16 == 0) {                                           // all banks of 16 projection rows in one launch each
+    const int arm = gn_project_arm(a, samples, stride_n, proj, out);
+    if (arm == GN_PROJ_DIRECT)                                      // weights read in place, no transposition launch
+        return pt_launch_mf_corr1_direct(samples, stride_n, proj, out, a.n, a.Kc, a.M, a.H, a.W, st, (long)a.Kc * a.HW);
+    if (arm == GN_PROJ_BANKED) {                                    // all banks of 16 projection rows in one launch each
         int rc = pt_launch_mf_wtrans(proj, wT, 16, a.M, 1, st, a.NGRP);
         if (rc) return rc;
         return pt_launch_mf_corr(samples, stride_n, wT, out, a.n, 16, a.M, a.H, a.W, 1, st, (long)a.Kc * a.HW, a.NGRP);
@@ -390,7 +409,8 @@ static int gn_jt(const GnArgs& a, const PtPlan& pl, const float* samples, long s
     const PtInputGrad ig = {a.v, a.f, a.gc, a.n, a.Kc, a.H, a.W, a.K};
     int rc = pt_launch_adj(pl, a.c, (long)a.Kc * a.HW, a.R, a.gpf, st, &ig);
     if (rc) return rc;
-    if (a.Kc % 16 == 0 && a.NSG == a.n && a.HW % 4 == 0 && stride_n % 4 == 0 && ((uintptr_t)samples % 16) == 0) {
+    const int arm = gn_jt_arm(a, samples, stride_n);
+    if (arm == GN_JT_GEMM) {
         // one partial per sample: a batch of n small NT GEMMs  gpP[., i][f][m] = sum_pos gc[i][f][pos] * S[i][m][pos]
         // (K = H*W contiguous in both operands) instead of the banded LDS kernel, whose fixed cost per workgroup
         // dominates on an 18x18 map (50 us vs 6)
@@ -399,7 +419,7 @@ static int gn_jt(const GnArgs& a, const PtPlan& pl, const float* samples, long s
         ga.c_seg = 16; ga.c_segstride = (long)a.NSG * 16; ga.c_zstride = (long)16 * a.M;
         return launch_gemm(ga, st);
     }
-    if (a.Kc % 16 == 0)
+    if (arm == GN_JT_BANKED)
         return pt_launch_mf_adj(samples, stride_n, a.gc, a.gpP, a.n, 16, a.M, a.H, a.W, 1, st, (long)a.Kc * a.HW, a.NGRP);
     for (int g = 0; g < a.NGRP; ++g) {
         const int Fg = std::min(16, a.Kc - 16 * g);
@@ -407,6 +427,38 @@ static int gn_jt(const GnArgs& a, const PtPlan& pl, const float* samples, long s
                               a.M, a.H, a.W, 1, st, (long)a.Kc * a.HW);
         if (rc) return rc;
     }
+    return PT_OK;
+}
+
+// second operand set of the CG step's paired correlation: conv_same(dc, x) -> sp2 beside conv_same(c, px) -> sp1
+static PtCorrFuse gn_pair(const GnArgs& a, const float* filter) {
+    const PtCorrFuse pair = {nullptr, 0, nullptr, 0.f, nullptr, nullptr, nullptr, a.dc, filter, a.sp2};
+    return pair;
+}
+
+// The routes of one call, nothing launched.  The workspace operands enter by their carve offsets from a 256-byte aligned base (what the
+// entry requires of `ws`); the projection arm is the CG step's (operand a.p + NF in the workspace), which the linearisation shares when
+// the caller's `proj` is 16-byte aligned -- NF = Kc * K * K is a multiple of 4 wherever the direct arm's Kc % 16 == 0 holds.
+extern "C" int pt_atom_gn_route(const float* samples, long samples_stride_n, int n, int M, int Kc, int H, int W, int K, int* out) {
+    if (!out) return PT_ERR_NULL;
+    for (int k = 0; k < 10; ++k) out[k] = 0;
+    if (!samples) return PT_ERR_NULL;
+    int rc = gn_check(n, M, Kc, H, W, K);
+    if (rc) return rc;
+    if (samples_stride_n < (long)M * H * W) return PT_ERR_SHAPE;
+    const PtPlan pl = pt_make_plan(n, Kc, H, W, K, K, H, W);
+    const GnCarve cv = gn_carve(pl, n, M, Kc, H, W, K);
+    GnArgs a;
+    gn_dims(a, pl, n, M, Kc, H, W, K);
+    float* const base = (float*)(uintptr_t)256;                     // never read through: only the alignment of base + offset counts
+    a.c = base + cv.c; a.dc = base + cv.dc; a.p = base + cv.p; a.sp2 = base + cv.sp2; a.v = base + cv.v; a.gc = base + cv.gc;
+    a.f = base;                                                     // the caller's filter: the pairing does not look at its address
+    const long cs = (long)Kc * a.HW;
+    const PtInputGrad ig = {a.v, a.f, a.gc, a.n, a.Kc, a.H, a.W, a.K};
+    const int v[10] = {gn_project_arm(a, samples, samples_stride_n, a.p + a.NF, a.dc), gn_jt_arm(a, samples, samples_stride_n), a.NGRP, a.NSG,
+                       pt_corr_pair_ok(a.c, gn_pair(a, a.f)) ? 1 : 0, pt_adj_grid_z(pl, &ig), pt_corr_vec(pl, a.c, cs, nullptr) ? 1 : 0,
+                       pt_corr_nk_arm(pl), pl.KS, pl.KSPL};
+    for (int k = 0; k < 10; ++k) out[k] = v[k];
     return PT_OK;
 }
 
@@ -424,9 +476,7 @@ extern "C" int pt_atom_gn_f32(float* filter, float* proj, const float* samples, 
     if (ws_bytes < cv.total * sizeof(float) || ((uintptr_t)ws % 256) != 0) return PT_ERR_WORKSPACE;
     float* base = (float*)ws;
     GnArgs a;
-    a.n = n; a.M = M; a.Kc = Kc; a.H = H; a.W = W; a.K = K; a.HW = H * W; a.KK = K * K;
-    a.NF = Kc * K * K; a.NP = Kc * M; a.NV = a.NF + a.NP;
-    a.KS = pl.KS; a.KSPL = pl.KSPL; a.NGRP = (Kc + 15) / 16; a.NSG = pt_mf_groups(n, std::min(Kc, 16), M, H, W, 1);
+    gn_dims(a, pl, n, M, Kc, H, W, K);
     a.lf = filter_reg; a.lP = projection_reg; a.act_min = act_min_val; a.fletcher_reeves = fletcher_reeves;
     a.f = filter; a.P = proj; a.y = y; a.sw = sample_weights;
     a.d = base + cv.d; a.v = base + cv.v; a.sp1 = base + cv.sp1; a.sp2 = base + cv.sp2; a.R = base + cv.R;
@@ -458,7 +508,7 @@ extern "C" int pt_atom_gn_f32(float* filter, float* proj, const float* samples, 
             rc = gn_project(a, samples, samples_stride_n, a.p + a.NF, a.dc, wT, st);           // conv1x1(S, pP)
             if (rc) return rc;
             // conv_same(c, px) -> sp1 and conv_same(dc, x) -> sp2 in one paired launch (same shape, two operand sets)
-            const PtCorrFuse pair = {nullptr, 0, nullptr, 0.f, nullptr, nullptr, nullptr, a.dc, filter, a.sp2};
+            const PtCorrFuse pair = gn_pair(a, filter);
             rc = pt_launch_corr(pl, a.c, cs, a.p, a.sp1, st, &pair);
             if (rc == PT_ERR_UNSUPPORTED) {
                 rc = pt_launch_corr(pl, a.c, cs, a.p, a.sp1, st);                              // conv_same(c, px)

@@ -402,16 +402,38 @@ PtPlan pt_make_plan(int n, int C, int H, int W, int KH, int KW, int OH, int OW) 
     return p;
 }
 
+// What the two launchers dispatch on beyond the plan, each decided in ONE place that the launcher and the host-only route queries
+// (pt_atom_cg_route, pt_atom_gn_route) both read.
+int pt_corr_nk_arm(const PtPlan& p) {                               // NK of the k_corr<VEC, NK> instantiation: 16 | 8 | 4, 0 = run-time count
+    const int nk = p.cper / 4;
+    return nk == 16 || nk == 8 || nk == 4 ? nk : 0;
+}
+bool pt_corr_vec(const PtPlan& p, const void* feat, long stride_n, const void* copy_dst) {
+    return p.vec4 && (stride_n % 4) == 0 && ((uintptr_t)feat % 16) == 0 && ((uintptr_t)copy_dst % 16) == 0;
+}
+bool pt_corr_pair_ok(const void* feat, const PtCorrFuse& fz) {     // second operand set in the same launch (grid.z = 2)
+    return fz.filt2 && fz.spart2 && !fz.gpart && !fz.copy_dst && ((uintptr_t)fz.feat2 % 16) == ((uintptr_t)feat % 16);
+}
+bool pt_adj_vec(const PtPlan& p, const void* feat, long stride_n) {
+    return p.vec4 && (stride_n % 4) == 0 && ((uintptr_t)feat % 16) == 0;
+}
+int pt_adj_grid_z(const PtPlan& p, const PtInputGrad* ig) {
+    if (!ig) return 1;
+    // enough extra layers that the (sample, 4-row group) jobs spread over the chip (~2 workgroups per CU)
+    const int jobs = ig->n * ((ig->Kc + 3) / 4), per = pt_ceil_div(p.C, 16) * p.KSPL;
+    return 1 + std::max(1, std::min(pt_ceil_div(std::min(jobs, 512), per), 64));
+}
+
 template <bool VEC>
 static void corr_dispatch(const PtPlan& p, dim3 grid, dim3 block, hipStream_t st, const float* feat, long stride_n,
                           const float* filt, float* spart, const PtCorrFuse& fz) {
-    const int nk = p.cper / 4;
+    const int arm = pt_corr_nk_arm(p);
 #define PT_CORR_CASE(NKV)                                                                                          \
     hipLaunchKernelGGL((k_corr<VEC, NKV>), grid, block, p.corr_lds, st, feat, stride_n, filt, spart, p.n, p.C, p.H, \
                        p.W, p.KH, p.KW, p.OH, p.OW, p.cper, fz)
-    if (nk == 16) PT_CORR_CASE(16);
-    else if (nk == 8) PT_CORR_CASE(8);
-    else if (nk == 4) PT_CORR_CASE(4);
+    if (arm == 16) PT_CORR_CASE(16);
+    else if (arm == 8) PT_CORR_CASE(8);
+    else if (arm == 4) PT_CORR_CASE(4);
     else PT_CORR_CASE(0);
 #undef PT_CORR_CASE
 }
@@ -422,12 +444,11 @@ int pt_launch_corr(const PtPlan& p, const float* feat, long stride_n, const floa
     PtCorrFuse fz = {nullptr, 0, nullptr, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (fuse) fz = *fuse;
     if (fz.feat2) {                                                 // paired launch: same shape, second operand set
-        if (!fz.filt2 || !fz.spart2 || fz.gpart || fz.copy_dst) return PT_ERR_UNSUPPORTED;
-        if (((uintptr_t)fz.feat2 % 16) != ((uintptr_t)feat % 16)) return PT_ERR_UNSUPPORTED;
+        if (!pt_corr_pair_ok(feat, fz)) return PT_ERR_UNSUPPORTED;
         grid.z = 2;
     }
     if (fz.copy_dst && p.n != 1) return PT_ERR_SHAPE;
-    if (p.vec4 && (stride_n % 4) == 0 && ((uintptr_t)feat % 16) == 0 && ((uintptr_t)fz.copy_dst % 16) == 0)
+    if (pt_corr_vec(p, feat, stride_n, fz.copy_dst))
         corr_dispatch<true>(p, grid, block, st, feat, stride_n, filt, spart, fz);
     else
         corr_dispatch<false>(p, grid, block, st, feat, stride_n, filt, spart, fz);
@@ -439,13 +460,9 @@ int pt_launch_adj(const PtPlan& p, const float* feat, long stride_n, const float
                   const PtInputGrad* ig) {
     dim3 grid(pt_ceil_div(p.C, 16), p.KSPL), block(512);
     PtInputGrad g = {nullptr, nullptr, nullptr, 0, 0, 0, 0, 0};
-    if (ig) {
-        // enough extra layers that the (sample, 4-row group) jobs spread over the chip (~2 workgroups per CU)
-        g = *ig;
-        const int jobs = g.n * ((g.Kc + 3) / 4), per = (int)(grid.x * grid.y);
-        grid.z = 1 + std::max(1, std::min(pt_ceil_div(std::min(jobs, 512), per), 64));
-    }
-    if (p.vec4 && (stride_n % 4) == 0 && ((uintptr_t)feat % 16) == 0)
+    if (ig) g = *ig;
+    grid.z = pt_adj_grid_z(p, ig);
+    if (pt_adj_vec(p, feat, stride_n))
         hipLaunchKernelGGL(k_adj<true>, grid, block, 0, st, feat, stride_n, R, gpart, p.n, p.C, p.HW, p.KK, p.NG, p.gper, g);
     else
         hipLaunchKernelGGL(k_adj<false>, grid, block, 0, st, feat, stride_n, R, gpart, p.n, p.C, p.HW, p.KK, p.NG, p.gper, g);

@@ -838,11 +838,16 @@ static int mf_launch_corr1(const float* feat, long stride_n, const float* w, boo
 
 // conv1x1 with the weights read from the (Ftot, C) matrix itself, Ftot = 16 * groups rows (no pt_launch_mf_wtrans in front).
 // PT_ERR_UNSUPPORTED when the shapes / alignments do not allow it: the caller falls back to wtrans + pt_launch_mf_corr.
+bool pt_mf_corr1_direct_ok(const void* feat, long stride_n, const void* filt, const void* scores, int n, int Ftot, int C, int H, int W,
+                           long out_stride_n) {
+    const int HW = H * W;
+    if (n <= 0 || Ftot <= 0 || Ftot % 16 || C % 16 || HW % 4 || stride_n % 4 || out_stride_n % 4) return false;
+    return !(((uintptr_t)feat % 16) || ((uintptr_t)filt % 16) || ((uintptr_t)scores % 16) || (long)C * HW >= (1L << 30));
+}
 int pt_launch_mf_corr1_direct(const float* feat, long stride_n, const float* filt, float* scores, int n, int Ftot, int C,
                               int H, int W, hipStream_t st, long out_stride_n) {
     const int HW = H * W;
-    if (n <= 0 || Ftot <= 0 || Ftot % 16 || C % 16 || HW % 4 || stride_n % 4 || out_stride_n % 4) return PT_ERR_UNSUPPORTED;
-    if (((uintptr_t)feat % 16) || ((uintptr_t)filt % 16) || ((uintptr_t)scores % 16) || (long)C * HW >= (1L << 30)) return PT_ERR_UNSUPPORTED;
+    if (!pt_mf_corr1_direct_ok(feat, stride_n, filt, scores, n, Ftot, C, H, W, out_stride_n)) return PT_ERR_UNSUPPORTED;
     return mf_launch_corr1(feat, stride_n, filt, true, scores, out_stride_n, n, 16, C, HW, Ftot / 16, 0, (long)16 * HW, 1, st);
 }
 

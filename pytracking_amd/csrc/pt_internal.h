@@ -54,6 +54,17 @@ int pt_launch_corr(const PtPlan& p, const float* feat, long stride_n, const floa
                    const PtCorrFuse* fuse = nullptr);
 int pt_launch_adj(const PtPlan& p, const float* feat, long stride_n, const float* R, float* gpart, hipStream_t st,
                   const PtInputGrad* ig = nullptr);
+// What pt_launch_corr / pt_launch_adj dispatch on beyond the plan, each decided in ONE place that the launcher and the host-only route
+// queries (pt_atom_cg_route, pt_atom_gn_route) both read:
+//   pt_corr_nk_arm    NK of the k_corr<VEC, NK> instantiation (16 | 8 | 4; 0 = the run-time k-step count)
+//   pt_corr_vec       VEC of k_corr (16-byte feature loads);  pt_adj_vec: VEC of k_adj
+//   pt_corr_pair_ok   whether the second operand set of `fz` can ride on the launch (grid.z = 2)
+//   pt_adj_grid_z     grid.z of k_adj: 1 + the input-gradient layers (1 without an input gradient)
+int pt_corr_nk_arm(const PtPlan& p);
+bool pt_corr_vec(const PtPlan& p, const void* feat, long stride_n, const void* copy_dst);
+bool pt_corr_pair_ok(const void* feat, const PtCorrFuse& fz);
+bool pt_adj_vec(const PtPlan& p, const void* feat, long stride_n);
+int pt_adj_grid_z(const PtPlan& p, const PtInputGrad* ig);
 // scores[i][o] = sum_ks spart[ks][i][o]
 int pt_launch_sum_slices(const float* part, float* out, int slices, size_t count, hipStream_t st);
 // R (im2col of the residual map, MFMA-B layout) from inp (n, OH, OW)
@@ -142,6 +153,9 @@ int pt_launch_mf_corr_tm(const float* feat, long stride_n, const float* w_tap_ma
                          int H, int W, int ksplit, hipStream_t st);          // 3x3, weights (Ftot, 9, C); partial maps
 int pt_launch_mf_corr1_direct(const float* feat, long stride_n, const float* filt, float* scores, int n, int Ftot, int C,
                               int H, int W, hipStream_t st, long out_stride_n);     // 1x1, weights (Ftot, C) untransposed
+// the predicate of pt_launch_mf_corr1_direct (which returns PT_ERR_UNSUPPORTED where it is false), nothing launched
+bool pt_mf_corr1_direct_ok(const void* feat, long stride_n, const void* filt, const void* scores, int n, int Ftot, int C, int H, int W,
+                           long out_stride_n);
 int pt_mf_corr_splits(int n, int F, int C, int H, int W, int K);               // channel splits used with a partial workspace
 size_t pt_mf_corr_part_floats(int n, int F, int C, int H, int W, int K);         // its size (0: no split for this shape)
 // `sq`: optional rider of the channel-split reduction (LWL few-shot learner: |sw * F g|^2 of steepestdescent.py:76-80): when the

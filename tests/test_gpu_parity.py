@@ -1302,13 +1302,19 @@ def test_atom_cg_direction_forgetting_golden(tag):
 
 @pytest.mark.parametrize("tag", ["pr", "fr", "pr0", "fr0"])
 def test_atom_cg_compressed_channels_golden(tag):
-    """C = 64, 4x4 filter -- the shape class of ATOM's online update, served by the fused path of csrc/atom_cg.hip (CG
-    recurrences in the prologue of the correlation launch, pointwise stage in its epilogue): Polak-Ribiere / Fletcher-Reeves,
-    with / without direction forgetting, state carried over three run() calls, against the reference's autograd CG."""
+    """C = 64, 4x4 filter -- the channel count and filter of ATOM's online update -- on a 12x12 map: two position tiles, so the GENERIC
+    route of csrc/atom_cg.hip (the fused one needs 4 or 5 tiles; tests/test_gpu_atom_routes.py runs this golden's 16x16 twin and every
+    other cell of it): Polak-Ribiere / Fletcher-Reeves, with / without direction forgetting, state carried over three run() calls,
+    against the reference's autograd CG."""
+    import ctypes
+    from pytracking_amd import _lib
     from pytracking_amd.optimization import ConjugateGradient, ConvProblem, MLU
     g = load_golden("atom_cg_c64")
     x0, samples, y, sw = synth.atom_problem(int(g["seed"]), int(g["n"]), small=dict(C=64, H=int(g["H"]), W=int(g["W"])))
     x = [T(x0.copy())[None].clone()]
+    route = (ctypes.c_int * 5)()
+    assert _lib.lib().pt_atom_cg_route(x[0].data_ptr(), 256, 64 * 144, 256, int(g["n"]), 64, int(g["H"]), int(g["W"]), 4, route) == 0
+    assert list(route) == [0, 1, 4, 4, 1]                               # generic, 16-byte loads, 4 k-steps per slice, 4 channel slices, 1 adjoint slice
     prob = ConvProblem([T(samples)], [T(y)[:, None]], [synth.ATOM18["filter_reg"]], [T(sw)], MLU(synth.ATOM18["act_min_val"]))
     opt = ConjugateGradient(prob, x, fletcher_reeves=bool(int(g[f"{tag}_fr"])), direction_forget_factor=float(g[f"{tag}_forget"]))
     for call, iters in enumerate(g["iters"]):
