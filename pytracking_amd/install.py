@@ -78,6 +78,10 @@ What gets rebound (import path = contract; nothing in the reference tree is edit
   ltr.models.transformer.heads.FPN, ltr.models.transformer.heads.DenseBoxRegressor
                                              (TaMOs two-level FPN and multi-object box regressor; only with install(tamos=True))
                                                                                       -> pytracking_amd.tamos
+  pytracking.tracker.tamos.tamos.TaMOs.classify_target / localize_target / direct_bbox_regression / encode_bbox / get_label_function
+                                             (TaMOs per-frame multi-object read-out and training targets, libpt_mot.so; only with
+                                             install(tamos_readout=True), meant to go with tamos=True)
+                                                                                      -> pytracking_amd.tamos_readout
 
 Dispatch rule of the rebound *functions*: device fp32 tensors of a shape the gfx950 kernels cover go to the C ABI;
 everything else (CPU tensors, dilations, grouped filters, K*K > 16, more than 16 filters) is outside the hot path and
@@ -373,6 +377,26 @@ def _install_tamos():
                 and isinstance(output_dim, int) and output_dim % 64 == 0 and 0 < output_dim <= 512)
 
     _rebind(hmod, "FPN", _choosing_class(hmod.FPN, fpn_covered, _ta.FPN, "FPN: configuration outside the gfx950 hot path"))
+
+
+def _install_tamos_readout():
+    """TaMOs per-frame multi-object read-out (`pytracking.tracker.tamos.tamos.TaMOs`, only with install(tamos_readout=True)): five methods of
+    the unmodified class.  `classify_target` runs the reference method and queues ONE read-out launch for all active objects on its two
+    outputs; `localize_target` and `direct_bbox_regression` answer from that stash after the frame's one wait; `encode_bbox` and
+    `get_label_function` build the training targets on the device.  Every call the stash does not cover goes to the reference method."""
+    from . import tamos_readout as _tr
+    try:
+        tmod = importlib.import_module("pytracking.tracker.tamos.tamos")
+        TensorList = importlib.import_module("pytracking.libs.tensorlist").TensorList
+    except Exception:                   # pytracking side not importable (missing cv2 ...)
+        return
+    cls = tmod.TaMOs
+    for name, make in (("classify_target", _tr.make_classify_target), ("localize_target", _tr.make_localize_target),
+                       ("direct_bbox_regression", _tr.make_direct_bbox_regression), ("encode_bbox", _tr.make_encode_bbox),
+                       ("get_label_function", functools.partial(_tr.make_get_label_function, TensorList=TensorList))):
+        ref = vars(cls)[name]
+        covered, fast = make(ref)
+        _rebind(cls, name, _dispatcher(ref, "TaMOs." + name, covered, fast, f"TaMOs.{name}: call outside the gfx950 read-out"))
 
 
 def _install_clf_head(feature_heads=False):
@@ -996,7 +1020,8 @@ def _install_atom_cg():
 
 def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=True, iou_refine=True, preprocessing=True,
             candidate_matching=True, kys=True, iou_feat=False, label_encoder=False, decoder=False, feature_heads=False,
-            rts_fusion=False, seg_readout=False, eco=False, tamos=False, box_encoder=False, eco_init=False, iou_mod=False):
+            rts_fusion=False, seg_readout=False, eco=False, tamos=False, box_encoder=False, eco_init=False, iou_mod=False,
+            tamos_readout=False):
     """Rebind the boundary symbols.  Call after the reference is importable (`sys.path`) and before networks or
     trackers are constructed.  Idempotent.  If an installer raises, what was rebound so far is undone before the exception
     propagates (an optional reference module that does not import is not a failure: its family is skipped)."""
@@ -1019,7 +1044,8 @@ def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=T
                                 (iou_feat, _install_iou_feat), (label_encoder, _install_label_encoder),
                                 (decoder, _install_lwl_decoder), (rts_fusion, _install_rts_fusion),
                                 (seg_readout, _install_seg_readout), (eco, _install_eco), (tamos, _install_tamos),
-                                (box_encoder, _install_box_encoder), (eco_init, _install_eco_init), (iou_mod, _install_iou_mod)):
+                                (box_encoder, _install_box_encoder), (eco_init, _install_eco_init), (iou_mod, _install_iou_mod),
+                                (tamos_readout, _install_tamos_readout)):
             if flag:
                 installer()
     except BaseException:

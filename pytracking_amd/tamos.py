@@ -24,8 +24,8 @@ What `pytracking/tracker/tamos/tamos.py:308-317` runs behind the predictor is he
     DenseBoxRegressor(num_channels, project_filter).forward(feat, filter) with T filters per sequence               heads.py:119-141
 
 both on the direct 3x3 token convolution of `pytracking_amd/csrc/tomp.hip` (pt_fpn2_f32, pt_tamos_bbreg_f32).  Not here: training; the
-`box_enc` / `label_enc` variants refused above; `TaMOs.track`'s own host glue, which runs unchanged -- including `classify_target`
-computing a classification FPN map it never reads when `cls_feature_type == 'trafo'`.
+`box_enc` / `label_enc` variants refused above; `classify_target` computing a classification FPN map it never reads when
+`cls_feature_type == 'trafo'`.  What `TaMOs.track` does per object with these outputs is `pytracking_amd/tamos_readout.py`.
 """
 import ctypes
 from collections import OrderedDict
