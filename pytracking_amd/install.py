@@ -82,6 +82,10 @@ What gets rebound (import path = contract; nothing in the reference tree is edit
                                              (TaMOs per-frame multi-object read-out and training targets, libpt_mot.so; only with
                                              install(tamos_readout=True), meant to go with tamos=True)
                                                                                       -> pytracking_amd.tamos_readout
+  pytracking.tracker.atom.atom.ATOM.localize_target
+                                             (ATOM's per-frame score localisation: Fourier upsampling, window, both peaks and the
+                                             outcome, libpt_loc.so; only with install(atom_localize=True))
+                                                                                      -> pytracking_amd.atom_localize
 
 Dispatch rule of the rebound *functions*: device fp32 tensors of a shape the gfx950 kernels cover go to the C ABI;
 everything else (CPU tensors, dilations, grouped filters, K*K > 16, more than 16 filters) is outside the hot path and
@@ -397,6 +401,23 @@ def _install_tamos_readout():
         ref = vars(cls)[name]
         covered, fast = make(ref)
         _rebind(cls, name, _dispatcher(ref, "TaMOs." + name, covered, fast, f"TaMOs.{name}: call outside the gfx950 read-out"))
+
+
+def _install_atom_localize():
+    """ATOM's per-frame score localisation (`pytracking.tracker.atom.atom.ATOM.localize_target`, atom.py:304-406; only with
+    install(atom_localize=True)): the Fourier interpolation onto the output grid, the output window, both peaks and every outcome of
+    `localize_advanced` in two launches and one wait.  `scale_ind` comes back as a CPU tensor, which atom.py:252 needs under torch 2.  CPU or
+    non-float32 scores, more than one feature block, `debug >= 2` and sizes outside include/pt_loc.h go to the reference method -- which
+    calls torch.rfft / torch.irfft and therefore works only next to `install(eco=True)`'s Fourier tools.  Off by default: the set a default
+    install() rebinds is pinned."""
+    from . import atom_localize as _al
+    try:
+        cls = importlib.import_module("pytracking.tracker.atom.atom").ATOM
+    except Exception:                   # pytracking side not importable (missing cv2 ...)
+        return
+    ref = vars(cls)["localize_target"]
+    _rebind(cls, "localize_target", _dispatcher(ref, "ATOM.localize_target", _al.covered_localize_target, _al.tracker_localize_target,
+                                                "ATOM.localize_target: call outside the gfx950 localisation"))
 
 
 def _install_clf_head(feature_heads=False):
@@ -1021,7 +1042,7 @@ def _install_atom_cg():
 def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=True, iou_refine=True, preprocessing=True,
             candidate_matching=True, kys=True, iou_feat=False, label_encoder=False, decoder=False, feature_heads=False,
             rts_fusion=False, seg_readout=False, eco=False, tamos=False, box_encoder=False, eco_init=False, iou_mod=False,
-            tamos_readout=False):
+            tamos_readout=False, atom_localize=False):
     """Rebind the boundary symbols.  Call after the reference is importable (`sys.path`) and before networks or
     trackers are constructed.  Idempotent.  If an installer raises, what was rebound so far is undone before the exception
     propagates (an optional reference module that does not import is not a failure: its family is skipped)."""
@@ -1045,7 +1066,7 @@ def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=T
                                 (decoder, _install_lwl_decoder), (rts_fusion, _install_rts_fusion),
                                 (seg_readout, _install_seg_readout), (eco, _install_eco), (tamos, _install_tamos),
                                 (box_encoder, _install_box_encoder), (eco_init, _install_eco_init), (iou_mod, _install_iou_mod),
-                                (tamos_readout, _install_tamos_readout)):
+                                (tamos_readout, _install_tamos_readout), (atom_localize, _install_atom_localize)):
             if flag:
                 installer()
     except BaseException:
