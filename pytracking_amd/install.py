@@ -86,6 +86,11 @@ What gets rebound (import path = contract; nothing in the reference tree is edit
                                              (ATOM's per-frame score localisation: Fourier upsampling, window, both peaks and the
                                              outcome, libpt_loc.so; only with install(atom_localize=True))
                                                                                       -> pytracking_amd.atom_localize
+  pytracking.tracker.{dimp.dimp.DiMP, kys.kys.KYS, tomp.tomp.ToMP, dimp_simple.dimp_simple.DiMPSimple, tamos.tamos.TaMOs,
+  keep_track.keep_track.KeepTrack, atom.atom.ATOM, lwl.lwl.LWL, rts.rts.RTS}.update_memory
+                                             (the per-frame sample-memory update: weight decay, slot arg-min, floor and the stores of
+                                             the sample, label, box and mask, libpt_mem.so; only with install(memory=True))
+                                                                                      -> pytracking_amd.memory_update
 
 Dispatch rule of the rebound *functions*: device fp32 tensors of a shape the gfx950 kernels cover go to the C ABI;
 everything else (CPU tensors, dilations, grouped filters, K*K > 16, more than 16 filters) is outside the hot path and
@@ -418,6 +423,25 @@ def _install_atom_localize():
     ref = vars(cls)["localize_target"]
     _rebind(cls, "localize_target", _dispatcher(ref, "ATOM.localize_target", _al.covered_localize_target, _al.tracker_localize_target,
                                                 "ATOM.localize_target: call outside the gfx950 localisation"))
+
+
+def _install_memory():
+    """The per-frame sample-memory update (`update_memory` of DiMP, KYS, ToMP, DiMPSimple, TaMOs, KeepTrack, ATOM, LWL and RTS; only with
+    install(memory=True)): the weight decay, the arg-min of the slot, the renormalisation, the `init_samples_minimum_weight` floor and the
+    stores of the sample and its label / box / mask in two launches of libpt_mem.so, without a host wait while the memory fills and with
+    one behind it.  A tracker on the CPU, memories that are not contiguous float32, sizes outside include/pt_mem.h and a source that overlaps
+    its memory go to the reference method.  The `update_sample_weights*` methods stay the reference's (`init_memory` calls them).  Off by
+    default: the set a default install() rebinds is pinned."""
+    from . import memory_update as _mu
+    for name, entry in _mu.TABLE.items():
+        try:
+            cls = getattr(importlib.import_module(entry.module), name)
+        except Exception:               # pytracking side not importable (missing cv2 ...)
+            continue
+        ref = vars(cls)["update_memory"]
+        covered, fast = _mu.make(name)
+        _rebind(cls, "update_memory", _dispatcher(ref, name + ".update_memory", covered, fast,
+                                                  f"{name}.update_memory: call outside the gfx950 memory update"))
 
 
 def _install_clf_head(feature_heads=False):
@@ -1042,7 +1066,7 @@ def _install_atom_cg():
 def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=True, iou_refine=True, preprocessing=True,
             candidate_matching=True, kys=True, iou_feat=False, label_encoder=False, decoder=False, feature_heads=False,
             rts_fusion=False, seg_readout=False, eco=False, tamos=False, box_encoder=False, eco_init=False, iou_mod=False,
-            tamos_readout=False, atom_localize=False):
+            tamos_readout=False, atom_localize=False, memory=False):
     """Rebind the boundary symbols.  Call after the reference is importable (`sys.path`) and before networks or
     trackers are constructed.  Idempotent.  If an installer raises, what was rebound so far is undone before the exception
     propagates (an optional reference module that does not import is not a failure: its family is skipped)."""
@@ -1066,7 +1090,8 @@ def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=T
                                 (decoder, _install_lwl_decoder), (rts_fusion, _install_rts_fusion),
                                 (seg_readout, _install_seg_readout), (eco, _install_eco), (tamos, _install_tamos),
                                 (box_encoder, _install_box_encoder), (eco_init, _install_eco_init), (iou_mod, _install_iou_mod),
-                                (tamos_readout, _install_tamos_readout), (atom_localize, _install_atom_localize)):
+                                (tamos_readout, _install_tamos_readout), (atom_localize, _install_atom_localize),
+                                (memory, _install_memory)):
             if flag:
                 installer()
     except BaseException:
