@@ -50,6 +50,14 @@
 #ifndef PT_C2_MINW
 #define PT_C2_MINW 6
 #endif
+// k_corr2, mixed pairs with uniform tap steps: 1 = the shift-and-add of both samples in ONE round when the workgroup has 2 * roundup64(OO)
+// threads, 0 = one round per sample (profiles/r12a_pass_wave_arbitration.txt: DiMP-50 frame 94.3 -> 92.1 us).  The same record holds
+// what did NOT pay and is not in the code: a static wave priority (s_setprio) for the waves barrier 2 of k_corr2 and the barriers of
+// k_adj2 wait for -- four placements / levels in k_corr2 (the leftover-quad waves do not move: 4.13 -> 4.08 us), three in k_adj2 (the
+// two waves of a SIMD swap their timings, the workgroup lasts as long), the frame at best 0.3 us shorter, a quarter of the margin asked.
+#ifndef PT_C2_SA1
+#define PT_C2_SA1 1
+#endif
 #ifndef PT_ADJ_PD
 #define PT_ADJ_PD 3      // k_adj2: feature groups requested in FRONT of the prologue's LDS work.  (The round-3 sweep 3 / 4 / 6 / 8 / 12 / 16
                          // -> 8.08 / 8.36 / 8.50 / 8.67 / 8.84 / 9.0 us measured these prologue requests only: inside the loop the compiler
@@ -605,6 +613,47 @@ __global__ __launch_bounds__(1024, (NK <= 8 && NH == 2 ? PT_C2_MINW : 4)) void k
     const float inv_ow = 1.0f / (float)a.OW;
     const int nsm = pair ? 2 : 1;                                   // samples whose tap planes this workgroup holds
     if (a.KH == 4 && a.KW == 4) {                                   // the trackers' filter size: fully unrolled
+      if constexpr (MIX && PT_C2_SA1 != 0) {
+        // Mixed pairs (NH == 1): a workgroup with 2 * roundup64(OO) threads (18x18 maps: 2 * 384 = 768) runs both samples in ONE round, the
+        // first half of its waves on sample 0 and the second half on sample 1.  In the two rounds below the second half of the waves has no
+        // output in either round, and the second sample starts when the first has ended (stamps, profiles/r12a_pass_wave_arbitration.txt:
+        // barrier 2 -> end 1.10 us, here 0.6).  Within a thread nothing changes -- the reads, the masks and the order of the 16 adds are
+        // those of the loop below -- so every score keeps its bits (tests/test_gpu_corr2_pair_epilogue.py).  DELIBERATELY a second copy
+        // of that loop's body: written once for both, every other arm compiles to other code, and those arms are held instruction-identical.
+        static_assert(NH == 1, "mixed pairs have one k-step set per wave");
+        const int hthreads = nthreads >> 1;                         // tiles + 1 waves
+        if (a.sa_direct && 2 * ((OO + 63) & ~63) <= nthreads) {     // uniform per workgroup
+            const int s2 = wave >= (hthreads >> 6) ? 1 : 0;         // scalar: which sample this wave adds up
+            const int o = (int)threadIdx.x - s2 * hthreads;
+            if (o < OO) {
+                const float* __restrict__ T0 = lds + nsl + (long)s2 * KK * hHWp;
+                const pt_gf out = a.spart + ((long)x * a.n + (2 * i0 + s2)) * OO;
+                const int su = 4 * hHWp + a.W, sv = hHWp + 1;
+                const int y = fdiv(o, inv_ow), xx0 = o - y * a.OW;
+                const int base = (y - 2) * a.W + (xx0 - 2);
+                float t0[16];                                       // all 16 LDS reads requested before the first use, see below
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) t0[u * 4 + v] = T0[base + (u * su + v * sv)];
+                int rok[4], cok[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) rok[u] = (unsigned)(y + u - 2) < (unsigned)a.H ? -1 : 0;
+#pragma unroll
+                for (int v = 0; v < 4; ++v) cok[v] = (unsigned)(xx0 + v - 2) < (unsigned)a.W ? -1 : 0;
+                __builtin_amdgcn_sched_barrier(0);
+                float tv[16];
+#pragma unroll
+                for (int q = 0; q < 16; ++q) tv[q] = __builtin_bit_cast(float, __builtin_bit_cast(int, t0[q]) & (rok[q >> 2] & cok[q & 3]));
+                float s = 0.f;
+#pragma unroll
+                for (int q = 0; q < 16; ++q) s += tv[q];
+                out[o] = s;
+            }
+            PT_STAMP(a, 7);
+            return;
+        }
+      }
       for (int s2 = 0; s2 < nsm; ++s2) {                            // uniform: one round of the block per sample of the pair
         const float* __restrict__ T0 = lds + nsl + (long)s2 * NH * KK * hHWp;
         const float* __restrict__ T1 = T0 + (long)KK * hHWp;      // second k-step half (NH == 2)

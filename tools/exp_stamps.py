@@ -104,9 +104,28 @@ def simd_table(t, hw):
     for w in range(nw):
         print(f"   wave {w:2d}: loop {np.nanmean(loop[:, w]):5.2f} us, done at {np.nanmean(t[:, w, 4]):5.2f}, shares its SIMD with "
               f"{np.nanmean(share[:, w]) - 1:4.2f} others")
+    kind_table(t, nw)
     wg_last = np.nanmax(t[:, :, 4], axis=1) - np.nanmin(t[:, :, 3], axis=1)
     wg_first = np.nanmin(t[:, :, 4], axis=1) - np.nanmin(t[:, :, 3], axis=1)
     print(f"   per workgroup, first barrier-1 exit -> MFMA loop done: first wave {np.mean(wg_first):5.2f} us, last wave {np.mean(wg_last):5.2f} us")
+
+
+def kind_table(t, nw):
+    """k_corr2, mixed pairs (2 tiles + 2 waves, csrc/fast_passes.hip: waves 0..3 = (sample, position half) of tile 0, then the full tiles
+    of sample 0 and of sample 1): MFMA loop, wait at barrier 2 and the epilogue (shift-and-add: barrier 2 -> end) per wave kind."""
+    if nw < 6 or nw % 2:
+        return
+    full = (nw - 4) // 2
+    kinds = (("half 0 + leftover quads", [0, 2]), ("half 1", [1, 3]), ("full tiles of sample 0", list(range(4, 4 + full))),
+             ("full tiles of sample 1", list(range(4 + full, nw))))
+    seg = lambda k0, k1, ws: np.nanmean((t[:, :, k1] - t[:, :, k0])[:, ws])
+    print("   per wave kind (mixed pair):          barrier 1 -> loop done | loop done -> T written | at barrier 2 | barrier 2 -> end | end at")
+    for name, ws in kinds:
+        print(f"   {name:24s} (waves {','.join(map(str, ws)):9s})   {seg(3, 4, ws):5.2f}   {seg(4, 5, ws):5.2f}   {seg(5, 6, ws):5.2f}   "
+              f"{seg(6, 7, ws):5.2f}   {np.nanmean(t[:, ws, 7]):5.2f}")
+    ep = t[:, :, 7] - t[:, :, 6]
+    print("   epilogue per wave (barrier 2 -> end): " + " ".join(f"w{w}:{np.nanmean(ep[:, w]):4.2f}" for w in range(nw)))
+    print(f"   per workgroup: last barrier-2 exit -> last wave's end {np.mean(np.nanmax(t[:, :, 7], axis=1) - np.nanmax(t[:, :, 6], axis=1)):5.2f} us")
 
 
 def adj_table(t, hw, n, c, nwg):
