@@ -91,6 +91,10 @@ What gets rebound (import path = contract; nothing in the reference tree is edit
                                              (the per-frame sample-memory update: weight decay, slot arg-min, floor and the stores of
                                              the sample, label, box and mask, libpt_mem.so; only with install(memory=True))
                                                                                       -> pytracking_amd.memory_update
+  ltr.models.backbone.resnet.ResNet.forward, ltr.models.backbone.resnet_mrcnn.ResNet.forward
+                                             (the ResNet backbone forward: stem, pool and residual blocks up to the deepest requested
+                                             layer, libpt_bbn.so; only with install(backbone=True))
+                                                                                      -> pytracking_amd.backbone
 
 Dispatch rule of the rebound *functions*: device fp32 tensors of a shape the gfx950 kernels cover go to the C ABI;
 everything else (CPU tensors, dilations, grouped filters, K*K > 16, more than 16 filters) is outside the hot path and
@@ -442,6 +446,22 @@ def _install_memory():
         covered, fast = _mu.make(name)
         _rebind(cls, "update_memory", _dispatcher(ref, name + ".update_memory", covered, fast,
                                                   f"{name}.update_memory: call outside the gfx950 memory update"))
+
+
+def _install_backbone():
+    """The ResNet backbone forward (`ResNet.forward` of ltr/models/backbone/resnet.py and resnet_mrcnn.py; only with
+    install(backbone=True)): the stem, the max-pool and the residual blocks up to the deepest requested layer in libpt_bbn.so.  CPU,
+    non-fp32 or non-contiguous input, training mode or enabled gradients, dilated networks, BasicBlock(use_bn=False), a request for `fc` /
+    'default' or an unknown layer and sizes outside include/pt_bbn.h go to the reference method.  Both classes count as `ResNet.forward`.
+    Off by default: the set a default install() rebinds is pinned."""
+    from . import backbone as _bb
+    for modname in ("ltr.models.backbone.resnet", "ltr.models.backbone.resnet_mrcnn"):
+        try:
+            cls = importlib.import_module(modname).ResNet
+        except Exception:               # ltr side not importable
+            continue
+        _rebind(cls, "forward", _dispatcher(vars(cls)["forward"], "ResNet.forward", _bb.covered, functools.partial(_bb.forward, checked=True),
+                                            "ResNet.forward: call outside the gfx950 backbone"))
 
 
 def _install_clf_head(feature_heads=False):
@@ -1066,7 +1086,7 @@ def _install_atom_cg():
 def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=True, iou_refine=True, preprocessing=True,
             candidate_matching=True, kys=True, iou_feat=False, label_encoder=False, decoder=False, feature_heads=False,
             rts_fusion=False, seg_readout=False, eco=False, tamos=False, box_encoder=False, eco_init=False, iou_mod=False,
-            tamos_readout=False, atom_localize=False, memory=False):
+            tamos_readout=False, atom_localize=False, memory=False, backbone=False):
     """Rebind the boundary symbols.  Call after the reference is importable (`sys.path`) and before networks or
     trackers are constructed.  Idempotent.  If an installer raises, what was rebound so far is undone before the exception
     propagates (an optional reference module that does not import is not a failure: its family is skipped)."""
@@ -1091,7 +1111,7 @@ def install(strict=False, atom_cg=True, tomp=True, clf_head=True, localization=T
                                 (seg_readout, _install_seg_readout), (eco, _install_eco), (tamos, _install_tamos),
                                 (box_encoder, _install_box_encoder), (eco_init, _install_eco_init), (iou_mod, _install_iou_mod),
                                 (tamos_readout, _install_tamos_readout), (atom_localize, _install_atom_localize),
-                                (memory, _install_memory)):
+                                (memory, _install_memory), (backbone, _install_backbone)):
             if flag:
                 installer()
     except BaseException:
